@@ -7,10 +7,12 @@ A "step" is one pass of the hot path over one batch of synthetic reads already r
 
 N = 1 (default): the workload BASELINE.json's metric is quoted on -- 100k x 150 bp reads, k=12, with the survey's
 headline synthetic shape D=64 dims, C=65 classes: fused count->twist (kpop_dev_count_twist), then
-rowwise distances to the class vectors (kpop_dev_distance_rowwise).  The same line also carries, measured in the same
-run and never mixed into `value`: the PCIe-inclusive rate through the host-buffer entry points, the file-to-file rate
-through the drop-in binaries, the CPU baseline, and BASELINE config 4 (1M reads) on this one GPU -- the N = 1 point of
-the strong-scaling curve below.
+rowwise distances to the class vectors (kpop_dev_distance_rowwise).  A plain run sets up, warms up, times --steps steps
+and prints the line.  With --full the same line also carries, measured in the same run after the timed steps and never
+mixed into `value`: the PCIe-inclusive rate through the host-buffer entry points, the file-to-file rate through the
+drop-in binaries, the CPU baseline with its parity check, BASELINE configs 2, 3 and 5, the dimension sweep, every leg's
+HBM traffic from rocprofv3 --pmc child passes, and BASELINE config 4 (1M reads) on this one GPU -- the N = 1 point of the
+strong-scaling curve below.  --dump-outputs DIR writes the last timed step's twisted rows and distances as .npy files.
 
 N > 1: BASELINE config 4, STRONG scaling -- 1M x 150 bp reads IN TOTAL, cut into contiguous shards, one rank per GPU;
 every rank twists its shard in chunks, the RCCL all-gather of chunk c (xGMI, own stream) travels under the twist of
@@ -43,6 +45,7 @@ MFMA_F64_PEAK_TFLOPS = 78.6  # MI355X f64 matrix peak (256 CUs x 4
 MALL_GATHER_PEAK_GBS = 8600.0  # random whole rows of a table that sits in the 256 MiB Infinity Cache (MI355X_MICROARCH.md, 'Indexed rows')
 L2_PEAK_GBS = 34500.0  # MI355X_MICROARCH.md: aggregate L2 bandwidth, 34.5 TB/s
 XGMI_DIRECT_ESTIMATE_MS = 0.42  # 64 MB per shard over 7 links x 153 GB/s, one shard per link
+DUMP_BYTES, DUMP_SEED = 60000000, 0  # --dump-outputs: at most this many bytes of rows in all (64 MB with room for the headers); the sample's seed
 
 
 def parse_args(argv=None):
@@ -67,10 +70,18 @@ def parse_args(argv=None):
                     help="all GPUs from ONE process through the C ABI (kpop_init_devices + kpop_sharded_*: one host thread per "
                          "device, hipMemcpyPeerAsync all-gather) instead of one torch.distributed rank per GPU with RCCL")
     ap.add_argument("--queries", type=int, default=1024, help="config4: rows (in total) of the all-vs-all summary")
+    ap.add_argument("--full", action="store_true",
+                    help="1-GPU headline: after the timed steps also run the CPU baseline with its parity check and the extra legs (PCIe-inclusive, "
+                         "config 4 on this GPU, file to file, configs 2 / 3 / 5, the dimension sweep, the rocprofv3 --pmc traffic passes); "
+                         "without it the run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="1-GPU headline: after the timed steps write what the last step computed as DIR/twisted.npy (reads x dims) and "
+                         "DIR/distances.npy (reads x classes), float64; when both together exceed %d bytes, the same seeded sample of rows of "
+                         "each (numpy default_rng(%d).choice, sorted)" % (DUMP_BYTES, DUMP_SEED))
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU time of the cpu_baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and its parity check")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the PCIe-inclusive, file-to-file and config-4 legs of the 1-GPU line")
+                    help="with --full: skip the PCIe-inclusive, file-to-file, config-4 and configs 2 / 3 / 5 legs of the 1-GPU line")
     ap.add_argument("--no-children", action="store_true",
                     help="skip the legs that start child processes (the rocprofv3 --pmc traffic passes, the file-to-file CLIs): for running the whole line under a profiler")
     ap.add_argument("--f2f-reads", type=int, default=1000000, help="reads of the file-to-file leg")
@@ -339,7 +350,7 @@ class Rank:
         return out
 
     # -- the headline job: reads resident, count->twist then distances to the classes, no collective
-    def run_headline(self, n_local, first, steps, warmup, want_outputs=0):
+    def run_headline(self, n_local, first, steps, warmup, want_outputs=0, dump=False):
         t, a = self.torch, self.args
         d, C, L = a.dims, a.classes, a.read_len
         bases, offsets = self.synth_reads(n_local, first)
@@ -369,6 +380,10 @@ class Rank:
             m = min(n_local, want_outputs)
             res["twisted"] = twisted[:m].cpu().numpy()
             res["dmat"] = dmat[:m].cpu().numpy()
+        if dump:  # what the last timed step left in the output buffers (every step writes all of them)
+            rows = dump_rows(n_local, (d + C) * 8)
+            pick = (lambda x: x[:n_local]) if rows is None else (lambda x: x.index_select(0, t.from_numpy(rows).to(self.dev)))
+            res["outputs"] = {"twisted": pick(twisted).cpu().numpy(), "distances": pick(dmat).cpu().numpy()}
         return res
 
     # -- BASELINE config 4: reads in total, sharded; chunked all-gather under the twist; distances to the classes
@@ -481,6 +496,23 @@ class Rank:
         if self.use_dist:
             self.dist.destroy_process_group()
         os.close(self.real_stdout)
+
+
+def dump_rows(n, row_bytes):
+    """the rows --dump-outputs writes: None = all n of them when they fit in DUMP_BYTES, else the same seeded sample every run (sorted)"""
+    import numpy as np
+    m = DUMP_BYTES // row_bytes
+    if n <= m:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, m, replace=False))
+
+
+def write_outputs(path, arrays):
+    """arrays {name: ndarray} -> path/<name>.npy, float64"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -1522,6 +1554,11 @@ def main():
     args = parse_args()
     if args.gpus < 1:
         sys.exit("--gpus must be positive")
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("--steps must be at least 1 and --warmup at least 0")
+    workload = args.workload if args.workload != "auto" else ("headline" if args.gpus == 1 else "config4")
+    if args.dump_outputs and (workload != "headline" or args.gpus != 1 or args.in_process):
+        sys.exit("--dump-outputs: the one-GPU headline workload only")
     if args.in_process:
         if args.workload == "config5":
             in_process_config5(args)
@@ -1532,7 +1569,6 @@ def main():
         self_launch(args)  # never returns
     if "WORLD_SIZE" in os.environ:
         rank_preamble()
-    workload = args.workload if args.workload != "auto" else ("headline" if args.gpus == 1 else "config4")
     scaling = args.scaling if args.scaling != "auto" else ("weak" if workload == "headline" else "strong")
     reads = args.reads or (100000 if workload == "headline" else 1000000)
     R = Rank(args)
@@ -1552,7 +1588,8 @@ def main():
             from kpop_amd.shard import shard_bounds
             lo, hi = shard_bounds(reads, R.rank, R.world)
             n_local, first, n_total = hi - lo, lo, reads
-        res = R.run_headline(n_local, first, args.steps, args.warmup, want_outputs=20000 if R.world == 1 else 0)
+        cpu = args.full and R.world == 1 and not args.no_cpu_baseline
+        res = R.run_headline(n_local, first, args.steps, args.warmup, want_outputs=20000 if cpu else 0, dump=bool(args.dump_outputs))
         line = None
         if R.rank == 0:
             line = {
@@ -1562,7 +1599,7 @@ def main():
                 "ms_per_step": res["elapsed"] / args.steps * 1e3, "higher_is_better": True, "scaling": scaling,
                 "vs_baseline": None, "dtype": "f64", "data": "synthetic",
                 "value_is": "device-resident: reads already in HBM when the timed region starts, results left in HBM "
-                            "(see pcie_inclusive and file_to_file for what a host caller and a shell user get)",
+                            "(with --full, pcie_inclusive and file_to_file say what a host caller and a shell user get)",
                 "config": dict(common_cfg, workload="%d reads x %d bp%s, k=%d DNA-ds, %d class vectors, euclidean, metric powers(1,1,2)"
                                % (reads, L, " per GPU" if scaling == "weak" else " in total", k, C),
                                reads_per_gpu=n_local,
@@ -1570,11 +1607,14 @@ def main():
                 "roofline": R.roofline(n_local, res["ms_fused"]),
                 "kernels_ms": {"count_twist": res["ms_fused"], "distance_rowwise(+norms)": res["ms_dist"]},
             }
-        if R.world == 1 and not args.no_cpu_baseline:
+        if args.dump_outputs:
+            write_outputs(args.dump_outputs, res["outputs"])
+            line["outputs_dumped"] = {"files": sorted(name + ".npy" for name in res["outputs"]), "rows": len(res["outputs"]["twisted"]), "of_rows": n_local}
+        if cpu:
             cb, parity = cpu_baseline(R, n_local, res["twisted"], res["dmat"], R.classes.cpu().numpy())
             line["cpu_baseline"] = cb
             line["parity_check"] = parity
-        if R.world == 1 and not args.no_extras:
+        if args.full and R.world == 1 and not args.no_extras:
             # (the timed legs first, the counter passes after them: with the rocprofv3 --pmc children run BEFORE it, the
             # pipeline leg of the same process came out at 38 M sequences/s instead of 50, four runs out of five --
             # tools/probes/pcie_leg_repeat.py, the leg alone: 50.4-50.5, eight times out of eight)

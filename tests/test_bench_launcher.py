@@ -66,3 +66,22 @@ def test_config5_shape_and_line_are_built_without_a_gpu():
     assert line["n_gpus"] == 2 and line["scaling"] == "strong" and line["dtype"] == "f64" and line["n_ranks_seen"] == 2
     assert abs(line["value"] - 500 * 2 / 0.004) < 1e-6 and abs(line["ms_per_step"] - 2.0) < 1e-9
     assert "config 5" in line["config"]["workload"] and "33554432 canonical" in line["config"]["workload"]
+
+
+def test_plain_run_options_and_the_dump_sample_without_a_gpu():
+    """--full is off by default; --steps counts at least one step; --dump-outputs is the one-GPU headline's and refused elsewhere before
+    anything starts; the dumped rows are all of them when they fit in the budget, else the same sorted sample every run"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse_args(["--steps", "7"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7
+    assert bench.parse_args(["--full", "--dump-outputs", "out"]).full is True
+    for argv, why in ((["--steps", "0"], "--steps must be at least 1"), (["--gpus", "2", "--dump-outputs", "out"], "--dump-outputs: the one-GPU headline"),
+                      (["--workload", "config5", "--dump-outputs", "out"], "--dump-outputs: the one-GPU headline")):
+        rc, out, err, took = _bench({}, *argv, timeout=60)
+        assert rc != 0 and out == "" and why in err, (argv, rc, err[-2000:])
+    assert bench.dump_rows(3000, 129 * 8) is None
+    rows = bench.dump_rows(100000, 129 * 8)
+    assert len(rows) * 129 * 8 <= bench.DUMP_BYTES < (len(rows) + 1) * 129 * 8
+    assert np.array_equal(rows, np.unique(rows)) and rows[-1] < 100000 and np.array_equal(rows, bench.dump_rows(100000, 129 * 8))

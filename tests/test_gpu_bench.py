@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -28,9 +29,9 @@ def test_self_launch_relays_one_json_line():
 
 
 def test_default_line_carries_every_baseline_config():
-    """the one-GPU line the driver records: BASELINE configs 2, 3 and 5 as legs of their own (config 4's N = 1 point was there),
+    """the one-GPU --full line: BASELINE configs 2, 3 and 5 as legs of their own (config 4's N = 1 point was there),
     each with ms_per_step and a roofline against a bound that can hold it (no fraction above 1); all-vs-all timed warm"""
-    j = _bench(["--no-children", "--cpu-seconds", "2", "--steps", "5", "--warmup", "2"])
+    j = _bench(["--full", "--no-children", "--cpu-seconds", "2", "--steps", "5", "--warmup", "2"])
     assert j["n_gpus"] == 1 and 0.0 < j["roofline"]["frac"] <= 1.0 and j["cpu_baseline"]["kind"] == "port"
     c2, c3, c5 = j["config2_on_this_gpu"], j["config3_on_this_gpu"], j["config5_on_this_gpu"]
     assert c2["ms_per_step"] > 0 and c2["roofline"]["bound"] == "infinity_cache" and 0.0 < c2["roofline"]["frac"] <= 1.0
@@ -41,6 +42,38 @@ def test_default_line_carries_every_baseline_config():
     assert "skipped" in c5 or (c5["rows_finite_and_inside_the_coefficient_range"] and 0.0 < c5["roofline"]["frac"] <= 1.0)
     ava = j["config4_on_this_gpu"]["all_vs_all"]
     assert ava["every_query_finds_itself_at_distance_0"] and ava["first_call_seconds"] > 0 and ava["seconds"] > 0
+
+
+def test_plain_line_is_the_headline_alone_and_dumps_the_last_steps_outputs(tmp_path, kpop, oracle):
+    """without --full: the timed steps and nothing else in the line; --dump-outputs writes the last step's twisted rows and distances
+    (all rows when they fit in the budget, else the same seeded sample of rows every run) -- the rows the library computes for those reads"""
+    import bench
+    big, small = tmp_path / "big", tmp_path / "small"
+    j = _bench(["--steps", "3", "--warmup", "1", "--dump-outputs", str(big)])
+    assert j["steps"] == 3 and j["ms_per_step"] > 0 and j["value"] > 0 and j["dtype"] == "f64" and j["higher_is_better"] is True
+    for leg in ("cpu_baseline", "parity_check", "pcie_inclusive", "config4_on_this_gpu", "file_to_file", "config2_on_this_gpu", "dims_sweep"):
+        assert leg not in j, leg
+    js = _bench(["--reads", "3000", "--steps", "2", "--warmup", "1", "--dump-outputs", str(small)])
+    n, d, C = 100000, 64, 65
+    rows = bench.dump_rows(n, (d + C) * 8)
+    assert rows is not None and j["outputs_dumped"]["rows"] == len(rows) and js["outputs_dumped"]["rows"] == 3000
+    assert sum(os.path.getsize(str(f)) for f in big.iterdir()) <= 64e6
+    # the same reads, twister, class vectors and metric through the library's host entry points
+    tw = kpop.Twister.synth(bench.TWISTER_SEED, 12, d)
+    try:
+        bases, offs = oracle.synth_reads(bench.READ_SEED, n, 150)
+        twisted = tw.count_twist(bases, offs)
+        cb, co = oracle.synth_reads(bench.CLASS_SEED, C, 30000)
+        classes = tw.count_twist(cb, co)
+    finally:
+        tw.free()
+    w = np.exp2(-np.arange(d, dtype=np.float64) / 8.0)
+    dist = kpop.distance_rowwise(classes, twisted, kpop.metric_compute(w / w.sum()))
+    for where, pick in ((big, rows), (small, np.arange(3000))):
+        t, di = np.load(str(where / "twisted.npy")), np.load(str(where / "distances.npy"))
+        assert t.dtype == np.float64 and di.dtype == np.float64 and t.shape == (len(pick), d) and di.shape == (len(pick), C)
+        assert np.max(np.abs(t - twisted[pick])) <= 1e-12 * np.max(np.abs(twisted[pick]))
+        assert np.max(np.abs(di - dist[pick]) / dist[pick]) <= 1e-12
 
 
 def test_config4_two_ranks_on_one_gpu():

@@ -8,5 +8,5 @@ cd /tmp && export TMPDIR=/tmp
 AB_ONLY_GENOMES=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/dense_trace -o dense -- python3 $R/tools/ab_dense_twist.py > $O/dense_trace.log 2>&1
 find $O -name "*kernel_trace.csv" -delete
 cd $R
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 tail -c 400 $O/bench.err; ls $O

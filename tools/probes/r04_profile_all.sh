@@ -22,8 +22,8 @@ CLASSES="65 64 100 130" bash tools/probes/r04_summary.sh > $O/summary_kernels.tx
 bash tools/probes/r04_summary_pmc.sh > $O/summary_pmc.txt 2>&1
 python tools/probes/probe_count.py > $O/count_wave_probe.txt 2>&1
 # 4. the bench line, plain; then the whole line (config legs included) under the kernel trace
-python bench.py > $O/bench.json 2> $O/bench.err
-(cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_trace -o bench -- python3 $R/bench.py --no-children --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err)
+python bench.py --full > $O/bench.json 2> $O/bench.err
+(cd "$O" && rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_trace -o bench -- python3 $R/bench.py --full --no-children --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err)
 find $O/bench_trace -name "*kernel_stats.csv" -exec cp {} $O/bench_kernel_stats.csv \;
 rm -rf $O/bench_trace
 tail -c 300 $O/bench.err; ls $O

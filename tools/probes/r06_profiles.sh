@@ -35,5 +35,5 @@ open(out + "/dist_sq.txt", "w").write("\n".join(lines) + "\n")
 print("\n".join(lines))
 PY
 # 5. the driver-form line
-timeout 900 python3 bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout 900 python3 bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 tail -c 300 "$OUT/bench.json" | head -c 300; echo
