@@ -528,6 +528,51 @@ int kpop_dev_summarize_distances(const double *d_dist, uint32_t r2, uint32_t r1,
                                  uint32_t max_neighbours, double *d_out_stats, uint32_t *d_out_n,
                                  uint32_t *d_out_idx, double *d_out_dist, double *d_out_z, void *stream);
 
+/* ------------------------------------------------- resident reference set
+ * A first operand of the distance calls that is prepared ONCE and queried many times (a database of genomes, the class
+ * vectors of a classifier).  The reference computes the norms of both operands on every invocation
+ * (Base.get_normalizations, lib/Matrix.ml:42-76, called from get_distance_rowwise :191-266 and summarize_rowwise
+ * :691-766); a set keeps, in device memory, the rows and everything about them that does not depend on the query rows:
+ * norms (0 -> 1, :67) and sums before the scale, the matrix-core summary's scalars, and -- made by the first call that
+ * needs them -- the divided copy a / n (:248) and the evenly spaced sample of rows.  Every call on a set returns the
+ * arrays of the unprepared call on the same rows BIT FOR BIT, under whatever kpop_tune settings hold at the time of the
+ * call: each piece comes out of the kernel the unprepared call runs, over the same row.
+ * A set belongs to the device slot that was current when it was made, is used by one host thread at a time, and
+ * kpop_tune settings change only while no call on it is in flight.                                                    */
+typedef struct kpop_refset kpop_refset;
+/* Rows copied from host memory (replaces the first operand of lib/Matrix.ml:191-266 and :691-766 when one register is
+   queried repeatedly).  capacity_rows >= r1 (0 = r1) is the room for kpop_refset_append; r1 = 0 makes an empty set.
+   n_dims of 32,768 and more: KPOP_ERR_UNSUPPORTED (as kpop_dev_row_norms).  Synchronises.                            */
+int kpop_refset_create(const double *m1, uint32_t r1, uint32_t n_dims, const double *metric, int kind, double p,
+                       int normalize, uint32_t capacity_rows, kpop_refset **out);
+/* Rows and metric already in device memory, BORROWED: not copied, not freed; the caller keeps them alive and unchanged
+   for the life of the set.  No append.  The preparation pass (lib/Matrix.ml:42-76 over the rows) runs on `stream`,
+   which the call waits for.                                                                                          */
+int kpop_dev_refset_wrap(const double *d_m1, uint32_t r1, uint32_t n_dims, const double *d_metric, int kind,
+                         double p, int normalize, void *stream, kpop_refset **out);
+/* n_rows more rows from host memory (Matrix.merge_rowwise, lib/Matrix.ml:130-147, for a register that grows): a copy and
+   one pass over the NEW rows.  r1 + n_rows > capacity: KPOP_ERR_CAPACITY, the set stays as it was.  Waits for the device. */
+int kpop_refset_append(kpop_refset *rs, const double *rows, uint32_t n_rows);
+/* any of the outputs may be NULL; device_bytes counts everything the set has allocated so far */
+int kpop_refset_info(const kpop_refset *rs, uint32_t *r1, uint32_t *n_dims, uint32_t *capacity_rows,
+                     uint64_t *device_bytes);
+int kpop_refset_free(kpop_refset *rs);
+/* kpop_distance_rowwise / kpop_distance_summary (lib/Matrix.ml:191-266 / :691-766) with the set as first operand: only
+   the query rows cross the bus.  Long neighbour lists are completed as there.                                        */
+int kpop_refset_distance_rowwise(kpop_refset *rs, const double *m2, uint32_t r2, double *out);
+int kpop_refset_distance_summary(kpop_refset *rs, const double *m2, uint32_t r2, uint32_t keep_at_most,
+                                 uint32_t max_neighbours, double *out_stats, uint32_t *out_n, uint32_t *out_idx,
+                                 double *out_dist, double *out_z);
+/* kpop_dev_distance_rowwise / kpop_dev_distance_summary with the set as first operand; enqueue only (a piece of the set
+   that the call's route needs and nobody has made yet is made on `stream`, other streams wait for it on an event).
+   d_work holds the QUERY side alone: kpop_dev_refset_workspace_bytes does not grow with the set.                     */
+uint64_t kpop_dev_refset_workspace_bytes(const kpop_refset *rs, uint32_t r2);
+int kpop_dev_refset_distance_rowwise(kpop_refset *rs, const double *d_m2, uint32_t r2, void *d_work, double *d_out,
+                                     void *stream);
+int kpop_dev_refset_distance_summary(kpop_refset *rs, const double *d_m2, uint32_t r2, uint32_t keep_at_most,
+                                     uint32_t max_neighbours, void *d_work, double *d_out_stats, uint32_t *d_out_n,
+                                     uint32_t *d_out_idx, double *d_out_dist, double *d_out_z, void *stream);
+
 /* ------------------------------------------------- k-mer database (KPopCountDB)
  * the operations of lib/KMerDB.ml that touch every count.  A database is the reference's
  * `storage: I32BAVector.t array` (lib/KMerDB.ml:54-63): n_cols spectra ("columns"), each a vector of n_rows int32

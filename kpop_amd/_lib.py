@@ -148,6 +148,16 @@ SIGNATURES = {
     "kpop_dev_distance_summary": (C.c_int, [vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, C.c_int,
                                             C.c_double, C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp,
                                             vp, vp]),
+    "kpop_refset_create": (C.c_int, [f64p, C.c_uint32, C.c_uint32, f64p, C.c_int, C.c_double, C.c_int, C.c_uint32, C.POINTER(vp)]),
+    "kpop_dev_refset_wrap": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp, C.c_int, C.c_double, C.c_int, vp, C.POINTER(vp)]),
+    "kpop_refset_append": (C.c_int, [vp, f64p, C.c_uint32]),
+    "kpop_refset_info": (C.c_int, [vp, u32p, u32p, u32p, u64p]),
+    "kpop_refset_free": (C.c_int, [vp]),
+    "kpop_refset_distance_rowwise": (C.c_int, [vp, f64p, C.c_uint32, f64p]),
+    "kpop_refset_distance_summary": (C.c_int, [vp, f64p, C.c_uint32, C.c_uint32, C.c_uint32, f64p, u32p, u32p, f64p, f64p]),
+    "kpop_dev_refset_workspace_bytes": (C.c_uint64, [vp, C.c_uint32]),
+    "kpop_dev_refset_distance_rowwise": (C.c_int, [vp, vp, C.c_uint32, vp, vp, vp]),
+    "kpop_dev_refset_distance_summary": (C.c_int, [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp]),
 }
 
 

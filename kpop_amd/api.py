@@ -691,6 +691,97 @@ def distance_summary(m1, m2, metric, kind=EUCLIDEAN, p=2.0, normalize=True, keep
     return stats, n, idx, dist, z
 
 
+class RefSet:
+    """A first operand that stays on the device, prepared once and queried many times (kpop_refset, include/kpop_hip.h): the
+    register of Matrix.get_distance_rowwise / summarize_rowwise (lib/Matrix.ml:191-266, :691-766) when it is queried repeatedly.
+    Every call returns what distance_rowwise / distance_summary return for the same rows, bit for bit."""
+
+    def __init__(self, m1, metric, kind=EUCLIDEAN, p=2.0, normalize=True, capacity=None):
+        metric = _c(metric, np.float64)
+        m1 = _c(m1, np.float64)
+        if m1.ndim != 2:
+            m1 = m1.reshape(0, len(metric))
+        if m1.shape[1] != len(metric):
+            raise ValueError("Incompatible_geometries")  # lib/Matrix.ml:193-194
+        self._h = None
+        self._keep = None
+        h = C.c_void_p()
+        check(_lib.load().kpop_refset_create(_p(_nz(m1, np.float64), C.c_double), m1.shape[0], m1.shape[1], _p(_nz(metric, np.float64), C.c_double),
+                                             int(kind), float(p), 1 if normalize else 0, int(capacity or 0), C.byref(h)))
+        self._h = h
+
+    @classmethod
+    def wrap(cls, d_m1, r1, n_dims, d_metric, kind=EUCLIDEAN, p=2.0, normalize=True, stream=0, keep=None):
+        """Rows and metric already on the device (pointers), borrowed: the caller keeps them alive and unchanged (`keep`: objects
+        to hold on to for the life of the set, such as the tensors the pointers came from).  No append."""
+        self = cls.__new__(cls)
+        self._h = None
+        self._keep = keep
+        h = C.c_void_p()
+        check(_lib.load().kpop_dev_refset_wrap(d_m1, int(r1), int(n_dims), d_metric, int(kind), float(p), 1 if normalize else 0, stream, C.byref(h)))
+        self._h = h
+        return self
+
+    @property
+    def handle(self):
+        return self._h
+
+    def info(self):
+        r1, d, cap, nbytes = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint64()
+        check(_lib.load().kpop_refset_info(self._h, C.byref(r1), C.byref(d), C.byref(cap), C.byref(nbytes)))
+        return {"r1": r1.value, "n_dims": d.value, "capacity": cap.value, "device_bytes": nbytes.value}
+
+    def append(self, rows):
+        rows = _c(rows, np.float64)
+        d = self.info()["n_dims"]
+        if rows.ndim != 2 or rows.shape[1] != d:
+            raise ValueError("Incompatible_geometries")
+        check(_lib.load().kpop_refset_append(self._h, _p(_nz(rows, np.float64), C.c_double), rows.shape[0]))
+
+    def distance_rowwise(self, m2):
+        """-> r2 x r1 matrix, as distance_rowwise(m1, m2, ...)"""
+        m2 = _c(m2, np.float64)
+        i = self.info()
+        if m2.ndim != 2 or m2.shape[1] != i["n_dims"]:
+            raise ValueError("Incompatible_geometries")
+        out = np.zeros((m2.shape[0], i["r1"]), dtype=np.float64)
+        check(_lib.load().kpop_refset_distance_rowwise(self._h, _p(_nz(m2, np.float64), C.c_double), m2.shape[0], _p(_nz(out, np.float64), C.c_double)))
+        return out
+
+    def distance_summary(self, m2, keep_at_most=2, max_neighbours=None):
+        """-> stats, n, idx, dist, z, as distance_summary(m1, m2, ...)"""
+        m2 = _c(m2, np.float64)
+        i = self.info()
+        if m2.ndim != 2 or m2.shape[1] != i["n_dims"]:
+            raise ValueError("Incompatible_geometries")
+        r1, r2 = i["r1"], m2.shape[0]
+        if max_neighbours is None:
+            max_neighbours = r1 if not keep_at_most else min(r1, max(keep_at_most * 4, 8))
+        max_neighbours = max(int(max_neighbours), 1)
+        stats = np.zeros((r2, 4), dtype=np.float64)
+        n = np.zeros(r2, dtype=np.uint32)
+        idx = np.zeros((r2, max_neighbours), dtype=np.uint32)
+        dist = np.zeros((r2, max_neighbours), dtype=np.float64)
+        z = np.zeros((r2, max_neighbours), dtype=np.float64)
+        check(_lib.load().kpop_refset_distance_summary(self._h, _p(_nz(m2, np.float64), C.c_double), r2, int(keep_at_most or 0), max_neighbours,
+                                                       _p(_nz(stats, np.float64), C.c_double), _p(_nz(n, np.uint32), C.c_uint32),
+                                                       _p(_nz(idx, np.uint32), C.c_uint32), _p(_nz(dist, np.float64), C.c_double),
+                                                       _p(_nz(z, np.float64), C.c_double)))
+        return stats, n, idx, dist, z
+
+    def free(self):
+        if self._h is not None and self._h.value:
+            check(_lib.load().kpop_refset_free(self._h))
+            self._h = None
+            self._keep = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 def embeddings(m, metric, kind=EUCLIDEAN, p=2.0, normalize=True):
     """Base.get_embeddings (lib/Matrix.ml:78-128): principal coordinates from twisted rows."""
     m = _c(m, np.float64)
@@ -803,3 +894,17 @@ def dev_distance_summary(d_m1, r1, d_m2, r2, n_dims, d_metric, d_work, d_stats, 
     check(_lib.load().kpop_dev_distance_summary(d_m1, int(r1), d_m2, int(r2), int(n_dims), d_metric, int(kind),
                                                 float(p), 1 if normalize else 0, int(keep_at_most or 0),
                                                 int(max_neighbours), d_work, d_stats, d_n, d_idx, d_dist, d_z, stream))
+
+
+def dev_refset_workspace_bytes(rs, r2):
+    """the size of d_work for r2 query rows against the set: the query side alone, whatever the set's size"""
+    return int(_lib.load().kpop_dev_refset_workspace_bytes(rs.handle, int(r2)))
+
+
+def dev_refset_distance_rowwise(rs, d_m2, r2, d_work, d_out, stream=0):
+    check(_lib.load().kpop_dev_refset_distance_rowwise(rs.handle, d_m2, int(r2), d_work, d_out, stream))
+
+
+def dev_refset_distance_summary(rs, d_m2, r2, d_work, d_stats, d_n, d_idx, d_dist, d_z, keep_at_most=2, max_neighbours=8, stream=0):
+    check(_lib.load().kpop_dev_refset_distance_summary(rs.handle, d_m2, int(r2), int(keep_at_most or 0), int(max_neighbours), d_work, d_stats, d_n,
+                                                       d_idx, d_dist, d_z, stream))

@@ -23,80 +23,13 @@
 #include "summary_types.h"
 #include "radix_sort.h"
 #include "space_ops.h"
+#include "row_norms.h"
+#include "refset.h"
 #include "wave_sort.h"
 
 namespace kpop {
 
-// ---------------------------------------------------------------------------
-// norms + pre-normalised rows.  One thread per row walks the dimensions in
-// order; 64-row x 32-dim tiles go through LDS so global traffic is coalesced.
-// ---------------------------------------------------------------------------
-constexpr int kNormRows = 64, kNormDims = 32;
-
-// norms[i] = scale(sum_c m_c g(a_ic)), 0 -> 1 (lib/Matrix.ml:67); when `normalised` is non-null the
-// block then re-reads its 64 rows (still in L2) and writes a_ic / n_i (adaptor_a/_b, lib/Matrix.ml:248)
-template <int KIND>
-__device__ __forceinline__ void row_norms_block(const double *__restrict__ m, uint32_t rows, uint32_t n_dims,
-                                                const double *__restrict__ metric, double p,
-                                                double *__restrict__ norms, double *__restrict__ normalised, uint32_t block,
-                                                double *__restrict__ sumsq = nullptr) {
-  // (sumsq: the sum itself, before the scale -- sum_c m_c a_ic^2 for the euclidean and the cosine form: what the matrix-core path wants of a row)
-  __shared__ double tile[kNormRows][kNormDims + 1];
-  __shared__ double s_metric[kNormDims];
-  __shared__ double s_norm[kNormRows];
-  const uint32_t row0 = block * kNormRows;
-  double acc = 0.0;
-  // (the next tile's loads fly while 64 of the block's threads walk this one: a tile at a time left the kernel at 2 TB/s on 1M x 64)
-  constexpr int kPer = kNormRows * kNormDims / 256;
-  double pre[kPer];
-  auto fetch = [&](uint32_t c0) {
-#pragma unroll
-    for (int u = 0; u < kPer; ++u) {
-      const uint32_t e = threadIdx.x + 256u * u, i = e / kNormDims, c = e % kNormDims;
-      // (addresses clamped into the matrix, what lies outside zeroed when the tile is stored: nothing here looks at a loaded value)
-      pre[u] = m[(uint64_t)min(row0 + i, rows - 1u) * n_dims + min(c0 + c, n_dims - 1u)];
-    }
-  };
-  fetch(0);
-  for (uint32_t c0 = 0; c0 < n_dims; c0 += kNormDims) {
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < kPer; ++u) {
-      const uint32_t e = threadIdx.x + 256u * u, i = e / kNormDims, c = e % kNormDims;
-      tile[i][c] = (row0 + i < rows && c0 + c < n_dims) ? pre[u] : 0.0;
-    }
-    if (threadIdx.x < kNormDims) s_metric[threadIdx.x] = (c0 + threadIdx.x < n_dims) ? metric[c0 + threadIdx.x] : 0.0;
-    __syncthreads();
-    if (c0 + kNormDims < n_dims) fetch(c0 + kNormDims);
-    if (threadIdx.x < kNormRows) {
-      const uint32_t lim = min((uint32_t)kNormDims, n_dims - c0);
-      for (uint32_t c = 0; c < lim; ++c) {
-        double el = tile[threadIdx.x][c];
-        // lib/Space.ml:169-178: acc +. (el *. el *. m_i)  |  acc +. ((|el| ** p) *. m_i)
-        acc = __dadd_rn(acc, component<KIND>(el, s_metric[c], p));
-      }
-    }
-  }
-  if (threadIdx.x < kNormRows) {
-    double nv = scale_distance<KIND>(acc, p);
-    nv = (nv == 0.0) ? 1.0 : nv;  // lib/Matrix.ml:67
-    s_norm[threadIdx.x] = nv;
-    if (row0 + threadIdx.x < rows) {
-      norms[row0 + threadIdx.x] = nv;
-      if (sumsq) sumsq[row0 + threadIdx.x] = acc;
-    }
-  }
-  if (!normalised) return;
-  __syncthreads();
-  const uint32_t nrows = min((uint32_t)kNormRows, rows - row0);
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  for (uint32_t i = wv; i < nrows; i += 4) {  // one wave per row: coalesced, no integer division
-    const double *src = m + (uint64_t)(row0 + i) * n_dims;
-    double *dst = normalised + (uint64_t)(row0 + i) * n_dims;
-    const double nv = s_norm[i];
-    for (uint32_t c = lane; c < n_dims; c += 64) dst[c] = src[c] / nv;
-  }
-}
+// (row_norms_block, the norms and pre-normalised rows of one operand: row_norms.h)
 
 template <int KIND>
 __global__ __launch_bounds__(256) void row_norms_kernel(const double *__restrict__ m, uint32_t rows, uint32_t n_dims,
@@ -1133,8 +1066,10 @@ struct DistWork {
   double *n1, *n2, *a, *b;
 };
 
-static DistWork carve(void *work, uint32_t r1, uint32_t r2, uint32_t n_dims) {
+// (prep: the first operand is a resident set that brings its own norms and copies -- the workspace holds the query side alone)
+static DistWork carve(void *work, uint32_t r1, uint32_t r2, uint32_t n_dims, const kpop_refset *prep = nullptr) {
   double *w = reinterpret_cast<double *>(work);
+  if (prep) r1 = 0;
   DistWork d;
   d.n1 = w;
   d.n2 = d.n1 + r1;
@@ -1146,13 +1081,19 @@ static DistWork carve(void *work, uint32_t r1, uint32_t r2, uint32_t n_dims) {
 template <int KIND>
 static int prepare_operands(const double *m1, uint32_t r1, const double *m2, uint32_t r2, uint32_t n_dims,
                             const double *metric, double p, int normalize, void *work, const double **a,
-                            const double **b, hipStream_t st) {
+                            const double **b, hipStream_t st, kpop_refset *prep = nullptr) {
   if (!normalize) {  // n1 = n2 = 1 (lib/Matrix.ml:201-202): x /. 1. = x
     *a = m1;
     *b = m2;
     return 0;
   }
-  DistWork w = carve(work, r1, r2, n_dims);
+  DistWork w = carve(work, r1, r2, n_dims, prep);
+  if (prep) {  // the set keeps its normalised copy (the same quotients): the query rows alone are divided here
+    KPOP_TRY(prep->divided(st, a));
+    KPOP_TRY(launch_row_norms_pair<KIND>(nullptr, 0, nullptr, nullptr, r2 ? m2 : nullptr, r2, w.n2, w.b, n_dims, metric, p, st));
+    *b = w.b;
+    return 0;
+  }
   KPOP_TRY(launch_row_norms_pair<KIND>(r1 ? m1 : nullptr, r1, w.n1, w.a, r2 ? m2 : nullptr, r2, w.n2, w.b, n_dims, metric, p, st));
   *a = w.a;
   *b = w.b;
@@ -1267,7 +1208,9 @@ int launch_distance_rowwise_mfma(int kind, const double *a, uint32_t r1, const d
 template <int KIND>
 static int rowwise_impl(const double *m1, uint32_t r1, const double *m2, uint32_t r2, uint32_t n_dims,
                         const double *metric, double p, int normalize, void *work, double *out, hipStream_t st,
-                        const double *norms1 = nullptr) {
+                        const double *norms1 = nullptr, kpop_refset *prep = nullptr) {
+  // prep: the first operand is a resident set (refset.h) -- what it holds is not computed again, everything else runs as without it
+  if (prep && normalize) KPOP_TRY(prep->prepared(st));
   if (n_dims >= kLongD) {  // spectral distances: a few rows over millions of k-mers
     const uint32_t slabs = long_slabs(r1, r2, n_dims), slab = slab_dims(n_dims, slabs);
     DistWork w = carve(work, r1, r2, n_dims);
@@ -1313,17 +1256,19 @@ static int rowwise_impl(const double *m1, uint32_t r1, const double *m2, uint32_
       if (!normalize) return launch_distance_rowwise_mfma(KIND, m1, r1, m2, r2, n_dims, metric, p, out, st, nullptr, nullptr, nullptr, nullptr);
       // (the norms' pass hands over the rows' sums of squares as well -- the same sums before their scale: the larger operand is read ONCE
       // before the contraction; they go where the normalised copies used to)
-      DistWork w = carve(work, r1, r2, n_dims);
-      KPOP_TRY(launch_row_norms_pair<KIND>(m1, r1, w.n1, nullptr, m2, r2, w.n2, nullptr, n_dims, metric, p, st, w.a, w.b));
+      DistWork w = carve(work, r1, r2, n_dims, prep);
+      KPOP_TRY(launch_row_norms_pair<KIND>(prep ? nullptr : m1, r1, w.n1, nullptr, m2, r2, w.n2, nullptr, n_dims, metric, p, st, w.a, w.b));
+      if (prep) return launch_distance_rowwise_mfma(KIND, m1, r1, m2, r2, n_dims, metric, p, out, st, prep->n1, w.n2, prep->s_raw, w.b);
       return launch_distance_rowwise_mfma(KIND, m1, r1, m2, r2, n_dims, metric, p, out, st, norms1 ? norms1 : w.n1, w.n2, w.a, w.b);
     }
     const double *a, *b;
-    KPOP_TRY(prepare_operands<KIND>(m1, r1, m2, r2, n_dims, metric, p, normalize, work, &a, &b, st));
+    KPOP_TRY(prepare_operands<KIND>(m1, r1, m2, r2, n_dims, metric, p, normalize, work, &a, &b, st, prep));
     return rowwise_block<KIND>(a, r1, b, r2, n_dims, metric, p, out, st);
   }
   // norms only; the rowwise kernel divides as it stages the rows
-  DistWork w = carve(work, r1, r2, n_dims);
-  // (a caller that keeps the first operand -- the class vectors of the streaming pipeline -- brings its norms along)
+  DistWork w = carve(work, r1, r2, n_dims, prep);
+  if (prep) norms1 = prep->n1;
+  // (a caller that keeps the first operand brings its norms along: kpop_dev_distance_rowwise_norms, or a resident set)
   KPOP_TRY(launch_row_norms_pair<KIND>((r1 && !norms1) ? m1 : nullptr, r1, w.n1, nullptr, r2 ? m2 : nullptr, r2, w.n2, nullptr, n_dims, metric, p, st));
   return rowwise_block<KIND>(m1, r1, m2, r2, n_dims, metric, p, out, st, norms1 ? norms1 : w.n1, w.n2);
 }
@@ -1350,11 +1295,11 @@ int launch_mfma_reference_norms(const double *a, uint32_t r1, uint32_t n_dims, c
                                 const double *na = nullptr, const double *s_raw = nullptr);
 int launch_mfma_copy_reference_norms(const void *from, void *to, uint32_t r1, uint32_t n_dims, uint32_t q_room, hipStream_t st);
 int launch_distance_rows_mfma(int kind, const double *a, uint32_t r1, const double *b, uint32_t q, uint32_t n_dims, const double *metric, double *rows,
-                              void *scratch, uint32_t q_room, hipStream_t st, bool a_raw = false);
+                              void *scratch, uint32_t q_room, hipStream_t st, bool a_raw = false, const RefScalars *ref = nullptr);
 int launch_summary_refine(int kind, const double *rows, const double *a, uint32_t r1, const double *b, uint32_t q, uint32_t n_dims, const double *metric,
                           double p, uint32_t row0, uint32_t keep_at_most, uint32_t max_neighbours, double *out_stats, uint32_t *out_n, uint32_t *out_idx,
                           double *out_dist, double *out_z, void *scratch, uint32_t q_room, hipStream_t st, const SummaryLists &lists, const uint32_t **gate,
-                          const void **row_counts, const double *na = nullptr);
+                          const void **row_counts, const double *na = nullptr, const RefScalars *ref = nullptr);
 int launch_summary_flagged_rows(const double *rows, uint32_t n_rows, uint32_t r1, uint32_t row0, uint32_t keep_at_most, uint32_t max_neighbours,
                                 double *out_stats, uint32_t *out_n, uint32_t *out_idx, double *out_dist, double *out_z, const void *flags, hipStream_t st);
 // ... the same without distance rows: the summary's pass inside the contraction (summary_large.hip / distance_mfma.hip)
@@ -1367,7 +1312,7 @@ int launch_row_sumsq(const double *x, uint32_t rows, uint32_t n_dims, const doub
 int launch_summary_fused_mfma(int kind, const double *a, uint32_t r1, uint32_t n_rows, uint32_t n_dims, const double *srow, uint32_t s, uint32_t row0,
                               uint32_t keep_at_most, uint32_t max_neighbours, double *out_stats, uint32_t *out_n, uint32_t *out_idx, double *out_dist,
                               double *out_z, double *seg, uint32_t *seg_i, void *scratch, const void *mscratch, uint32_t q_room, hipStream_t st,
-                              SummaryLists *lists);
+                              SummaryLists *lists, const RefScalars *ref = nullptr);
 int launch_summary_failed_rows(const double *rows, uint32_t n_rows, uint32_t r1, uint32_t row0, uint32_t keep_at_most, uint32_t max_neighbours,
                                double *out_stats, uint32_t *out_n, uint32_t *out_idx, double *out_dist, double *out_z, void *scratch,
                                hipStream_t st);
@@ -1395,9 +1340,12 @@ template <int KIND>
 static int summary_large_impl(const double *m1, uint32_t r1, const double *m2, uint32_t r2, uint32_t n_dims,
                               const double *metric, double p, int normalize, uint32_t keep_at_most,
                               uint32_t max_neighbours, void *work, double *out_stats, uint32_t *out_n,
-                              uint32_t *out_idx, double *out_dist, double *out_z, hipStream_t st) {
+                              uint32_t *out_idx, double *out_dist, double *out_z, hipStream_t st, kpop_refset *prep = nullptr) {
+  // prep: the reference rows are a resident set (refset.h); its norms, scalars, copy and sample are read, not made again -- the same
+  // kernels made them, over the same rows
   const double *a, *b;
   const uint64_t budget = 4096ull << 20;
+  if (prep && normalize) KPOP_TRY(prep->prepared(st));
   const bool mfma = summary_mfma_applies(KIND, r1, n_dims, keep_at_most, max_neighbours);
   const bool mfma_select = mfma && ctx().tune_summary_mfma == 2 && n_dims <= 128 && summary_select_mfma_applies(r1, keep_at_most);
   // The matrix-core path (its default form) takes the REFERENCE set as it is: no normalised copy of it is made (8.5 GB read and written
@@ -1405,21 +1353,31 @@ static int summary_large_impl(const double *m1, uint32_t r1, const double *m2, u
   // norm's reciprocal where it comes out, the exact chains of the refinement and of the fall-back divide element by element as the copy
   // did (the same bits).  The query rows, a few hundred, are divided as before.  kpop_tune("summary_rawref", 0): the copy, as before.
   const double *na = nullptr, *s_raw = nullptr;  // the reference rows' norms and raw sums of squares when `a` is NOT divided
+  RefScalars ref_store;
+  const RefScalars *ref = nullptr;  // the reference rows' scalars of the matrix-core routes, when a set holds them
   if (mfma && !mfma_select && normalize && ctx().tune_summary_rawref) {
-    DistWork w = carve(work, r1, r2, n_dims);
-    KPOP_TRY(launch_row_norms_pair<KIND>(m1, r1, w.n1, nullptr, m2, r2, w.n2, w.b, n_dims, metric, p, st, w.a, nullptr));
+    DistWork w = carve(work, r1, r2, n_dims, prep);
+    KPOP_TRY(launch_row_norms_pair<KIND>(prep ? nullptr : m1, r1, w.n1, nullptr, m2, r2, w.n2, w.b, n_dims, metric, p, st, w.a, nullptr));
     a = m1;
     b = w.b;
-    na = w.n1;
-    s_raw = w.a;  // (r1 doubles at the head of the room the copy would have taken)
+    na = prep ? prep->n1 : w.n1;
+    s_raw = prep ? prep->s_raw : w.a;  // (r1 doubles at the head of the room the copy would have taken)
+    if (prep) {
+      KPOP_TRY(prep->scalars_default(st, &ref_store));
+      ref = &ref_store;
+    }
   } else {
-    KPOP_TRY(prepare_operands<KIND>(m1, r1, m2, r2, n_dims, metric, p, normalize, work, &a, &b, st));
+    KPOP_TRY(prepare_operands<KIND>(m1, r1, m2, r2, n_dims, metric, p, normalize, work, &a, &b, st, prep));
+    if (prep && mfma) {  // sums of squares of the operand the contraction reads (row_sumsq_kernel's own arithmetic)
+      KPOP_TRY(prep->scalars_of(a, st, &ref_store));
+      ref = &ref_store;
+    }
   }
   if (mfma) {
     // the distances on the matrix cores, approximately, to LOCATE what the summary reports; what is reported is recomputed with the
     // reference's chain (distance_mfma.hip).  Rows the refinement cannot vouch for: exact distance rows and the one-block-per-row
     // kernel over them, both launched whatever happened and both returning at once when nothing was flagged.
-    // Up to 128 dimensions (kpop_tune("summary_mfma", 2), the default) no approximate row is WRITTEN either: thresholds from the
+    // Up to 128 dimensions and under kpop_tune("summary_mfma", 2) (not the default: measured slower, common.h) no approximate row is WRITTEN either: thresholds from the
     // distances to a sample of the reference rows, then ONE kernel that classifies every distance in the accumulators' registers
     // (summary_select_mfma_kernel); beyond, and under kpop_tune("summary_mfma", 1), round 5's path: rows, then the summary's pass over them.
     const bool select = mfma_select;
@@ -1457,11 +1415,16 @@ static int summary_large_impl(const double *m1, uint32_t r1, const double *m2, u
       }
       double *a_s2 = reinterpret_cast<double *>(wp + 2 * lane_bytes), *sa_s2 = reinterpret_cast<double *>(wp + 2 * lane_bytes + as2_bytes),
              *ia_s2 = na ? reinterpret_cast<double *>(wp + 2 * lane_bytes + as2_bytes + sas2_bytes) : nullptr;
-      KPOP_TRY(launch_mfma_reference_norms(a, r1, n_dims, metric, lane[0].mscratch, chunk, st, na, s_raw));
-      KPOP_TRY(launch_mfma_copy_reference_norms(lane[0].mscratch, lane[1].mscratch, r1, n_dims, chunk, st));
-      if (row_sample2) {
-        KPOP_TRY(launch_sample_gather(a, r1, n_dims, s_rows2, a_s2, st));
-        KPOP_TRY(launch_mfma_sample_scalars(lane[0].mscratch, chunk, r1, n_dims, s_rows2, sa_s2, ia_s2, st));
+      const double *as2 = a_s2, *sas2 = sa_s2, *ias2 = ia_s2;
+      if (ref) {  // (both lanes read the set's scalars and its sample: nothing to make, nothing to copy)
+        if (row_sample2) KPOP_TRY(prep->sample(a, s_rows2, kSampleGathered, ref, st, &as2, &sas2, &ias2));
+      } else {
+        KPOP_TRY(launch_mfma_reference_norms(a, r1, n_dims, metric, lane[0].mscratch, chunk, st, na, s_raw));
+        KPOP_TRY(launch_mfma_copy_reference_norms(lane[0].mscratch, lane[1].mscratch, r1, n_dims, chunk, st));
+        if (row_sample2) {
+          KPOP_TRY(launch_sample_gather(a, r1, n_dims, s_rows2, a_s2, st));
+          KPOP_TRY(launch_mfma_sample_scalars(lane[0].mscratch, chunk, r1, n_dims, s_rows2, sa_s2, ia_s2, st));
+        }
       }
       KPOP_HIP(hipEventRecord(aux->fork, st));
       KPOP_HIP(hipStreamWaitEvent(aux->stream, aux->fork, 0));
@@ -1476,13 +1439,13 @@ static int summary_large_impl(const double *m1, uint32_t r1, const double *m2, u
         const void *flags = nullptr;
         auto batch = [&]() -> int {
           if (bi > 0) KPOP_HIP(hipStreamWaitEvent(L.s, aux->step[(bi - 1) & 1u], 0));  // this batch's contraction after the one before it
-          KPOP_TRY(launch_distance_rows_mfma(KIND, a, r1, bq, q, n_dims, metric, L.rows, L.mscratch, chunk, L.s, na != nullptr));
+          KPOP_TRY(launch_distance_rows_mfma(KIND, a, r1, bq, q, n_dims, metric, L.rows, L.mscratch, chunk, L.s, na != nullptr, ref));
           KPOP_HIP(hipEventRecord(aux->step[bi & 1u], L.s));
-          if (row_sample2) KPOP_TRY(launch_rows_mfma_against(KIND, a_s2, sa_s2, s_rows2, q, n_dims, L.srow, L.mscratch, chunk, r1, L.s, ia_s2));
+          if (row_sample2) KPOP_TRY(launch_rows_mfma_against(KIND, as2, sas2, s_rows2, q, n_dims, L.srow, L.mscratch, chunk, r1, L.s, ias2));
           KPOP_TRY(launch_summary_large(L.rows, q, r1, q0, keep_at_most, max_neighbours, out_stats, out_n, out_idx, out_dist, out_z, L.s, L.scratch, &lists, true,
                                         row_sample2 ? L.srow : nullptr, s_rows2));
           KPOP_TRY(launch_summary_refine(KIND, L.rows, a, r1, bq, q, n_dims, metric, p, q0, keep_at_most, max_neighbours, out_stats, out_n, out_idx, out_dist, out_z,
-                                         L.mscratch, chunk, L.s, lists, &gate, &flags, na));
+                                         L.mscratch, chunk, L.s, lists, &gate, &flags, na, ref));
           KPOP_TRY(audit_fallback(gate, L.s));
           KPOP_TRY(audit_fallback(lists.n_failed, L.s));
           KPOP_TRY(rowwise_block<KIND>(a, r1, bq, q, n_dims, metric, p, L.rows, L.s, na, nullptr, gate));  // (na: the kernel divides the reference rows as it stages them)
@@ -1518,14 +1481,19 @@ static int summary_large_impl(const double *m1, uint32_t r1, const double *m2, u
     double *a_s = reinterpret_cast<double *>(wp + row_bytes + segi_bytes + sum_bytes + m_bytes);
     double *sa_s = reinterpret_cast<double *>(wp + row_bytes + segi_bytes + sum_bytes + m_bytes + as_bytes);
     double *srow = reinterpret_cast<double *>(wp + row_bytes + segi_bytes + sum_bytes + m_bytes + as_bytes + sas_bytes);
-    KPOP_TRY(launch_mfma_reference_norms(a, r1, n_dims, metric, mscratch, chunk, st, na, s_raw));
-    double *ia_s = nullptr;
-    if (row_sample) {  // the sample of the reference rows, its sums of squares and (the set taken as it is) its norms' reciprocals: once a call
+    if (!ref) KPOP_TRY(launch_mfma_reference_norms(a, r1, n_dims, metric, mscratch, chunk, st, na, s_raw));
+    const double *ia_s = nullptr;
+    if (ref && (row_sample || select)) {  // (a set keeps its sample and the sample's scalars: once, not once a call)
+      const double *as_set = nullptr, *sas_set = nullptr;
+      KPOP_TRY(prep->sample(a, s_rows, select ? kSampleSumsq : kSampleGathered, ref, st, &as_set, &sas_set, &ia_s));
+      a_s = const_cast<double *>(as_set);
+      sa_s = const_cast<double *>(sas_set);
+    } else if (row_sample) {  // the sample of the reference rows, its sums of squares and (the set taken as it is) its norms' reciprocals: once a call
       KPOP_TRY(launch_sample_gather(a, r1, n_dims, s_rows, a_s, st));
-      if (na) ia_s = sa_s + (sas_bytes / 16);
-      KPOP_TRY(launch_mfma_sample_scalars(mscratch, chunk, r1, n_dims, s_rows, sa_s, ia_s, st));
-    }
-    if (select) {  // the sample of the reference rows and its norms: once a call
+      double *ia_w = na ? sa_s + (sas_bytes / 16) : nullptr;
+      KPOP_TRY(launch_mfma_sample_scalars(mscratch, chunk, r1, n_dims, s_rows, sa_s, ia_w, st));
+      ia_s = ia_w;
+    } else if (select) {  // the sample of the reference rows and its norms: once a call
       KPOP_TRY(launch_sample_gather(a, r1, n_dims, s_rows, a_s, st));
       KPOP_TRY(launch_row_sumsq(a_s, s_rows, n_dims, metric, sa_s, st));
     }
@@ -1539,17 +1507,17 @@ static int summary_large_impl(const double *m1, uint32_t r1, const double *m2, u
         KPOP_TRY(launch_mfma_query_prep(bq, q, r1, n_dims, metric, mscratch, chunk, st));
         KPOP_TRY(launch_rows_mfma_against(KIND, a_s, sa_s, s_rows, q, n_dims, srow, mscratch, chunk, r1, st));
         KPOP_TRY(launch_summary_fused_mfma(KIND, a, r1, q, n_dims, srow, s_rows, q0, keep_at_most, max_neighbours, out_stats, out_n, out_idx, out_dist, out_z, rows,
-                                           seg_i, scratch, mscratch, chunk, st, &lists));
+                                           seg_i, scratch, mscratch, chunk, st, &lists, ref));
         KPOP_TRY(launch_summary_refine(KIND, nullptr, a, r1, bq, q, n_dims, metric, p, q0, keep_at_most, max_neighbours, out_stats, out_n, out_idx, out_dist,
-                                       out_z, mscratch, chunk, st, lists, &gate, &flags));
+                                       out_z, mscratch, chunk, st, lists, &gate, &flags, nullptr, ref));
         KPOP_TRY(audit_fallback(gate, st));
       } else {
-        KPOP_TRY(launch_distance_rows_mfma(KIND, a, r1, bq, q, n_dims, metric, rows, mscratch, chunk, st, na != nullptr));
+        KPOP_TRY(launch_distance_rows_mfma(KIND, a, r1, bq, q, n_dims, metric, rows, mscratch, chunk, st, na != nullptr, ref));
         if (row_sample) KPOP_TRY(launch_rows_mfma_against(KIND, a_s, sa_s, s_rows, q, n_dims, srow, mscratch, chunk, r1, st, ia_s));  // (the chunk's query rows are prepared: the call above)
         KPOP_TRY(launch_summary_large(rows, q, r1, q0, keep_at_most, max_neighbours, out_stats, out_n, out_idx, out_dist, out_z, st, scratch, &lists, true,
                                       row_sample ? srow : nullptr, s_rows));
         KPOP_TRY(launch_summary_refine(KIND, rows, a, r1, bq, q, n_dims, metric, p, q0, keep_at_most, max_neighbours, out_stats, out_n, out_idx, out_dist,
-                                       out_z, mscratch, chunk, st, lists, &gate, &flags, na));
+                                       out_z, mscratch, chunk, st, lists, &gate, &flags, na, ref));
         KPOP_TRY(audit_fallback(gate, st));
         KPOP_TRY(audit_fallback(lists.n_failed, st));  // (rows whose sample-based brackets missed: the ten-pass kernel's)
       }
@@ -1574,7 +1542,13 @@ static int summary_large_impl(const double *m1, uint32_t r1, const double *m2, u
     double *seg = reinterpret_cast<double *>(wp), *a_s = reinterpret_cast<double *>(wp + bytes_seg),
            *srow = reinterpret_cast<double *>(wp + bytes_seg + bytes_as);
     void *scratch = wp + bytes_seg + bytes_as + bytes_srow;
-    KPOP_TRY(launch_sample_gather(a, r1, n_dims, s, a_s, st));
+    if (prep) {
+      const double *as_set = nullptr;
+      KPOP_TRY(prep->sample(a, s, kSampleRowsOnly, nullptr, st, &as_set, nullptr, nullptr));
+      a_s = const_cast<double *>(as_set);
+    } else {
+      KPOP_TRY(launch_sample_gather(a, r1, n_dims, s, a_s, st));
+    }
     for (uint32_t q0 = 0; q0 < r2; q0 += chunk) {
       const uint32_t q = std::min(chunk, r2 - q0);
       const double *bq = b + (uint64_t)q0 * n_dims;
@@ -1606,7 +1580,13 @@ static int summary_large_impl(const double *m1, uint32_t r1, const double *m2, u
   void *scratch = reinterpret_cast<char *>(ws) + row_bytes;
   double *a_s = reinterpret_cast<double *>(reinterpret_cast<char *>(ws) + row_bytes + sum_bytes);
   double *srow = reinterpret_cast<double *>(reinterpret_cast<char *>(ws) + row_bytes + sum_bytes + as_bytes);
-  if (s_rows) KPOP_TRY(launch_sample_gather(a, r1, n_dims, s_rows, a_s, st));
+  if (s_rows && prep) {
+    const double *as_set = nullptr;
+    KPOP_TRY(prep->sample(a, s_rows, kSampleRowsOnly, nullptr, st, &as_set, nullptr, nullptr));
+    a_s = const_cast<double *>(as_set);
+  } else if (s_rows) {
+    KPOP_TRY(launch_sample_gather(a, r1, n_dims, s_rows, a_s, st));
+  }
   for (uint32_t q0 = 0; q0 < r2; q0 += chunk) {
     const uint32_t q = std::min(chunk, r2 - q0);
     KPOP_TRY(rowwise_block<KIND>(a, r1, b + (uint64_t)q0 * n_dims, q, n_dims, metric, p, rows, st));
@@ -1650,17 +1630,20 @@ template <int KIND>
 static int summary_impl(const double *m1, uint32_t r1, const double *m2, uint32_t r2, uint32_t n_dims,
                         const double *metric, double p, int normalize, uint32_t keep_at_most, uint32_t max_neighbours,
                         void *work, double *out_stats, uint32_t *out_n, uint32_t *out_idx, double *out_dist,
-                        double *out_z, hipStream_t st) {
+                        double *out_z, hipStream_t st, kpop_refset *prep = nullptr) {
   const double *a, *b;
+  if (prep && normalize) KPOP_TRY(prep->prepared(st));
   if (normalize && r2 && summary_fits_wave(r1, n_dims, false) && ctx().tune_dbg != 4 && summary_batch_case(r1, n_dims, false)) {
     // The kernel that takes four rows of a wavefront at a time stages the second operand's rows itself: they go in as they are,
     // with their norms, and are divided on the way (the same quotients); only the few rows of the first operand get a divided copy.
-    DistWork w = carve(work, r1, r2, n_dims);
-    KPOP_TRY(launch_row_norms_pair<KIND>(m1, r1, w.n1, w.a, m2, r2, w.n2, nullptr, n_dims, metric, p, st));
-    return launch_summary<KIND, false>(w.a, r1, m2, r2, n_dims, metric, p, keep_at_most, max_neighbours, out_stats, out_n, out_idx, out_dist,
+    DistWork w = carve(work, r1, r2, n_dims, prep);
+    const double *a_div = w.a;
+    if (prep) KPOP_TRY(prep->divided(st, &a_div));  // (the set's divided copy: the same quotients)
+    KPOP_TRY(launch_row_norms_pair<KIND>(prep ? nullptr : m1, r1, w.n1, w.a, m2, r2, w.n2, nullptr, n_dims, metric, p, st));
+    return launch_summary<KIND, false>(a_div, r1, m2, r2, n_dims, metric, p, keep_at_most, max_neighbours, out_stats, out_n, out_idx, out_dist,
                                        out_z, st, w.n2);
   }
-  KPOP_TRY(prepare_operands<KIND>(m1, r1, m2, r2, n_dims, metric, p, normalize, work, &a, &b, st));
+  KPOP_TRY(prepare_operands<KIND>(m1, r1, m2, r2, n_dims, metric, p, normalize, work, &a, &b, st, prep));
   if (r1 >= 1 && r1 <= kSummaryMaxR1 && !summary_fits_wave(r1, n_dims, false) && ctx().tune_dbg != 4) {
     // A first operand that does not fit LDS (100 x 200 dimensions, 500 x 64, anything of 513..4,096 rows): the distances of
     // a chunk of second-operand rows into the workspace (the tiled kernel), then the summary over them -- one wavefront per
@@ -1726,6 +1709,7 @@ struct LongListSource {  // where a row's distances come from
   uint32_t n_dims = 0;
   int kind = 0, normalize = 0;
   double p = 2.0;
+  kpop_refset *rs = nullptr;  // ... or a resident set as the first operand (kpop_refset_distance_summary)
 };
 
 static int fill_long_lists(const LongListSource &src, uint32_t r1, uint32_t r2, uint32_t max_neighbours, const double *out_stats, const uint32_t *out_n,
@@ -1739,7 +1723,7 @@ static int fill_long_lists(const LongListSource &src, uint32_t r1, uint32_t r2, 
   DevBuf drow, dw, ka, kb, va, vb, scr;
   if (!src.d_rows) {
     KPOP_TRY(drow.alloc((uint64_t)r1 * 8));
-    KPOP_TRY(dw.alloc(kpop_dev_distance_workspace_bytes(r1, 1, src.n_dims)));
+    KPOP_TRY(dw.alloc(kpop_dev_distance_workspace_bytes(src.rs ? 0 : r1, 1, src.n_dims)));
   }
   KPOP_TRY(ka.alloc((uint64_t)r1 * 8));
   KPOP_TRY(kb.alloc((uint64_t)r1 * 8));
@@ -1749,7 +1733,9 @@ static int fill_long_lists(const LongListSource &src, uint32_t r1, uint32_t r2, 
   std::vector<uint64_t> hk;
   for (uint32_t j : todo) {
     const double *row = src.d_rows ? src.d_rows + (uint64_t)j * r1 : drow.as<double>();
-    if (!src.d_rows)
+    if (!src.d_rows && src.rs)
+      KPOP_TRY(refset_dev_rowwise(src.rs, src.d2 + (uint64_t)j * src.n_dims, 1, dw.p, drow.as<double>(), st));
+    else if (!src.d_rows)
       KPOP_TRY(kpop_dev_distance_rowwise(src.d1, r1, src.d2 + (uint64_t)j * src.n_dims, 1, src.n_dims, src.dm, src.kind, src.p, src.normalize, dw.p,
                                          drow.as<double>(), st));
     long_list_keys_kernel<<<dim3(div_up(r1, 256)), dim3(256), 0, st>>>(row, r1, ka.as<uint64_t>(), va.as<uint32_t>());
@@ -1785,6 +1771,67 @@ static int check_kind(int kind, double p, const char *who) {
     KPOP_FAIL(KPOP_ERR_INVALID, "%s: unknown distance kind %d", who, kind);
   if (kind == KPOP_MINKOWSKI && !(p >= 0.0)) KPOP_FAIL(KPOP_ERR_INVALID, "%s: negative Minkowski power", who);  // lib/Space.ml:222-223
   return 0;
+}
+
+// the three kinds of every entry point; prep: the first operand is a resident set (refset.h), nullptr otherwise
+static int rowwise_by_kind(const double *d_m1, uint32_t r1, const double *d_norms1, const double *d_m2, uint32_t r2, uint32_t n_dims, const double *d_metric,
+                           int kind, double p, int normalize, void *d_work, double *d_out, hipStream_t st, kpop_refset *prep) {
+  switch (kind) {
+    case KPOP_EUCLIDEAN: return rowwise_impl<KPOP_EUCLIDEAN>(d_m1, r1, d_m2, r2, n_dims, d_metric, p, normalize, d_work, d_out, st, d_norms1, prep);
+    case KPOP_COSINE: return rowwise_impl<KPOP_COSINE>(d_m1, r1, d_m2, r2, n_dims, d_metric, p, normalize, d_work, d_out, st, d_norms1, prep);
+    default: return rowwise_impl<KPOP_MINKOWSKI>(d_m1, r1, d_m2, r2, n_dims, d_metric, p, normalize, d_work, d_out, st, d_norms1, prep);
+  }
+}
+static int summary_by_kind(const double *d_m1, uint32_t r1, const double *d_m2, uint32_t r2, uint32_t n_dims, const double *d_metric, int kind, double p,
+                           int normalize, uint32_t keep_at_most, uint32_t max_neighbours, void *d_work, double *d_out_stats, uint32_t *d_out_n,
+                           uint32_t *d_out_idx, double *d_out_dist, double *d_out_z, hipStream_t st, kpop_refset *prep) {
+  if (r1 > kSummaryMaxR1) {
+    switch (kind) {
+      case KPOP_EUCLIDEAN:
+        return summary_large_impl<KPOP_EUCLIDEAN>(d_m1, r1, d_m2, r2, n_dims, d_metric, p, normalize, keep_at_most,
+                                                  max_neighbours, d_work, d_out_stats, d_out_n, d_out_idx, d_out_dist, d_out_z, st, prep);
+      case KPOP_COSINE:
+        return summary_large_impl<KPOP_COSINE>(d_m1, r1, d_m2, r2, n_dims, d_metric, p, normalize, keep_at_most,
+                                               max_neighbours, d_work, d_out_stats, d_out_n, d_out_idx, d_out_dist, d_out_z, st, prep);
+      default:
+        return summary_large_impl<KPOP_MINKOWSKI>(d_m1, r1, d_m2, r2, n_dims, d_metric, p, normalize, keep_at_most,
+                                                  max_neighbours, d_work, d_out_stats, d_out_n, d_out_idx, d_out_dist, d_out_z, st, prep);
+    }
+  }
+  switch (kind) {
+    case KPOP_EUCLIDEAN:
+      return summary_impl<KPOP_EUCLIDEAN>(d_m1, r1, d_m2, r2, n_dims, d_metric, p, normalize, keep_at_most, max_neighbours,
+                                          d_work, d_out_stats, d_out_n, d_out_idx, d_out_dist, d_out_z, st, prep);
+    case KPOP_COSINE:
+      return summary_impl<KPOP_COSINE>(d_m1, r1, d_m2, r2, n_dims, d_metric, p, normalize, keep_at_most, max_neighbours,
+                                       d_work, d_out_stats, d_out_n, d_out_idx, d_out_dist, d_out_z, st, prep);
+    default:
+      return summary_impl<KPOP_MINKOWSKI>(d_m1, r1, d_m2, r2, n_dims, d_metric, p, normalize, keep_at_most, max_neighbours,
+                                          d_work, d_out_stats, d_out_n, d_out_idx, d_out_dist, d_out_z, st, prep);
+  }
+}
+
+// kpop_dev_refset_distance_rowwise / _summary (refset.hip checks the handle): the bodies of kpop_dev_distance_rowwise / _summary
+int refset_dev_rowwise(kpop_refset *rs, const double *d_m2, uint32_t r2, void *d_work, double *d_out, hipStream_t st) {
+  if (rs->r1 == 0 || r2 == 0) return KPOP_OK;
+  if (!d_m2 || !d_out || (rs->normalize && !d_work)) KPOP_FAIL(KPOP_ERR_INVALID, "kpop_dev_refset_distance_rowwise: null argument (the workspace is needed when normalising)");
+  return rowwise_by_kind(rs->rows, rs->r1, nullptr, d_m2, r2, rs->n_dims, rs->metric, rs->kind, rs->p, rs->normalize, d_work, d_out, st, rs);
+}
+int refset_dev_summary(kpop_refset *rs, const double *d_m2, uint32_t r2, uint32_t keep_at_most, uint32_t max_neighbours, void *d_work,
+                       double *d_out_stats, uint32_t *d_out_n, uint32_t *d_out_idx, double *d_out_dist, double *d_out_z, hipStream_t st) {
+  if (r2 == 0) return KPOP_OK;
+  if (!d_m2 || !d_out_stats || !d_out_n || (rs->normalize && !d_work)) KPOP_FAIL(KPOP_ERR_INVALID, "kpop_dev_refset_distance_summary: null argument");
+  if (max_neighbours && (!d_out_idx || !d_out_dist || !d_out_z)) KPOP_FAIL(KPOP_ERR_INVALID, "kpop_dev_refset_distance_summary: null neighbour buffers");
+  return summary_by_kind(rs->rows, rs->r1, d_m2, r2, rs->n_dims, rs->metric, rs->kind, rs->p, rs->normalize, keep_at_most, max_neighbours, d_work, d_out_stats,
+                         d_out_n, d_out_idx, d_out_dist, d_out_z, st, rs);
+}
+int refset_fill_long_lists(kpop_refset *rs, const double *d_m2, uint32_t r2, uint32_t max_neighbours, const double *out_stats, const uint32_t *out_n,
+                           uint32_t *out_idx, double *out_dist, double *out_z, hipStream_t st) {
+  LongListSource src;
+  src.rs = rs;
+  src.d2 = d_m2;
+  src.n_dims = rs->n_dims;
+  return fill_long_lists(src, rs->r1, r2, max_neighbours, out_stats, out_n, out_idx, out_dist, out_z, st);
 }
 
 }  // namespace kpop
@@ -1873,12 +1920,7 @@ extern "C" int kpop_dev_distance_rowwise_norms(const double *d_m1, uint32_t r1, 
   if (!d_m1 || !d_m2 || !d_metric || !d_out || ((normalize || n_dims >= kLongD) && !d_work))
     KPOP_FAIL(KPOP_ERR_INVALID, "kpop_dev_distance_rowwise: null argument (the workspace is needed when normalising and for rows of %u dimensions or more)", kLongD);
   if (n_dims == 0) KPOP_FAIL(KPOP_ERR_INVALID, "kpop_dev_distance_rowwise: n_dims must be positive");
-  hipStream_t st = as_stream(stream);
-  switch (kind) {
-    case KPOP_EUCLIDEAN: return rowwise_impl<KPOP_EUCLIDEAN>(d_m1, r1, d_m2, r2, n_dims, d_metric, p, normalize, d_work, d_out, st, d_norms1);
-    case KPOP_COSINE: return rowwise_impl<KPOP_COSINE>(d_m1, r1, d_m2, r2, n_dims, d_metric, p, normalize, d_work, d_out, st, d_norms1);
-    default: return rowwise_impl<KPOP_MINKOWSKI>(d_m1, r1, d_m2, r2, n_dims, d_metric, p, normalize, d_work, d_out, st, d_norms1);
-  }
+  return rowwise_by_kind(d_m1, r1, d_norms1, d_m2, r2, n_dims, d_metric, kind, p, normalize, d_work, d_out, as_stream(stream), nullptr);
 }
 
 extern "C" int kpop_dev_distance_summary(const double *d_m1, uint32_t r1, const double *d_m2, uint32_t r2,
@@ -1894,31 +1936,8 @@ extern "C" int kpop_dev_distance_summary(const double *d_m1, uint32_t r1, const 
   if (max_neighbours && (!d_out_idx || !d_out_dist || !d_out_z))
     KPOP_FAIL(KPOP_ERR_INVALID, "kpop_dev_distance_summary: null neighbour buffers");
   if (n_dims == 0) KPOP_FAIL(KPOP_ERR_INVALID, "kpop_dev_distance_summary: n_dims must be positive");
-  hipStream_t st = as_stream(stream);
-  if (r1 > kSummaryMaxR1) {
-    switch (kind) {
-      case KPOP_EUCLIDEAN:
-        return summary_large_impl<KPOP_EUCLIDEAN>(d_m1, r1, d_m2, r2, n_dims, d_metric, p, normalize, keep_at_most,
-                                                  max_neighbours, d_work, d_out_stats, d_out_n, d_out_idx, d_out_dist, d_out_z, st);
-      case KPOP_COSINE:
-        return summary_large_impl<KPOP_COSINE>(d_m1, r1, d_m2, r2, n_dims, d_metric, p, normalize, keep_at_most,
-                                               max_neighbours, d_work, d_out_stats, d_out_n, d_out_idx, d_out_dist, d_out_z, st);
-      default:
-        return summary_large_impl<KPOP_MINKOWSKI>(d_m1, r1, d_m2, r2, n_dims, d_metric, p, normalize, keep_at_most,
-                                                  max_neighbours, d_work, d_out_stats, d_out_n, d_out_idx, d_out_dist, d_out_z, st);
-    }
-  }
-  switch (kind) {
-    case KPOP_EUCLIDEAN:
-      return summary_impl<KPOP_EUCLIDEAN>(d_m1, r1, d_m2, r2, n_dims, d_metric, p, normalize, keep_at_most, max_neighbours,
-                                          d_work, d_out_stats, d_out_n, d_out_idx, d_out_dist, d_out_z, st);
-    case KPOP_COSINE:
-      return summary_impl<KPOP_COSINE>(d_m1, r1, d_m2, r2, n_dims, d_metric, p, normalize, keep_at_most, max_neighbours,
-                                       d_work, d_out_stats, d_out_n, d_out_idx, d_out_dist, d_out_z, st);
-    default:
-      return summary_impl<KPOP_MINKOWSKI>(d_m1, r1, d_m2, r2, n_dims, d_metric, p, normalize, keep_at_most, max_neighbours,
-                                          d_work, d_out_stats, d_out_n, d_out_idx, d_out_dist, d_out_z, st);
-  }
+  return summary_by_kind(d_m1, r1, d_m2, r2, n_dims, d_metric, kind, p, normalize, keep_at_most, max_neighbours, d_work, d_out_stats, d_out_n, d_out_idx,
+                         d_out_dist, d_out_z, as_stream(stream), nullptr);
 }
 
 extern "C" int kpop_dev_summarize_distances(const double *d_dist, uint32_t r2, uint32_t r1, uint32_t keep_at_most,

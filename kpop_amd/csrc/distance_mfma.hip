@@ -24,6 +24,7 @@
 #include "common.h"
 #include "summary_types.h"
 #include "space_ops.h"
+#include "refset.h"
 
 namespace kpop {
 
@@ -1036,7 +1037,8 @@ struct MfmaScratch {
   unsigned long long *smax;
   uint32_t *rc, *n_failed;
 };
-static MfmaScratch carve_mfma(void *scratch, uint32_t q, uint32_t r1, uint32_t n_dims, uint32_t bm_rows = 0) {  // (bm_rows: rows of the copy times the metric, q unless said)
+// (ref: the reference rows' scalars live in a resident set -- kpop_refset -- and are read from there; their room in the scratch stays unused)
+static MfmaScratch carve_mfma(void *scratch, uint32_t q, uint32_t r1, uint32_t n_dims, uint32_t bm_rows = 0, const RefScalars *ref = nullptr) {  // (bm_rows: rows of the copy times the metric, q unless said)
   char *p = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(scratch) + 255) & ~(uintptr_t)255);
   MfmaScratch M;
   M.bm = reinterpret_cast<double *>(p);
@@ -1052,6 +1054,11 @@ static MfmaScratch carve_mfma(void *scratch, uint32_t q, uint32_t r1, uint32_t n
   M.rc = reinterpret_cast<uint32_t *>(p);
   p += ((uint64_t)q * kRowCountsWords * 4 + 255) & ~255ull;
   M.n_failed = reinterpret_cast<uint32_t *>(p);
+  if (ref) {
+    M.sa = const_cast<double *>(ref->sa);
+    M.ia = const_cast<double *>(ref->ia);
+    M.smax = const_cast<unsigned long long *>(ref->smax);
+  }
   return M;
 }
 
@@ -1213,8 +1220,8 @@ int launch_distance_rowwise_mfma(int kind, const double *a, uint32_t r1, const d
 // the one-kernel path's pass (declared in summary_large.hip, which owns its scratch): q query rows (their fragments and norms in the
 // matrix-core scratch: launch_mfma_query_prep) against all r1 reference rows, a block a (stripe, 128 query rows)
 int launch_select_mfma(int kind, const double *a, uint32_t r1, uint32_t q, uint32_t n_dims, const void *mscratch, uint32_t q_room, const FusedThr *thr, double *seg,
-                       uint32_t *seg_i, StripeRec *rec, double *part, RowCounts *cnt, uint32_t *nb_idx, double *nb_d, uint32_t n_stripes, hipStream_t st) {
-  const MfmaScratch M = carve_mfma(const_cast<void *>(mscratch), q_room, r1, n_dims);
+                       uint32_t *seg_i, StripeRec *rec, double *part, RowCounts *cnt, uint32_t *nb_idx, double *nb_d, uint32_t n_stripes, hipStream_t st, const RefScalars *ref) {
+  const MfmaScratch M = carve_mfma(const_cast<void *>(mscratch), q_room, r1, n_dims, 0, ref);
   const dim3 grid(n_stripes, div_up(q, 128u));
 #define KPOP_SEL(K, KSV) summary_select_mfma_kernel<K, KSV><<<grid, dim3(256), 0, st>>>(a, r1, M.bm, q, n_dims, M.sa, M.sb, thr, seg, seg_i, rec, part, cnt, nb_idx, nb_d, n_stripes)
   if (kind == KPOP_EUCLIDEAN) {
@@ -1286,6 +1293,17 @@ int launch_mfma_sample_scalars(const void *scratch, uint32_t q_room, uint32_t r1
   KPOP_LAUNCH_CHECK();
   return 0;
 }
+// (a resident set's: the same kernel out of the set's own arrays, and row_sumsq_kernel with the running maximum of a set that grows)
+int launch_gather_sample_scalars(const double *sa, const double *ia, uint32_t r1, uint32_t s, double *sas, double *ias, hipStream_t st) {
+  gather_sample_scalars_kernel<<<dim3(div_up(s, 256u)), dim3(256), 0, st>>>(sa, ia, r1, s, sas, ias);
+  KPOP_LAUNCH_CHECK();
+  return 0;
+}
+int launch_row_sumsq_max(const double *x, uint32_t rows, uint32_t n_dims, const double *metric, double *out, unsigned long long *smax, hipStream_t st) {
+  row_sumsq_kernel<<<dim3(std::min(div_up(rows, 16), 4096u)), dim3(256), 0, st>>>(x, rows, n_dims, metric, out, nullptr, smax);
+  KPOP_LAUNCH_CHECK();
+  return 0;
+}
 int launch_row_sumsq(const double *x, uint32_t rows, uint32_t n_dims, const double *metric, double *out, hipStream_t st) {
   row_sumsq_kernel<<<dim3(std::min(div_up(rows, 16), 4096u)), dim3(256), 0, st>>>(x, rows, n_dims, metric, out, nullptr, nullptr);
   KPOP_LAUNCH_CHECK();
@@ -1294,8 +1312,8 @@ int launch_row_sumsq(const double *x, uint32_t rows, uint32_t n_dims, const doub
 
 // the chunk's approximate distance rows (into `rows`), and the flags of its fall-back cleared
 int launch_distance_rows_mfma(int kind, const double *a, uint32_t r1, const double *b, uint32_t q, uint32_t n_dims, const double *metric, double *rows,
-                              void *scratch, uint32_t q_room, hipStream_t st, bool a_raw) {
-  const MfmaScratch M = carve_mfma(scratch, q_room, r1, n_dims);
+                              void *scratch, uint32_t q_room, hipStream_t st, bool a_raw, const RefScalars *ref) {
+  const MfmaScratch M = carve_mfma(scratch, q_room, r1, n_dims, 0, ref);
   KPOP_HIP(hipMemsetAsync(M.rc, 0, (uint64_t)q * kRowCountsWords * 4, st));
   KPOP_HIP(hipMemsetAsync(M.n_failed, 0, 256, st));
   return kind == KPOP_EUCLIDEAN ? launch_rows_mfma<KPOP_EUCLIDEAN>(a, r1, b, q, n_dims, metric, rows, M, st, a_raw)
@@ -1306,8 +1324,8 @@ int launch_distance_rows_mfma(int kind, const double *a, uint32_t r1, const doub
 int launch_summary_refine(int kind, const double *rows, const double *a, uint32_t r1, const double *b, uint32_t q, uint32_t n_dims, const double *metric,
                           double p, uint32_t row0, uint32_t keep_at_most, uint32_t max_neighbours, double *out_stats, uint32_t *out_n, uint32_t *out_idx,
                           double *out_dist, double *out_z, void *scratch, uint32_t q_room, hipStream_t st, const SummaryLists &lists, const uint32_t **gate,
-                          const void **row_counts, const double *na) {
-  const MfmaScratch M = carve_mfma(scratch, q_room, r1, n_dims);
+                          const void **row_counts, const double *na, const RefScalars *ref) {
+  const MfmaScratch M = carve_mfma(scratch, q_room, r1, n_dims, 0, ref);
   const uint32_t req_len = keep_at_most ? keep_at_most : r1;
   // |u~ - u| <= gamma (|a|^2 + |b|^2): n_dims products and additions of the contraction and of the two norms at 2^-53 each, the
   // chain's own roundings, and a factor of ten on top

@@ -73,7 +73,7 @@ struct kpop_pipeline {
   const kpop_twister *tw = nullptr;
   kpop_pipeline_config cfg{};
   uint32_t n_classes = 0, n_dims = 0;
-  double *d_classes = nullptr, *d_metric = nullptr, *d_class_norms = nullptr;
+  kpop_refset *classes = nullptr;  // the class vectors as a resident reference set: rows, metric, and what of them every chunk would compute again
   hipStream_t s_h2d = nullptr, s_compute = nullptr, s_d2h = nullptr;
   std::vector<RingSlot> ring;
   uint64_t next_chunk = 0;
@@ -157,9 +157,7 @@ static void destroy(kpop_pipeline *pl) {
   for (int i = 0; i < kTicketRing; ++i)
     if (pl->ticket_done[i]) (void)hipEventDestroy(pl->ticket_done[i]);
   for (hipEvent_t e : pl->tl_events) (void)hipEventDestroy(e);
-  if (pl->d_classes) (void)hipFree(pl->d_classes);
-  if (pl->d_metric) (void)hipFree(pl->d_metric);
-  if (pl->d_class_norms) (void)hipFree(pl->d_class_norms);
+  if (pl->classes) (void)kpop_refset_free(pl->classes);
   if (pl->s_compute) {
     // the per-stream workspace of the genome kernel dies with its stream
     Context &c = ctx();
@@ -247,20 +245,10 @@ extern "C" int kpop_pipeline_create(const kpop_twister *tw, const double *classe
       break;
     }
     if (need_classes) {
-      const uint64_t cb = (uint64_t)n_classes * tw->n_dims * 8, mb = (uint64_t)tw->n_dims * 8;
-      PL_HIP(hipMalloc((void **)&pl->d_classes, cb));
-      PL_HIP(hipMalloc((void **)&pl->d_metric, mb));
-      PL_HIP(hipMemcpy(pl->d_classes, classes, cb, hipMemcpyHostToDevice));
-      PL_HIP(hipMemcpy(pl->d_metric, metric, mb, hipMemcpyHostToDevice));
-      // the norms of the class vectors (lib/Matrix.ml:42-76) once, not with every chunk
-      if (pl->cfg.normalize_distances && n_classes < 128) {
-        PL_HIP(hipMalloc((void **)&pl->d_class_norms, (uint64_t)n_classes * 8));
-        if (kpop_dev_row_norms(pl->d_classes, n_classes, tw->n_dims, pl->d_metric, pl->cfg.kind, pl->cfg.p, pl->d_class_norms, nullptr) != KPOP_OK) {
-          rc = KPOP_ERR_HIP;
-          break;
-        }
-        PL_HIP(hipStreamSynchronize(nullptr));
-      }
+      // the class vectors' norms (lib/Matrix.ml:42-76), and whatever else of them a chunk's route wants, once -- not with every chunk,
+      // whether they are a few dozen classes or a database of 70,000 rows
+      rc = kpop_refset_create(classes, n_classes, tw->n_dims, metric, pl->cfg.kind, pl->cfg.p, pl->cfg.normalize_distances, 0, &pl->classes);
+      if (rc != KPOP_OK) break;
     }
 #undef PL_HIP
   } while (0);
@@ -384,7 +372,7 @@ static int pipeline_submit_impl(kpop_pipeline *pl, const uint8_t *bases, const u
     KPOP_TRY(s.offsets.ensure((uint64_t)(cap_n + 1) * 8));
     KPOP_TRY(s.twisted.ensure((uint64_t)cap_n * D * 8));
     if (outs & KPOP_OUT_DISTANCES) KPOP_TRY(s.dist.ensure((uint64_t)cap_n * C * 8));
-    if (outs & (KPOP_OUT_DISTANCES | KPOP_OUT_SUMMARY)) KPOP_TRY(s.work.ensure(kpop_dev_distance_workspace_bytes(C, cap_n, D)));
+    if (outs & (KPOP_OUT_DISTANCES | KPOP_OUT_SUMMARY)) KPOP_TRY(s.work.ensure(kpop_dev_refset_workspace_bytes(pl->classes, cap_n)));
     if (outs & KPOP_OUT_SUMMARY) {
       KPOP_TRY(s.stats.ensure((uint64_t)cap_n * 4 * 8));
       KPOP_TRY(s.nn.ensure((uint64_t)cap_n * 4));
@@ -426,13 +414,10 @@ static int pipeline_submit_impl(kpop_pipeline *pl, const uint8_t *bases, const u
     const bool early = (outs & KPOP_OUT_TWISTED) && (outs & (KPOP_OUT_DISTANCES | KPOP_OUT_SUMMARY));
     if (early) KPOP_HIP(hipEventRecord(s.twist_done, pl->s_compute));
     if (outs & KPOP_OUT_DISTANCES)
-      KPOP_TRY(kpop_dev_distance_rowwise_norms(pl->d_classes, C, pl->d_class_norms, s.twisted.as<double>(), n, D, pl->d_metric, pl->cfg.kind,
-                                               pl->cfg.p, pl->cfg.normalize_distances, s.work.p, s.dist.as<double>(), pl->s_compute));
+      KPOP_TRY(kpop_dev_refset_distance_rowwise(pl->classes, s.twisted.as<double>(), n, s.work.p, s.dist.as<double>(), pl->s_compute));
     if (outs & KPOP_OUT_SUMMARY)
-      KPOP_TRY(kpop_dev_distance_summary(pl->d_classes, C, s.twisted.as<double>(), n, D, pl->d_metric, pl->cfg.kind, pl->cfg.p,
-                                         pl->cfg.normalize_distances, pl->cfg.keep_at_most, mn, s.work.p, s.stats.as<double>(),
-                                         s.nn.as<uint32_t>(), s.idx.as<uint32_t>(), s.ndist.as<double>(), s.z.as<double>(),
-                                         pl->s_compute));
+      KPOP_TRY(kpop_dev_refset_distance_summary(pl->classes, s.twisted.as<double>(), n, pl->cfg.keep_at_most, mn, s.work.p, s.stats.as<double>(),
+                                                s.nn.as<uint32_t>(), s.idx.as<uint32_t>(), s.ndist.as<double>(), s.z.as<double>(), pl->s_compute));
     KPOP_TRY(mark(n_chunks, 3, pl->s_compute));
     KPOP_HIP(hipEventRecord(s.compute_done, pl->s_compute));
     // down

@@ -18,6 +18,7 @@
 #include "common.h"
 #include "summary_types.h"
 #include "space_ops.h"
+#include "refset.h"
 
 namespace kpop {
 
@@ -1835,11 +1836,11 @@ int launch_summary_fused(int kind, const double *a, uint32_t r1, const double *b
 // well), the pass, the finish over the stripes' segments (values in `seg`, columns in `seg_i`, both [n_rows][r1]).  What it reports is
 // approximate: `lists` is what the exact refinement (summary_refine_kernel) reads.
 int launch_select_mfma(int kind, const double *a, uint32_t r1, uint32_t q, uint32_t n_dims, const void *mscratch, uint32_t q_room, const FusedThr *thr, double *seg,
-                       uint32_t *seg_i, StripeRec *rec, double *part, RowCounts *cnt, uint32_t *nb_idx, double *nb_d, uint32_t n_stripes, hipStream_t st);
+                       uint32_t *seg_i, StripeRec *rec, double *part, RowCounts *cnt, uint32_t *nb_idx, double *nb_d, uint32_t n_stripes, hipStream_t st, const RefScalars *ref);
 int launch_summary_fused_mfma(int kind, const double *a, uint32_t r1, uint32_t n_rows, uint32_t n_dims, const double *srow, uint32_t s, uint32_t row0,
                               uint32_t keep_at_most, uint32_t max_neighbours, double *out_stats, uint32_t *out_n, uint32_t *out_idx, double *out_dist,
                               double *out_z, double *seg, uint32_t *seg_i, void *scratch, const void *mscratch, uint32_t q_room, hipStream_t st,
-                              SummaryLists *lists) {
+                              SummaryLists *lists, const RefScalars *ref) {
   const uint32_t req_len = keep_at_most ? keep_at_most : r1;
   const uint32_t n_stripes = (r1 + kStripe - 1) / kStripe;  // blocks of the matrix-core kernel along the reference rows; it keeps FOUR records a stripe
   FusedScratch F;
@@ -1849,7 +1850,7 @@ int launch_summary_fused_mfma(int kind, const double *a, uint32_t r1, uint32_t n
   // its record, of zeros: every record of a row is written, see the kernel)
   fused_sample_kernel<false><<<dim3(n_rows), dim3(kLT), 0, st>>>(srow, s, r1, req_len, F.info, F.cnt, F.thr);
   KPOP_LAUNCH_CHECK();
-  KPOP_TRY(launch_select_mfma(kind, a, r1, n_rows, n_dims, mscratch, q_room, F.thr, seg, seg_i, F.rec, F.part, F.cnt, F.nb_idx, F.nb_d, n_stripes, st));
+  KPOP_TRY(launch_select_mfma(kind, a, r1, n_rows, n_dims, mscratch, q_room, F.thr, seg, seg_i, F.rec, F.part, F.cnt, F.nb_idx, F.nb_d, n_stripes, st, ref));
   fused_finish_kernel<true><<<dim3(n_rows), dim3(kLT), 0, st>>>(seg, r1, row0, req_len, max_neighbours, F.info, F.thr, F.cnt, F.rec, F.part, 4 * n_stripes, F.pre,
                                                           F.ccand, fused_cand_cap(r1), F.nb_idx, F.nb_d, F.n_failed, out_stats, out_n, out_idx, out_dist,
                                                           out_z, seg_i, F.ccand_i, kStripe / 4, (uint64_t)n_stripes * kStripe);
