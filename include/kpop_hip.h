@@ -16,13 +16,41 @@
  *     H2D / compute / D2H internally;
  *   - device entry points (kpop_dev_*) take pointers that already live in HBM
  *     plus a hipStream_t passed as void* (NULL = default stream); they only
- *     enqueue work and never synchronise;
+ *     enqueue work and do not synchronise, with these exceptions: kpop_dev_ca
+ *     (host work between its launches: complete when it returns),
+ *     kpop_dev_refset_wrap (it waits for its preparation pass), the first
+ *     call on a stream that needs more of the library's workspace than any
+ *     before it (it waits for the device, frees the block and allocates a
+ *     larger one; kpop_dev_workspace_reserve[_stream] ahead of time avoids
+ *     that), and kpop_dev_distance_summary against 65,536 rows and more
+ *     under kpop_tune("summary_audit", 1) (it reads its counter back).  The
+ *     completion of neighbour lists longer than 2,048 entries synchronises
+ *     too: it belongs to the HOST entry points (kpop_distance_summary,
+ *     kpop_refset_distance_summary), the device ones report such a row's
+ *     length and fill 2,048 entries;
  *   - call from the PARENT process only (a HIP context does not survive
  *     fork(); the reference's fork()ed workers at lib/Twister.ml:90 are
- *     replaced wholesale, not per-worker).  Host entry points of one device
- *     run one at a time (the library serialises them); device entry points on
- *     different streams may run concurrently (the library's scratch is per
- *     stream);
+ *     replaced wholesale, not per-worker).
+ *   - threads and streams (tests/test_gpu_concurrency.py holds the library
+ *     to every line of this).  Host entry points of one device slot run one
+ *     at a time, whatever threads call them (a lock per slot; their device
+ *     scratch is an arena that every call rewinds to where it found it).
+ *     Device entry points on DIFFERENT streams may be enqueued back to back
+ *     and run concurrently: the library's scratch is a block per stream (two
+ *     for kpop_dev_count_twist_packed, and a stream with four events of the
+ *     library's own beside a caller's stream for the two-lane summary).
+ *     Calls on ONE stream may follow each other without synchronisation,
+ *     whichever routes they take: each leaves the stream's block ready for
+ *     the next.  One stream is driven by one host thread at a time.  A
+ *     stream's workspace lives until kpop_shutdown (a pipeline's compute
+ *     stream's: until kpop_pipeline_destroy).  Handles made outside a host
+ *     entry point's scope by a second thread (kpop_twister_load,
+ *     kpop_refset_create) get device memory of their own, never the arena's.
+ *     kpop_last_error() is per thread.  A host thread works on the device
+ *     slot it chose (kpop_use_device; slot 0 until it says otherwise), with
+ *     handles made on that slot.  kpop_tune knobs are per slot, set for all
+ *     slots at once, and must not change while a call is in flight on any
+ *     thread or stream;
  *   - kpop_init(device) drives one GPU; kpop_init_devices(devices, n) drives
  *     n of them from ONE process (SURVEY.md 8b "multi-GPU sharding is
  *     internal"): handles (twisters, pipelines) belong to the device slot that

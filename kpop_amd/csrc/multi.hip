@@ -270,7 +270,8 @@ extern "C" int kpop_twister_replicate(const kpop_twister *src, int slot, kpop_tw
   tw->d_rblk = nullptr;
   tw->d_sorted_hash = nullptr;
   tw->d_direct = nullptr;  // (the copy keeps the rows in rank order only: device_bytes below)
-  if (src->d_direct) tw->device_bytes -= (1ull << (2 * src->k)) * src->d_pad * 8;
+  if (src->d_direct) tw->device_bytes -= (src->direct_hi - src->direct_lo) * src->d_pad * 8;  // (a slice's table covers its hash range only)
+  tw->direct_lo = tw->direct_hi = 0;
   const int prev = current_slot();
   int rc = use_slot(slot);
   if (rc == 0) do {

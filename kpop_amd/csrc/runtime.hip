@@ -111,12 +111,23 @@ extern "C" int kpop_device_count(void) {
 
 int Context::aux_for(hipStream_t st, AuxLane **out) {
   std::lock_guard<std::mutex> g(ws_mu);
-  AuxLane &a = aux_by_stream[st];
-  if (!a.stream) {
-    KPOP_HIP(hipStreamCreateWithFlags(&a.stream, hipStreamNonBlocking));
-    for (hipEvent_t *e : {&a.fork, &a.join, &a.step[0], &a.step[1]}) KPOP_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
+  auto it = aux_by_stream.find(st);
+  if (it == aux_by_stream.end()) {
+    // made in a local and committed to the map only when the stream and all four events exist: a lane that failed half way
+    // would hand null events to the next call's hipEventRecord
+    AuxLane a;
+    hipError_t e = hipStreamCreateWithFlags(&a.stream, hipStreamNonBlocking);
+    for (hipEvent_t *ev : {&a.fork, &a.join, &a.step[0], &a.step[1]})
+      if (e == hipSuccess) e = hipEventCreateWithFlags(ev, hipEventDisableTiming);
+    if (e != hipSuccess) {
+      for (hipEvent_t ev : {a.fork, a.join, a.step[0], a.step[1]})
+        if (ev) (void)hipEventDestroy(ev);
+      if (a.stream) (void)hipStreamDestroy(a.stream);
+      KPOP_FAIL(KPOP_ERR_HIP, "%s:%d: the summary's second stream and its events -> %s", __FILE__, __LINE__, hipGetErrorString(e));
+    }
+    it = aux_by_stream.emplace(st, a).first;
   }
-  *out = &a;
+  *out = &it->second;
   return 0;
 }
 

@@ -64,6 +64,79 @@ def test_metric_matches_oracle(oracle):
         kpop_amd.metric_compute([1.0], kpop_amd.METRIC_POWERS, -1.0, 1.0, 2.0)  # Negative_power, lib/Space.ml:124
 
 
+def _last_error_is_per_thread():
+    """(the body of the test below; runs in a process of its own, where no kpop_init has happened)"""
+    import ctypes as C
+    import threading
+    from kpop_amd import _lib
+    lib = _lib.load()
+    assert lib.kpop_device_slots() == 0
+    turn = [threading.Event() for _ in range(4)]
+    seen, errors = {}, []
+
+    def msg():
+        return lib.kpop_last_error().decode()
+
+    def thread_a():
+        try:
+            seen["a0"] = msg()
+            rc = lib.kpop_dev_workspace_reserve_stream(4096, None)  # a device entry point without kpop_init
+            seen["a_rc"], seen["a1"] = rc, msg()
+            turn[0].set()
+            assert turn[1].wait(30)
+            seen["a2"] = msg()  # ... after B's failure
+            rc = lib.kpop_dev_count_twist(None, None, None, 1, 0, 0, 0, 1, None, None)
+            seen["a_rc2"], seen["a3"] = rc, msg()
+            turn[2].set()
+        except BaseException as e:  # noqa: BLE001
+            errors.append(e)
+            for t in turn:
+                t.set()
+
+    def thread_b():
+        try:
+            assert turn[0].wait(30)
+            seen["b0"] = msg()  # A has failed, B has not
+            w, out = (C.c_double * 2)(1.0, 2.0), (C.c_double * 2)()
+            rc = lib.kpop_metric_compute(1, w, 2, -1.0, 1.0, 2.0, out)  # Negative_power, lib/Space.ml:124: pure host arithmetic
+            seen["b_rc"], seen["b1"] = rc, msg()
+            turn[1].set()
+            assert turn[2].wait(30)
+            seen["b2"] = msg()  # ... after A's second failure
+            turn[3].set()
+        except BaseException as e:  # noqa: BLE001
+            errors.append(e)
+            for t in turn:
+                t.set()
+
+    threads = [threading.Thread(target=thread_a), threading.Thread(target=thread_b)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join(60)
+        assert not t.is_alive(), "a thread did not finish"
+    if errors:
+        raise errors[0]
+    assert seen["a0"] == "" and seen["b0"] == ""  # a thread that has not failed has no message, whatever the others did
+    assert seen["a_rc"] == -5 and "kpop_init" in seen["a1"]  # KPOP_ERR_NOT_INIT
+    assert seen["b_rc"] == -1 and "negative power" in seen["b1"]  # KPOP_ERR_INVALID
+    assert seen["a2"] == seen["a1"] and seen["b2"] == seen["b1"]  # each its own, unchanged by the other's later failure
+    assert seen["a_rc2"] == -5 and seen["a3"] == seen["a1"]
+    assert lib.kpop_last_error().decode() == ""  # the main thread never failed
+
+
+def test_last_error_is_per_thread():
+    """kpop_last_error() is thread-local (include/kpop_hip.h, conventions): one thread takes KPOP_ERR_NOT_INIT from a device entry
+    point, another the "negative power" failure of kpop_metric_compute (host arithmetic, lib/Space.ml:124); each reads its own
+    message, before and after the other's later failure.  In a fresh process: no kpop_init has happened there, GPU or not."""
+    import subprocess
+    import sys
+    code = "import sys; sys.path[:0] = [%r, %r]; import test_abi; test_abi._last_error_is_per_thread()" % (os.path.join(ROOT, "tests"), ROOT)
+    flags = ["-s"] if sys.flags.no_user_site else []
+    r = subprocess.run([sys.executable] + flags + ["-c", code], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+
+
 def test_parse_distance():
     import kpop_amd
     assert kpop_amd.parse_distance("euclidean") == (kpop_amd.EUCLIDEAN, 2.0)
