@@ -633,8 +633,33 @@ int kpop_counter_combine(const int32_t *const *columns, uint64_t n_rows, const u
 int kpop_counter_transform(const int32_t *const *columns, uint32_t n_cols, uint64_t n_rows, int which,
                            double threshold, double power, const double *col_stats, int kmer_major, double *out);
 
+/* Replaces distill_kmers, lib/KMerDB.ml:812-976 (KPopCountDB -d): ranks the k-mers by how well they separate the
+ * classes of the spectra.  classes[c] in [0, n_classes) is the class of column c.  For every k-mer, the absolute
+ * differences of the normalised counts (count / linear column sum) of all pairs of spectra are binned by pair of
+ * classes; mean, sample variance and coefficient of variation per bin; mean and median of each over the diagonal
+ * ("Inner") and the off-diagonal ("Outer") bins; a straight line Outer ~ Inner over all k-mers per (quantity, mean |
+ * median) and its residuals.  out is [KPOP_DISTILL_ROWS][n_rows] in the reference's row order (:960-965:
+ * Inner/Outer/Residual x AvgMean, AvgMedian, VarMean, VarMedian, COVMean, COVMedian); fits (may be NULL) receives
+ * {intercept, slope} of the six lines in that order.  The semantics are spelled out in INTEGRATION.md ("distill").
+ * The same bits on every run.  KPOP_ERR_INVALID: a class index >= n_classes, an empty class, n_classes == 1 or
+ * == n_cols ("Invalid_number_of_classes", :822-823).                                                             */
+#define KPOP_DISTILL_ROWS 18
+int kpop_counter_distill(const int32_t *const *columns, uint32_t n_cols, uint64_t n_rows, const uint32_t *classes,
+                         uint32_t n_classes, double *out, double *fits);
+
 /* device-resident forms: storage is [n_cols][ld] int32 with ld = kpop_dev_counter_ld(n_rows) */
 uint64_t kpop_dev_counter_ld(uint64_t n_rows);
+/* d_classes is on the device, fits_host (may be NULL) on the host; the k-mers go through in bands of what
+   d_workspace (kpop_dev_counter_distill_workspace_bytes) holds, or of kpop_tune("distill_band", n) k-mers if that
+   is fewer: the same bits either way.  Runs on `stream` and returns when it has finished (the fits come back to
+   the host).                                                                                                     */
+uint64_t kpop_dev_counter_distill_workspace_bytes(uint32_t n_cols, uint64_t n_rows, uint32_t n_classes);
+int kpop_dev_counter_distill(const int32_t *d_storage, uint64_t ld, uint32_t n_cols, uint64_t n_rows,
+                             const uint32_t *d_classes, uint32_t n_classes, void *d_workspace, double *d_out,
+                             double *fits_host, void *stream);
+/* development: under kpop_tune("distill_clock", 1) the last distill call on this slot drained its stream after
+   every band and kept the milliseconds of its phases: out_ms[0] cells, [1] reduce, [2] fit                      */
+int kpop_debug_distill_clocks(double *out_ms);
 uint64_t kpop_dev_counter_workspace_bytes(uint32_t n_cols, uint64_t n_rows);
 int kpop_dev_counter_stats(const int32_t *d_storage, uint64_t ld, uint32_t n_cols, uint64_t n_rows,
                            double threshold, double power, void *d_workspace, double *d_col_stats,

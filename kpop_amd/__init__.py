@@ -7,14 +7,14 @@ reference's interface for that path.  Importing it does not touch the GPU;
 """
 from .api import (check, COSINE, DNA_DS, DNA_SS, PROTEIN, EUCLIDEAN, METRIC_FLAT, METRIC_POWERS, MINKOWSKI, KPopError,  # noqa: F401
                   Twister, ca, count_reads, device_count, distance_rowwise, distance_summary, embeddings, init, summarize_distances,
-                  metric_compute, parse_distance, splits_gaps, counter_stats, counter_combine, counter_transform, COMBINE_MEAN,
+                  metric_compute, parse_distance, splits_gaps, counter_stats, counter_combine, counter_transform, counter_distill, DISTILL_ROW_NAMES, COMBINE_MEAN,
                   COMBINE_MEDIAN, TRANSF_BINARY, TRANSF_POWER, TRANSF_CLR, TRANSF_PSEUDO, Pipeline, host_empty, init_devices, use_device,
                   device_slots, OUT_TWISTED, OUT_DISTANCES, OUT_SUMMARY, Sharded, shard_bounds, sharded_distance_rowwise,
                   sharded_distance_summary, RefSet, dev_refset_workspace_bytes, dev_refset_distance_rowwise, dev_refset_distance_summary)
 
 __all__ = ["init", "device_count", "count_reads", "Twister", "ca", "metric_compute", "distance_rowwise",
            "distance_summary", "embeddings", "splits_gaps", "summarize_distances", "parse_distance", "KPopError", "DNA_DS", "DNA_SS", "PROTEIN", "EUCLIDEAN", "COSINE",
-           "MINKOWSKI", "METRIC_FLAT", "METRIC_POWERS", "counter_stats", "counter_combine", "counter_transform",
+           "MINKOWSKI", "METRIC_FLAT", "METRIC_POWERS", "counter_stats", "counter_combine", "counter_transform", "counter_distill", "DISTILL_ROW_NAMES",
            "COMBINE_MEAN", "COMBINE_MEDIAN", "TRANSF_BINARY", "TRANSF_POWER", "TRANSF_CLR", "TRANSF_PSEUDO", "Pipeline", "host_empty",
            "init_devices", "use_device", "device_slots", "OUT_TWISTED", "OUT_DISTANCES", "OUT_SUMMARY", "Sharded", "shard_bounds",
            "sharded_distance_rowwise", "sharded_distance_summary", "RefSet", "dev_refset_workspace_bytes",

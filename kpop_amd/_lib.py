@@ -115,6 +115,10 @@ SIGNATURES = {
     "kpop_counter_combine": (C.c_int, [C.POINTER(vp), C.c_uint64, u32p, C.c_uint32, f64p, C.c_int, vp, f64p]),
     "kpop_counter_transform": (C.c_int, [C.POINTER(vp), C.c_uint32, C.c_uint64, C.c_int, C.c_double, C.c_double, f64p,
                                          C.c_int, f64p]),
+    "kpop_counter_distill": (C.c_int, [C.POINTER(vp), C.c_uint32, C.c_uint64, u32p, C.c_uint32, f64p, f64p]),
+    "kpop_dev_counter_distill_workspace_bytes": (C.c_uint64, [C.c_uint32, C.c_uint64, C.c_uint32]),
+    "kpop_dev_counter_distill": (C.c_int, [vp, C.c_uint64, C.c_uint32, C.c_uint64, vp, C.c_uint32, vp, vp, f64p, vp]),
+    "kpop_debug_distill_clocks": (C.c_int, [f64p]),
     "kpop_dev_counter_ld": (C.c_uint64, [C.c_uint64]),
     "kpop_dev_counter_workspace_bytes": (C.c_uint64, [C.c_uint32, C.c_uint64]),
     "kpop_dev_counter_stats": (C.c_int, [vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_double, C.c_double, vp, vp, vp, vp]),

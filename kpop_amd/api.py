@@ -635,6 +635,28 @@ def counter_transform(columns, col_stats, which=TRANSF_POWER, threshold=1.0, pow
     return out
 
 
+# rows of counter_distill's result, in the reference's order (lib/KMerDB.ml:960-965)
+DISTILL_ROW_NAMES = tuple("%s%s%s" % (part, quantity, across) for quantity in ("Avg", "Var", "COV")
+                          for across in ("Mean", "Median") for part in ("Inner", "Outer", "Residual"))
+
+
+def counter_distill(columns, classes, n_classes=None):
+    """distill_kmers (lib/KMerDB.ml:812-976; semantics declared in INTEGRATION.md) -> (out [18, n_rows] in the order of
+    DISTILL_ROW_NAMES, fits [6, 2]: intercept and slope of the lines behind the six Residual rows).  classes[c] is the
+    class index of spectrum c; n_classes defaults to max(classes) + 1."""
+    cols, ptrs, n_rows = _columns(columns)
+    classes = _c(classes, np.uint32)
+    if classes.ndim != 1 or classes.size != len(cols):
+        raise ValueError("one class index per spectrum")
+    if n_classes is None:
+        n_classes = int(classes.max()) + 1 if classes.size else 0
+    out = np.zeros((len(DISTILL_ROW_NAMES), n_rows), dtype=np.float64)
+    fits = np.zeros((6, 2), dtype=np.float64)
+    check(_lib.load().kpop_counter_distill(ptrs, len(cols), n_rows, _p(_nz(classes, np.uint32), C.c_uint32), int(n_classes),
+                                           _p(_nz(out, np.float64), C.c_double), _p(fits, C.c_double)))
+    return out, fits
+
+
 # ----------------------------------------------------------------- metric
 def metric_compute(inertia, kind=METRIC_POWERS, power_int=1.0, threshold=1.0, power_ext=2.0):
     """Default = powers(1,1,2), bin/KPopTwistDB.ml:92."""

@@ -137,6 +137,9 @@ struct Context {
   int tune_summary_audit = 0;  // 1: count the rows the large-reference summaries leave to their exact fall-back (kpop_debug_summary_fallbacks reads and clears)
   uint64_t summary_fallback_rows = 0;
   int tune_summary2 = 1; // summaries against > 4,096 rows: 1 brackets and bands from a sample + ONE pass over distance rows, 3 the same in two passes (median, then MAD), 0 round 2's one block per row (8-10 passes), 2 the distances computed and reduced in one kernel, no distance rows (131,072 rows and more); 1, 2 and 3 are level at 256 x 1M
+  int tune_distill_band = 0;  // k-mers a band of kpop_dev_counter_distill at most (0: what the workspace holds); same results
+  int tune_distill_clock = 0; // 1: distill drains its stream after every band and keeps the time of its three phases (kpop_debug_distill_clocks)
+  double distill_ms[3] = {0., 0., 0.};
   int tune_histlds = 1;  // ... staged through LDS: private tables (k <= 7), sorted chunks of assemblies (0: direct atomics; 2: always sort the chunks)
 };
 constexpr int kMaxSlots = 16;
@@ -224,6 +227,9 @@ struct DevBuf {
     return reinterpret_cast<T *>(p);
   }
 };
+
+// host columns of a k-mer database -> device [n_cols][ld], ld = kpop_dev_counter_ld(n_rows) (counter.hip)
+int upload_columns(const int32_t *const *columns, uint32_t n_cols, uint64_t n_rows, DevBuf &d, uint64_t *ld_out, hipStream_t st);
 
 constexpr int kWave = 64;  // gfx950 wavefront
 

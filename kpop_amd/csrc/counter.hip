@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "common.h"
+#include "wave_select.h"
 #include "wave_sort.h"
 
 namespace kpop {
@@ -356,48 +357,6 @@ __device__ __forceinline__ double ordered_value(uint64_t k) {
   return __longlong_as_double((long long)b);
 }
 
-// The element of rank `target` (0-based, ascending) among the wave's 64*R values, without sorting them: quickselect on
-// wave ballots.  The values strictly between `lo` and `hi` are still candidates; the first candidate in (register, lane)
-// order is the pivot (the registers are looked at until one holds a candidate); two comparisons per register count the
-// values below the pivot and those not above it -- over all the values, so the bounds need not be applied -- and one of
-// the bounds moves.  Every step is wave-uniform (no divergence, no LDS, no cross-lane data movement but one readlane);
-// ties and the zeros that dominate sparse spectra finish in a step.  Expected ~2 ln(m) steps of ~2R comparisons against
-// the ~R log^2(64R) compare-exchanges plus cross-lane shuffles of a full sort.
-// The values are compared as the doubles they are (f64 comparisons issue at the full rate, 64-bit integer ones on
-// order-preserving keys do not): there is no NaN among them -- the norms are positive and finite -- and +inf is the
-// padding of the empty slots, never a candidate (hi starts there).
-template <int R>
-__device__ __forceinline__ double wave_select_rank(const double (&v)[R], uint32_t target) {
-  double lo = -INFINITY, hi = INFINITY;
-  for (;;) {
-    double pivot = 0.;
-    bool found = false;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      if (!found) {
-        const uint64_t alive = __ballot(v[r] > lo && v[r] < hi);
-        if (alive) {
-          const int src = __builtin_amdgcn_readfirstlane(__ffsll((long long)alive) - 1);  // (uniform already: v_readlane, not a trip through LDS)
-          const uint64_t bits = (uint64_t)__double_as_longlong(v[r]);
-          pivot = __longlong_as_double((long long)(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(bits >> 32), src) << 32) |
-                                                   (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)bits, src)));
-          found = true;
-        }
-      }
-    }
-    if (!found) return lo;  // cannot happen for target < number of values
-    uint32_t n_lt = 0, n_le = 0;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      n_lt += (uint32_t)__popcll(__ballot(v[r] < pivot));
-      n_le += (uint32_t)__popcll(__ballot(v[r] <= pivot));
-    }
-    if (target < n_lt) hi = pivot;
-    else if (target < n_le) return pivot;
-    else lo = pivot;
-  }
-}
-
 // RescaledMedian, 65 .. 64*R spectra: one wavefront per k-mer.  A tile of TR k-mers x m spectra of raw counts is staged in
 // LDS; each wave then takes a k-mer, rescales its m counts into registers (R per lane; which lane holds which spectrum
 // does not matter to a sort), finds the value of rank m/2 among the 64*R (empty slots carry +inf) with
@@ -703,7 +662,9 @@ int check_transform(int which, double threshold, double power, const char *who) 
   return 0;
 }
 
-// host columns -> device [n_cols][ld]
+}  // namespace
+
+// host columns -> device [n_cols][ld] (distill.hip uploads with it too)
 int upload_columns(const int32_t *const *columns, uint32_t n_cols, uint64_t n_rows, DevBuf &d, uint64_t *ld_out, hipStream_t st) {
   const uint64_t ld = kpop_dev_counter_ld(n_rows);
   KPOP_TRY(d.alloc((uint64_t)n_cols * ld * 4));
@@ -714,8 +675,6 @@ int upload_columns(const int32_t *const *columns, uint32_t n_cols, uint64_t n_ro
   *ld_out = ld;
   return 0;
 }
-
-}  // namespace
 
 }  // namespace kpop
 

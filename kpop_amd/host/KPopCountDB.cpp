@@ -3,10 +3,11 @@
 //
 // Same registers (database + selection), same actions executed in order of specification
 // (bin/KPopCountDB.ml:94-330,357-436), same file naming and text formats (lib/KMerDB.ml).  Every loop over all
-// counts runs in libkpop_hip.so: statistics, mean/median combination, transformations, distances.
+// counts runs in libkpop_hip.so: statistics, mean/median combination, distillation, transformations, distances.
 //
 // Differences from the reference, on purpose:
-//   * -d/--distill is refused: it leans on BiOCamLib's OnlineStats/LinearFit, which are not part of the checkout;
+//   * -d/--distill follows the semantics declared in INTEGRATION.md ("distill"): BiOCamLib's OnlineStats/LinearFit, which
+//     the reference leans on, are not part of the checkout;
 //   * -T is accepted and ignored (the GPU is the parallelism);
 //   * a runtime failure exits with status 1 (the reference prints the exception and exits 0);
 //   * regular expressions are translated from OCaml Str syntax to ECMAScript (std::regex).
@@ -40,6 +41,8 @@ void usage(FILE *f) {
           " -k|--kmers|--add-kmers|--add-kmer-files <prefix>[,...]   add spectra from <prefix>.KPopSpectra.txt\n"
           " --combination-criterion|--spectrum-combination-criterion mean|median   (default mean)\n"
           " -c|--combine|--combine-by-class|--combine-spectra-by-class <metadata_field>\n"
+          " -d|--distill|--distill-kmers <metadata_field> <prefix>   rank k-mers by how well they separate the classes;\n"
+          "                                          writes <prefix>.KPopDistill.txt\n"
           " --summary                                print a summary of the database\n"
           " -o|--output <prefix>                     save <prefix>.KPopCounter\n"
           " --distance|--distance-function euclidean|cosine|minkowski(<p>)   (default euclidean)\n"
@@ -167,9 +170,8 @@ int main(int argc, char **argv) {
       const std::string p = need(i, a);
       program.push_back([p](State &s) { s.db.split_spectra(p, s.criterion); });
     } else if (is({"-d", "--distill", "--distill-kmers"})) {
-      need(i, a);
-      need(i, a);
-      program.push_back([](State &) { throw Error("-d/--distill is not supported by the HIP build (see the head of KPopCountDB.cpp)"); });
+      const std::string label = need(i, a), p = need(i, a);
+      program.push_back([label, p](State &s) { s.db.distill(label, p); });
     } else if (is({"--summary"})) program.push_back([](State &s) { s.db.output_summary(); });
     else if (is({"-o", "--output"})) {
       const std::string p = need(i, a);

@@ -583,6 +583,54 @@ void CounterDB::split_spectra(const std::string &classes_label, int criterion) {
   remove_selected(originals);
 }
 
+void CounterDB::distill(const std::string &classes_label, const std::string &prefix) {
+  // (a register without spectra has no metadata either: the reference's exception, and what it means here)
+  if (n_cols() == 0) throw Error("Classes_label_not_found(\"" + classes_label + "\"): distilling an empty database is not supported");
+  auto mi = meta_idx_.find(classes_label);
+  if (mi == meta_idx_.end()) throw Error("Classes_label_not_found(\"" + classes_label + "\")");  // :740-741
+  // get_indicator_vector (:742-764), as in split_spectra: classes numbered in order of first appearance
+  std::map<std::string, uint32_t> class_to_ind;
+  std::vector<uint32_t> classes(n_cols());
+  for (size_t c = 0; c < n_cols(); ++c) {
+    const std::string &cl = core.meta[c][mi->second];
+    auto it = class_to_ind.find(cl);
+    if (it == class_to_ind.end()) it = class_to_ind.emplace(cl, (uint32_t)class_to_ind.size()).first;
+    classes[c] = it->second;
+  }
+  const uint32_t n_classes = (uint32_t)class_to_ind.size();
+  if (n_classes == 1 || n_classes == n_cols()) throw Error("Invalid_number_of_classes(" + std::to_string(n_classes) + ")");  // :822-823
+  if (verbose) {
+    fprintf(stderr, "(KPopCountDB): Classes=[");
+    for (uint32_t c : classes) fprintf(stderr, " %u", c);
+    fprintf(stderr, " ]\n");
+  }
+  ensure_gpu();
+  std::vector<const int32_t *> all = columns();
+  const size_t nr = n_rows();
+  std::vector<double> rows((size_t)KPOP_DISTILL_ROWS * std::max<size_t>(1, nr));
+  double fits[12];
+  check(kpop_counter_distill(all.data(), (uint32_t)all.size(), nr, classes.data(), n_classes, rows.data(), fits));
+  static const char *const quantity[3] = {"Avg", "Var", "COV"}, *const across[2] = {"Mean", "Median"},
+                           *const part[3] = {"Inner", "Outer", "Residual"}, *const fit_name[3] = {"avgs", "vars", "covs"};
+  if (verbose) {
+    fprintf(stderr, "(KPopCountDB): Distilled %zu/%zu kmers.\n", nr, nr);
+    for (int f = 0; f < 6; ++f)  // :935-952
+      fprintf(stderr, "(KPopCountDB): Fit for %s %s is %.6g + %.6g * x\n", fit_name[f / 2], f % 2 ? "median" : "mean", fits[2 * f], fits[2 * f + 1]);
+  }
+  // Matrix.transpose, then Matrix.to_file (:976): one line per k-mer
+  Table t;
+  for (int q = 0; q < 3; ++q)
+    for (int m = 0; m < 2; ++m)
+      for (int p = 0; p < 3; ++p) t.col_names.push_back(std::string(part[p]) + quantity[q] + across[m]);
+  t.row_names = core.row_names;
+  t.data.resize(nr * KPOP_DISTILL_ROWS);
+  parallel_for(nr, 1 << 16, [&](size_t lo, size_t hi) {
+    for (size_t r = lo; r < hi; ++r)
+      for (size_t k = 0; k < KPOP_DISTILL_ROWS; ++k) t.data[r * KPOP_DISTILL_ROWS + k] = rows[k * nr + r];
+  });
+  write_table(make_filename(prefix, "KPopDistill", true), t, 15);
+}
+
 void CounterDB::output_summary() const {
   fprintf(stderr, "[Spectrum labels (%zu)]:", n_cols());
   for (const std::string &s : core.col_names) fprintf(stderr, " '%s'", s.c_str());

@@ -1,7 +1,7 @@
 // counter_db.h -- the k-mer database register of KPopCountDB (lib/KMerDB.ml), host side.
 //
 // Name tables, metadata, selection logic and text output live here; every loop that touches all counts
-// (statistics, class combination, table transformations, spectral distances) is a call into libkpop_hip.so
+// (statistics, class combination, distillation, table transformations, spectral distances) is a call into libkpop_hip.so
 // (kpop_counter_*, kpop_distance_rowwise).  file:line citations are into the reference checkout.
 #pragma once
 #include <stdint.h>
@@ -57,6 +57,7 @@ class CounterDB {
   void add_combined_selected(const std::string &new_label, const std::set<std::string> &selection, int criterion);  // :639-736
   void split_spectra(const std::string &classes_label, int criterion);   // :787-813
   void remove_selected(const std::set<std::string> &selected);           // :766-785
+  void distill(const std::string &classes_label, const std::string &prefix);  // :816-976; writes <prefix>.KPopDistill.txt
   void output_summary() const;                                           // :241-266
   void to_table(const TableFilter &filter, const std::string &prefix);   // :1012-1169
   void to_spectra(const TableFilter &filter, const std::string &prefix); // :1170-1236
