@@ -144,6 +144,10 @@ int kpop_synchronize(void *stream);
    rows (a database laid out lineage by lineage makes those runs speak for a few lineages: the brackets miss, the rows take the slow kernel);
    "summary_rawref" 1 (default) | 0: such a summary takes its reference set as it is (no normalised copy of it is made: the norms' pass keeps the
    rows' sums of squares, dot products are scaled where they come out, the exact chains divide as they go -- the same bits), or makes the copy;
+   "class_set" 1 (default) | 0 | 2: kpop_dev_distance_rowwise (and _norms, and a resident set's) against a set of classes -- a first operand of
+   fewer than 128 rows of at most 64 dimensions, euclidean or cosine, a workspace given -- through the kernel that holds a row of the second
+   operand in a lane's registers and takes the class values as scalar operands (class_set.hip), from 128 rows of the second operand on; 0: never
+   (the tiled kernel: the same bits); 2: every eligible shape whatever its number of rows;
    "summary_pass" 1 (default) | 0: the pass over such a summary's approximate rows written for rows the library made itself, or the general one;
    "tilepipe" 1 (default) | 0: the tile route's kernel with producer and consumer wavefronts (tile_pipe.h; beyond 64 dimensions its three-stage
    form: producers / MFMA wavefronts / gather wavefronts), or round 4's; "tilewide" 0 (default) | 1: that three-stage form at any number of

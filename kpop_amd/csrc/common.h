@@ -127,6 +127,7 @@ struct Context {
   int tune_hist = 1;     // merged (-l) spectrum by atomic histogram when the hashes fit 26 bits (0: always sort)
   int tune_histguess = 1; // the merged count's partition path sizes its buckets from a sample of the items (one in 32) instead of a counting pass over all of them; a bucket that overflows sends the call back to the exact count.  0: always the exact count
   int tune_direct = 2; // a nearly complete twister of k 13..15 and <= 32 dimensions also keeps its rows at their hashes (twister.h): 2 by that rule, 1 whenever the table fits (any k <= 15), 0 never.  Read when a twister is loaded or synthesised
+  int tune_class_set = 1; // kpop_dev_distance_rowwise against a class set (fewer than 128 rows of at most 64 dimensions, euclidean / cosine): class_set.hip's kernel, a row a lane and the class values as scalar operands, from 128 rows of the second operand on; 0: never (distance_rowwise_kernel, the same bits), 2: every eligible shape whatever its rows (tests)
   int tune_summary_mfma_lists = 1; // the refinement reads the summary's candidate lists where its bands lie inside them; 0: it scans every distance row again
   int tune_distance_mfma = 1; // kpop_dev_distance_rowwise of 2^32 products and more (rows x rows x dimensions), euclidean / cosine: the contraction on the f64 matrix cores, pairs that cancel recomputed with the reference's chain (<= 1e-12 relative, not bit for bit); 0: the vector-pipe chain for every pair (the reference's bits)
   int tune_summary_mfma = 1; // (1, the default: approximate rows, then the summary's pass over them; 2: up to 128 dimensions the pass runs INSIDE the contraction and no approximate row is written -- same results, measured SLOWER: 256 x 1M x 64 2.9-3.2 against 2.7-2.8 ms, the classification's ~50 vector operations a pair serialise with the matrix pipe on a SIMD: profiles/r06_summary_select.txt) summaries against >= 65,536 rows, euclidean / cosine: the distances as f64 MFMAs + exact refinement (distance_mfma.hip); 0: the vector-pipe chain for every pair

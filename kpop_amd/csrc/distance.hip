@@ -4,6 +4,8 @@
 //                            Space.compute_norm        lib/Space.ml:166-181
 //   distance_rowwise_kernel  Base.get_distance_rowwise lib/Matrix.ml:191-266
 //                            Space.Distance.compute    lib/Space.ml:182-205
+//                            (many rows against a set of classes -- fewer than 128 rows of at most 64 dimensions, euclidean / cosine --
+//                            go through class_set.hip's kernel instead: the same operations, the same bits; rowwise_impl dispatches)
 //   distance_summary_kernel  summarize_rowwise / summarize_distance_matrix_row
 //                                                      lib/Matrix.ml:691-766,632-690
 //
@@ -1205,6 +1207,11 @@ bool distance_mfma_applies(int kind, uint32_t r1, uint32_t r2, uint32_t n_dims);
 int launch_distance_rowwise_mfma(int kind, const double *a, uint32_t r1, const double *b, uint32_t r2, uint32_t n_dims, const double *metric, double p, double *out,
                                  hipStream_t st, const double *n1, const double *n2, const double *s1, const double *s2);
 
+// class_set.hip: many rows against a small set of classes, a row a lane
+bool class_set_applies(int kind, uint32_t r1, uint32_t r2, uint32_t n_dims, uint64_t room_doubles);
+int launch_class_set_distance(int kind, const double *m1, uint32_t r1, const double *norms1, double *n1_out, const double *m2, uint32_t r2, double *n2,
+                              uint32_t n_dims, const double *metric, double p, bool divide, double *room, double *out, hipStream_t st);
+
 template <int KIND>
 static int rowwise_impl(const double *m1, uint32_t r1, const double *m2, uint32_t r2, uint32_t n_dims,
                         const double *metric, double p, int normalize, void *work, double *out, hipStream_t st,
@@ -1244,6 +1251,19 @@ static int rowwise_impl(const double *m1, uint32_t r1, const double *m2, uint32_
     reduce_slabs_kernel<KIND><<<dim3(div_up(pairs, 256)), dim3(256), 0, st>>>(partial, pairs, slabs, p, out);
     KPOP_LAUNCH_CHECK();
     return 0;
+  }
+  // A set of classes (fewer than 128 rows of at most 64 dimensions, euclidean / cosine) against many rows: class_set.hip -- a row a
+  // lane, the class values as scalar operands, the rows' norms and divisions inside the one kernel.  The same operations in the same
+  // order as the routes below (the same bits); the padded classes and metric borrow the room of the second operand's copy.
+  // kpop_tune("class_set", 0): never.  (What the matrix cores take today -- no normalisation, 2^32 products and more -- stays theirs.)
+  {
+    // (the room of the operands' copies, DistWork::a and ::b, which this path does not otherwise use; a set's workspace has ::b alone)
+    const uint64_t room = work ? ((uint64_t)r2 + (prep ? 0u : r1)) * n_dims : 0;
+    if (class_set_applies(KIND, r1, r2, n_dims, room) && !(!normalize && distance_mfma_applies(KIND, r1, r2, n_dims))) {
+      DistWork w = carve(work, r1, r2, n_dims, prep);
+      if (prep && normalize) norms1 = prep->n1;
+      return launch_class_set_distance(KIND, m1, r1, norms1, prep ? nullptr : w.n1, m2, r2, w.n2, n_dims, metric, p, normalize != 0, prep ? w.b : w.a, out, st);
+    }
   }
   // One column tile (r1 < 128: distances to a set of classes): every row is divided about once either way, and dividing while
   // staging saves writing and re-reading a copy of both operands -- 0.144 -> 0.132 ms at 65 x 100,000 x 64, 0.031 -> 0.023 ms at
