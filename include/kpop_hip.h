@@ -605,6 +605,35 @@ int kpop_dev_refset_distance_summary(kpop_refset *rs, const double *d_m2, uint32
                                      uint32_t max_neighbours, void *d_work, double *d_out_stats, uint32_t *d_out_n,
                                      uint32_t *d_out_idx, double *d_out_dist, double *d_out_z, void *stream);
 
+/* ------------------------------------------------- neighbours within a distance (range queries on a resident set)
+ * Every row of the set within max_distance of a query row: H_j = { i < r1 : d(j, i) <= max_distance }, where d is the
+ * reference chain's distance (lib/Space.ml:182-205 with the adaptors of lib/Matrix.ml:243-250) -- the bits
+ * kpop_refset_distance_rowwise writes under kpop_tune("distance_mfma", 0) -- whatever kpop_tune says.  A row's list is in
+ * ascending (distance, index) order with -0 as +0: the multimap order of summarize_distance_matrix_row
+ * (lib/Matrix.ml:632-690, the order :641-650), cut at a distance where the summary cuts at a count; the reference's
+ * Space.Distance.Iterator (lib/Space.ml:231-487) bounds its pairs by a max_distance_component in the same way.  A NaN
+ * distance is never a hit; max_distance may be +inf, a negative one gives empty lists, NaN is KPOP_ERR_INVALID.
+ * CSR layout: out_offsets[r2 + 1] (out_offsets[0] = 0), out_idx[] and out_dist[] of out_offsets[r2] entries.  The same
+ * bits on every run.  out_offsets is always complete and exact; r1 = 0 and r2 = 0 give all-zero offsets.  The r2 x r1
+ * matrix is never formed.  The set's limits, slot and thread ownership hold as for every call on a set.               */
+/* (lib/Matrix.ml:632-690 cut at a distance; lib/Space.ml:182-205.)  out_offsets[r2] > capacity: KPOP_ERR_CAPACITY, out_idx
+   and out_dist untouched.  out_idx == out_dist == NULL: count only, KPOP_OK.  Synchronises.                           */
+int kpop_neighbours_within(kpop_refset *rs, const double *m2, uint32_t r2, double max_distance, uint64_t capacity,
+                           uint64_t *out_offsets, uint32_t *out_idx, double *out_dist);
+/* bytes of d_work for kpop_dev_neighbours_within (the lists of lib/Matrix.ml:632-690 cut at a distance, see the block above): the
+   query side and 32 bytes a list entry of `capacity`; does not grow with the set                                     */
+uint64_t kpop_dev_neighbours_within_workspace_bytes(const kpop_refset *rs, uint32_t r2, uint64_t capacity);
+/* (lib/Matrix.ml:632-690 cut at a distance; lib/Space.ml:182-205.)  Enqueues only.  The lists are written only when they
+   fit `capacity`: the caller reads d_out_offsets[r2].  NULL lists: count only.                                        */
+int kpop_dev_neighbours_within(kpop_refset *rs, const double *d_m2, uint32_t r2, double max_distance, uint64_t capacity,
+                               void *d_work, uint64_t *d_out_offsets, uint32_t *d_out_idx, double *d_out_dist,
+                               void *stream);
+/* unprepared convenience (lib/Matrix.ml:191-266 for the distances, :632-690 for the order): a temporary set over m1, then
+   kpop_neighbours_within                                                                                              */
+int kpop_distance_within(const double *m1, uint32_t r1, const double *m2, uint32_t r2, uint32_t n_dims,
+                         const double *metric, int kind, double p, int normalize, double max_distance,
+                         uint64_t capacity, uint64_t *out_offsets, uint32_t *out_idx, double *out_dist);
+
 /* ------------------------------------------------- k-mer database (KPopCountDB)
  * the operations of lib/KMerDB.ml that touch every count.  A database is the reference's
  * `storage: I32BAVector.t array` (lib/KMerDB.ml:54-63): n_cols spectra ("columns"), each a vector of n_rows int32

@@ -10,7 +10,8 @@ from .api import (check, COSINE, DNA_DS, DNA_SS, PROTEIN, EUCLIDEAN, METRIC_FLAT
                   metric_compute, parse_distance, splits_gaps, counter_stats, counter_combine, counter_transform, counter_distill, DISTILL_ROW_NAMES, COMBINE_MEAN,
                   COMBINE_MEDIAN, TRANSF_BINARY, TRANSF_POWER, TRANSF_CLR, TRANSF_PSEUDO, Pipeline, host_empty, init_devices, use_device,
                   device_slots, OUT_TWISTED, OUT_DISTANCES, OUT_SUMMARY, Sharded, shard_bounds, sharded_distance_rowwise,
-                  sharded_distance_summary, RefSet, dev_refset_workspace_bytes, dev_refset_distance_rowwise, dev_refset_distance_summary)
+                  sharded_distance_summary, RefSet, dev_refset_workspace_bytes, dev_refset_distance_rowwise, dev_refset_distance_summary,
+                  dev_neighbours_within_workspace_bytes, dev_neighbours_within, distance_within)
 
 __all__ = ["init", "device_count", "count_reads", "Twister", "ca", "metric_compute", "distance_rowwise",
            "distance_summary", "embeddings", "splits_gaps", "summarize_distances", "parse_distance", "KPopError", "DNA_DS", "DNA_SS", "PROTEIN", "EUCLIDEAN", "COSINE",
@@ -18,4 +19,5 @@ __all__ = ["init", "device_count", "count_reads", "Twister", "ca", "metric_compu
            "COMBINE_MEAN", "COMBINE_MEDIAN", "TRANSF_BINARY", "TRANSF_POWER", "TRANSF_CLR", "TRANSF_PSEUDO", "Pipeline", "host_empty",
            "init_devices", "use_device", "device_slots", "OUT_TWISTED", "OUT_DISTANCES", "OUT_SUMMARY", "Sharded", "shard_bounds",
            "sharded_distance_rowwise", "sharded_distance_summary", "RefSet", "dev_refset_workspace_bytes",
-           "dev_refset_distance_rowwise", "dev_refset_distance_summary"]
+           "dev_refset_distance_rowwise", "dev_refset_distance_summary", "dev_neighbours_within_workspace_bytes",
+           "dev_neighbours_within", "distance_within"]

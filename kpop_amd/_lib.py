@@ -162,6 +162,11 @@ SIGNATURES = {
     "kpop_dev_refset_workspace_bytes": (C.c_uint64, [vp, C.c_uint32]),
     "kpop_dev_refset_distance_rowwise": (C.c_int, [vp, vp, C.c_uint32, vp, vp, vp]),
     "kpop_dev_refset_distance_summary": (C.c_int, [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp]),
+    "kpop_neighbours_within": (C.c_int, [vp, f64p, C.c_uint32, C.c_double, C.c_uint64, u64p, u32p, f64p]),
+    "kpop_dev_neighbours_within_workspace_bytes": (C.c_uint64, [vp, C.c_uint32, C.c_uint64]),
+    "kpop_dev_neighbours_within": (C.c_int, [vp, vp, C.c_uint32, C.c_double, C.c_uint64, vp, vp, vp, vp, vp]),
+    "kpop_distance_within": (C.c_int, [f64p, C.c_uint32, f64p, C.c_uint32, C.c_uint32, f64p, C.c_int, C.c_double, C.c_int, C.c_double, C.c_uint64,
+                                       u64p, u32p, f64p]),
 }
 
 

@@ -791,6 +791,31 @@ class RefSet:
                                                        _p(_nz(z, np.float64), C.c_double)))
         return stats, n, idx, dist, z
 
+    def within(self, m2, max_distance, capacity=None):
+        """Every row of the set within max_distance of each row of m2 -> (offsets[r2 + 1] u64, idx u32, dist f64), CSR; a row's list
+        ascending by (distance, index): the neighbour list of distance_summary (lib/Matrix.ml:632-690) cut at a distance instead of a
+        count.  capacity=None: one call counts, a second fills arrays of exactly that size; a capacity that turns out too small raises
+        KPopError with code ERR_CAPACITY (kpop_neighbours_within, include/kpop_hip.h)."""
+        m2 = _c(m2, np.float64)
+        i = self.info()
+        if m2.ndim != 2 or m2.shape[1] != i["n_dims"]:
+            raise ValueError("Incompatible_geometries")
+        r2 = m2.shape[0]
+        lib = _lib.load()
+        offsets = np.zeros(r2 + 1, dtype=np.uint64)
+        pm2, poff = _p(_nz(m2, np.float64), C.c_double), _p(offsets, C.c_uint64)
+        if capacity is None:
+            check(lib.kpop_neighbours_within(self._h, pm2, r2, float(max_distance), 0, poff, None, None))
+            capacity = int(offsets[r2])
+            if capacity == 0:  # (nothing to fill: the offsets are all there is)
+                return offsets, np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.float64)
+        capacity = int(capacity)
+        idx = np.zeros(max(capacity, 1), dtype=np.uint32)
+        dist = np.zeros(max(capacity, 1), dtype=np.float64)
+        check(lib.kpop_neighbours_within(self._h, pm2, r2, float(max_distance), capacity, poff, _p(idx, C.c_uint32), _p(dist, C.c_double)))
+        total = int(offsets[r2])
+        return offsets, idx[:total], dist[:total]
+
     def free(self):
         if self._h is not None and self._h.value:
             check(_lib.load().kpop_refset_free(self._h))
@@ -930,3 +955,36 @@ def dev_refset_distance_rowwise(rs, d_m2, r2, d_work, d_out, stream=0):
 def dev_refset_distance_summary(rs, d_m2, r2, d_work, d_stats, d_n, d_idx, d_dist, d_z, keep_at_most=2, max_neighbours=8, stream=0):
     check(_lib.load().kpop_dev_refset_distance_summary(rs.handle, d_m2, int(r2), int(keep_at_most or 0), int(max_neighbours), d_work, d_stats, d_n,
                                                        d_idx, d_dist, d_z, stream))
+
+
+def dev_neighbours_within_workspace_bytes(rs, r2, capacity):
+    """the size of d_work for r2 query rows and lists of `capacity` entries in all: it does not grow with the set"""
+    return int(_lib.load().kpop_dev_neighbours_within_workspace_bytes(rs.handle, int(r2), int(capacity)))
+
+
+def dev_neighbours_within(rs, d_m2, r2, max_distance, capacity, d_work, d_offsets, d_idx, d_dist, stream=0):
+    """enqueue only: d_offsets[r2 + 1] (u64) is always complete, d_idx (u32) / d_dist (f64) are written when d_offsets[r2] <= capacity;
+    d_idx = d_dist = None counts only"""
+    check(_lib.load().kpop_dev_neighbours_within(rs.handle, d_m2, int(r2), float(max_distance), int(capacity), d_work, d_offsets, d_idx, d_dist, stream))
+
+
+def distance_within(m1, m2, metric, max_distance, kind=EUCLIDEAN, p=2.0, normalize=True, capacity=None):
+    """RefSet(m1, ...).within(m2, max_distance) without keeping the set; with a capacity, one call of kpop_distance_within"""
+    m1, m2, metric = _c(m1, np.float64), _c(m2, np.float64), _c(metric, np.float64)
+    if capacity is None:
+        rs = RefSet(m1, metric, kind=kind, p=p, normalize=normalize)
+        try:
+            return rs.within(m2, max_distance)
+        finally:
+            rs.free()
+    if m1.ndim != 2 or m2.ndim != 2 or m1.shape[1] != len(metric) or m2.shape[1] != len(metric):
+        raise ValueError("Incompatible_geometries")  # lib/Matrix.ml:193-194
+    r2, capacity = m2.shape[0], int(capacity)
+    offsets = np.zeros(r2 + 1, dtype=np.uint64)
+    idx = np.zeros(max(capacity, 1), dtype=np.uint32)
+    dist = np.zeros(max(capacity, 1), dtype=np.float64)
+    check(_lib.load().kpop_distance_within(_p(_nz(m1, np.float64), C.c_double), m1.shape[0], _p(_nz(m2, np.float64), C.c_double), r2, len(metric),
+                                           _p(_nz(metric, np.float64), C.c_double), int(kind), float(p), 1 if normalize else 0, float(max_distance),
+                                           capacity, _p(offsets, C.c_uint64), _p(idx, C.c_uint32), _p(dist, C.c_double)))
+    total = int(offsets[r2])
+    return offsets, idx[:total], dist[:total]

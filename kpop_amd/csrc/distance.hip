@@ -79,6 +79,9 @@ constexpr int kDC = 16, kMaxW = 128, kMaxTJ = 256;
 // applies the scale.  SLAB = false is the hot path: one block walks all the dimensions, the sum is the reference's.
 // MAXTJ: the most second-operand rows a block stages (TJ <= MAXTJ).  With 128 (one column tile of 61..127 columns: distances to a
 // set of classes) and the rows' norms in LDS instead of 48 registers the kernel fits 168 VGPRs: three wavefronts a SIMD, not two.
+// TWIN: within_tile_kernel (within.hip) repeats this kernel's staging, prefetch and inner loop (the SLAB = false, undivided form) with an
+// epilogue that compares instead of storing, and within_tiles repeats rowwise_block's choice of tiles.  Its results must be this kernel's
+// bits (tests/test_gpu_within.py): a change to the order of operations here goes there as well.
 template <int KIND, bool SLAB = false, int TY = 4, int MAXTJ = 256>
 __global__ __launch_bounds__(256, MAXTJ == 128 ? 3 : 1) void distance_rowwise_kernel(const double *__restrict__ a, uint32_t w, uint32_t r1,
                                                                const double *__restrict__ b, uint32_t r2,
@@ -1844,6 +1847,14 @@ int refset_dev_summary(kpop_refset *rs, const double *d_m2, uint32_t r2, uint32_
   if (max_neighbours && (!d_out_idx || !d_out_dist || !d_out_z)) KPOP_FAIL(KPOP_ERR_INVALID, "kpop_dev_refset_distance_summary: null neighbour buffers");
   return summary_by_kind(rs->rows, rs->r1, d_m2, r2, rs->n_dims, rs->metric, rs->kind, rs->p, rs->normalize, keep_at_most, max_neighbours, d_work, d_out_stats,
                          d_out_n, d_out_idx, d_out_dist, d_out_z, st, rs);
+}
+// the query rows' norms and divided copy, as prepare_operands makes them against a set (within.hip)
+int refset_query_norms(const kpop_refset *rs, const double *d_m2, uint32_t r2, double *n2, double *b_div, hipStream_t st) {
+  switch (rs->kind) {
+    case KPOP_EUCLIDEAN: return launch_row_norms_pair<KPOP_EUCLIDEAN>(nullptr, 0, nullptr, nullptr, r2 ? d_m2 : nullptr, r2, n2, b_div, rs->n_dims, rs->metric, rs->p, st);
+    case KPOP_COSINE: return launch_row_norms_pair<KPOP_COSINE>(nullptr, 0, nullptr, nullptr, r2 ? d_m2 : nullptr, r2, n2, b_div, rs->n_dims, rs->metric, rs->p, st);
+    default: return launch_row_norms_pair<KPOP_MINKOWSKI>(nullptr, 0, nullptr, nullptr, r2 ? d_m2 : nullptr, r2, n2, b_div, rs->n_dims, rs->metric, rs->p, st);
+  }
 }
 int refset_fill_long_lists(kpop_refset *rs, const double *d_m2, uint32_t r2, uint32_t max_neighbours, const double *out_stats, const uint32_t *out_n,
                            uint32_t *out_idx, double *out_dist, double *out_z, hipStream_t st) {

@@ -69,6 +69,9 @@ int refset_dev_summary(kpop_refset *rs, const double *d_m2, uint32_t r2, uint32_
                        double *d_out_stats, uint32_t *d_out_n, uint32_t *d_out_idx, double *d_out_dist, double *d_out_z, hipStream_t st);
 int refset_fill_long_lists(kpop_refset *rs, const double *d_m2, uint32_t r2, uint32_t max_neighbours, const double *out_stats, const uint32_t *out_n,
                            uint32_t *out_idx, double *out_dist, double *out_z, hipStream_t st);
+int refset_query_norms(const kpop_refset *rs, const double *d_m2, uint32_t r2, double *n2, double *b_div, hipStream_t st);
+// refset.hip: the handle belongs to the calling thread's device slot
+int refset_check_handle(const kpop_refset *rs, const char *who);
 // distance_mfma.hip / summary_large.hip: kernels the set's lazily built pieces share with the unprepared call
 int launch_sample_gather(const double *a, uint32_t r1, uint32_t n_dims, uint32_t s, double *out, hipStream_t st);
 int launch_row_sumsq(const double *x, uint32_t rows, uint32_t n_dims, const double *metric, double *out, hipStream_t st);
