@@ -401,6 +401,13 @@ int kpop_sharded_distance_summary(const double *m1, uint32_t r1, const double *m
  * arbitrary, as they are in R.  The dense S'S and S*W contractions run on the f64 matrix cores.            */
 int kpop_ca(const double *counts, uint64_t n_kmers, uint32_t n_spectra, int normalize, uint32_t *n_dims_out,
             double *twisted, double *inertia, double *twister);
+/* development: what the eigen-solver did in the last kpop_ca / kpop_dev_ca of the calling thread's device slot.  out[0] blocked
+   steps (0/1), out[1] the iteration ran on the Cholesky factor of the Gram matrix (0/1, after the pivot count), out[2] pivots at
+   the rounding floor, out[3] the kernel (0 plain steps, 1..8 rows a thread of the register kernel, 9 the looped kernel), out[4]
+   sweeps run, out[5] converged (0/1), out[6] the last sweep's largest cosine between two columns (the bits of the double),
+   out[7] how many of the sweeps were the closing ones on G after a run on the factor (0 otherwise).  Reads host words only: no
+   synchronisation.                                                                                                           */
+int kpop_debug_ca(uint64_t out[8]);
 
 /* ----------------------------------------------------------------- metric
  * Replaces Space.Distance.Metric.compute, lib/Space.ml:88-105 (called from

@@ -99,6 +99,7 @@ SIGNATURES = {
     "kpop_count_twist": (C.c_int, [vp, u8p, u64p, C.c_uint32, C.c_int, C.c_int, f64p]),
     "kpop_spectra_twist": (C.c_int, [vp, u8p, u64p, C.c_uint32, C.c_int, C.c_int, C.c_int, f64p]),
     "kpop_ca": (C.c_int, [f64p, C.c_uint64, C.c_uint32, C.c_int, u32p, f64p, f64p, f64p]),
+    "kpop_debug_ca": (C.c_int, [C.POINTER(C.c_uint64)]),
     "kpop_metric_compute": (C.c_int, [C.c_int, f64p, C.c_uint32, C.c_double, C.c_double, C.c_double, f64p]),
     "kpop_distance_rowwise": (C.c_int, [f64p, C.c_uint32, f64p, C.c_uint32, C.c_uint32, f64p, C.c_int,
                                         C.c_double, C.c_int, f64p]),

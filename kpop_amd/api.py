@@ -566,6 +566,14 @@ def ca(counts, normalize=True):
     return twisted[:, :nd], inertia[:nd], twister[:nd]
 
 
+def debug_ca():
+    """what the eigen-solver did in this thread's last ca() / dev_ca() (kpop_debug_ca): the route taken and its convergence"""
+    out = (C.c_uint64 * 8)()
+    check(_lib.load().kpop_debug_ca(out))
+    return {"blocked": int(out[0]), "on_factor": int(out[1]), "dead": int(out[2]), "kernel": int(out[3]), "sweeps": int(out[4]),
+            "converged": int(out[5]), "cosine": float(np.array([out[6]], dtype=np.uint64).view(np.float64)[0]), "closing": int(out[7])}
+
+
 def dev_ca_workspace_bytes(n_kmers, n_spectra):
     return int(_lib.load().kpop_dev_ca_workspace_bytes(int(n_kmers), int(n_spectra)))
 

@@ -13,6 +13,7 @@
 // The Gram route squares the condition number: dimensions whose singular value is below ~1e-7 of the largest
 // lose accuracy -- they carry < 1e-14 of the inertia.
 #include <math.h>
+#include <string.h>
 
 #include <algorithm>
 
@@ -116,8 +117,9 @@ __global__ __launch_bounds__(256) void ca_row_coords_kernel(const double *__rest
   }
 }
 
-// One-sided Jacobi (Hestenes) on the columns of the symmetric PSD matrix G (n x n): on exit the column norms
-// are the eigenvalues and V holds the eigenvectors.  Round-robin (circle method) pairing: the n/2 rotations of a
+// One-sided Jacobi (Hestenes) on the columns of the symmetric PSD matrix G (n x n): on exit the columns are orthogonal, their
+// norms the size of the eigenvalues, and V holds the eigenvectors (jacobi_eigen_psd_device reads the eigenvalues from V and G,
+// not from the norms).  Round-robin (circle method) pairing: the n/2 rotations of a
 // step touch disjoint columns, so a step is one launch with one 256-thread block per pair; 3 ordered block
 // reductions (|a_p|^2, |a_q|^2, a_p.a_q) then the rotation of both columns of A and of V.  The largest
 // |a_p.a_q| / (|a_p||a_q|) of a sweep is kept in `worst` (non-negative doubles order like their bit patterns).
@@ -199,7 +201,7 @@ __device__ __forceinline__ int jb_partner(int i, int round) {  // circle method 
 // orthogonal already).
 template <int WAVES>
 __device__ __forceinline__ void jacobi_solve_8x8(double (*s_part)[kJC * kJC], double (*s_R)[kJC], int *s_skip, unsigned long long *worst,
-                                                 int inner_sweeps) {
+                                                 int inner_sweeps, double null_sq) {
   const int lane = threadIdx.x & 63;
   const int r = lane >> 3, c = lane & 7;
   double M = 0.0;
@@ -208,11 +210,21 @@ __device__ __forceinline__ void jacobi_solve_8x8(double (*s_part)[kJC * kJC], do
   double R = r == c ? 1.0 : 0.0;
   // how far from orthogonal the eight columns are (the sweep's convergence measure, as in the plain step)
   const double drr = __shfl(M, 9 * r, 64), dcc = __shfl(M, 9 * c, 64);
-  double off = (r < c && drr > 0.0 && dcc > 0.0) ? fabs(M) / sqrt(drr * dcc) : 0.0;
+  // (the roots one by one: the product of two squared norms of a null direction's columns -- 1e-170 and less after a few sweeps --
+  // underflows, and |M| over the root of nothing was an infinite cosine in every sweep up to the sixtieth)
+  double off = (r < c && drr > 0.0 && dcc > 0.0) ? fabs(M) / (sqrt(drr) * sqrt(dcc)) : 0.0;
+  // A column of G V whose squared norm is not above null_sq belongs to a null direction of G.  It lies in the range of G all the
+  // same, so every sweep takes it off the other columns once more and leaves the rounding of that subtraction: 1e-16 of its
+  // length, with cosines of any size against everything -- until it underflows, twenty sweeps on.  Such a column is rotated
+  // like the others and kept out of the sweep's measure.
+  double off_live = (drr > null_sq && dcc > null_sq) ? off : 0.0;
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) off = fmax(off, __shfl_xor(off, o, 64));
+  for (int o = 32; o > 0; o >>= 1) {
+    off = fmax(off, __shfl_xor(off, o, 64));
+    off_live = fmax(off_live, __shfl_xor(off_live, o, 64));
+  }
   if (lane == 0) {
-    atomicMax(worst, (unsigned long long)__double_as_longlong(off));
+    atomicMax(worst, (unsigned long long)__double_as_longlong(off_live));
     *s_skip = off < 1e-15;
   }
   if (!(off < 1e-15)) {
@@ -258,7 +270,8 @@ __device__ __forceinline__ void jacobi_solve_8x8(double (*s_part)[kJC * kJC], do
 
 template <int NT>
 __global__ __launch_bounds__(NT) void jacobi_block_step_kernel(double *__restrict__ A, double *__restrict__ V, uint32_t n,
-                                                                uint32_t m_blk, uint32_t step, unsigned long long *worst, int inner_sweeps) {
+                                                                uint32_t m_blk, uint32_t step, unsigned long long *worst, int inner_sweeps,
+                                                                double null_sq) {
   __shared__ double s_part[NT / 64][kJC * kJC];
   __shared__ double s_R[kJC][kJC];
   __shared__ int s_skip;
@@ -314,7 +327,7 @@ __global__ __launch_bounds__(NT) void jacobi_block_step_kernel(double *__restric
       }
   }
   __syncthreads();
-  if (wv == 0) jacobi_solve_8x8<NT / 64>(s_part, s_R, &s_skip, worst, inner_sweeps);
+  if (wv == 0) jacobi_solve_8x8<NT / 64>(s_part, s_R, &s_skip, worst, inner_sweeps, null_sq);
   __syncthreads();
   if (s_skip) return;
   double Rl[kJC][kJC];
@@ -373,7 +386,8 @@ static_assert(kJC * (kJC + 1) / 2 == 36, "jacobi_wave_totals is written for 36 s
 // seven dependent trips to the L2 / MALL.
 template <int ROWS, bool WITH_V>
 __global__ __launch_bounds__(256) void jacobi_block_step_reg_kernel(double *__restrict__ A, double *__restrict__ V, uint32_t n,
-                                                                    uint32_t m_blk, uint32_t step, unsigned long long *worst, int inner_sweeps) {
+                                                                    uint32_t m_blk, uint32_t step, unsigned long long *worst, int inner_sweeps,
+                                                                double null_sq) {
   __shared__ double s_part[4][kJC * kJC];
   __shared__ double s_R[kJC][kJC];
   __shared__ int s_skip;
@@ -462,7 +476,7 @@ __global__ __launch_bounds__(256) void jacobi_block_step_reg_kernel(double *__re
     }
   }
   __syncthreads();
-  if (wv == 0) jacobi_solve_8x8<4>(s_part, s_R, &s_skip, worst, inner_sweeps);
+  if (wv == 0) jacobi_solve_8x8<4>(s_part, s_R, &s_skip, worst, inner_sweeps, null_sq);
   __syncthreads();
   if (s_skip) return;
   double Rl[kJC][kJC];
@@ -590,17 +604,33 @@ __global__ void chol_zero_upper_kernel(double *__restrict__ A, uint32_t n) {
     if (e % n < e / n) A[e] = 0.0;
 }
 
-// columns orthogonal: eigenvalue = squared norm, eigenvector = the column over its norm (zero for a null direction)
-__global__ __launch_bounds__(256) void jacobi_unit_columns_kernel(const double *__restrict__ A, uint32_t n, double *__restrict__ V,
-                                                                  double *__restrict__ lambda) {
+// columns orthogonal: eigenvector = the column over its norm (zero for a null direction).  V may be A: a thread rewrites what
+// it alone has read.
+__global__ __launch_bounds__(256) void jacobi_unit_columns_kernel(const double *A, uint32_t n, double *V) {
   __shared__ double s_w[4];
   const double *a = A + (uint64_t)blockIdx.x * n;
   double s = 0.0;
   for (uint32_t i = threadIdx.x; i < n; i += 256) s += a[i] * a[i];
   s = block_sum_256(s, s_w);
-  if (threadIdx.x == 0) lambda[blockIdx.x] = s;
   const double norm = sqrt(s);
   for (uint32_t i = threadIdx.x; i < n; i += 256) V[(uint64_t)blockIdx.x * n + i] = norm > 0.0 ? a[i] / norm : 0.0;
+}
+
+// V <- (3 V - H) / 2 with H = (V V') V
+__global__ void jacobi_newton_schulz_kernel(double *__restrict__ V, const double *__restrict__ H, uint32_t n) {
+  const uint64_t total = (uint64_t)n * n, stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) V[e] = 1.5 * V[e] - 0.5 * H[e];
+}
+
+// eigenvalue of unit vector j = v_j' (G v_j), GV holding G v_j where V holds v_j
+__global__ __launch_bounds__(256) void jacobi_rayleigh_kernel(const double *__restrict__ V, const double *__restrict__ GV, uint32_t n,
+                                                              double *__restrict__ lambda) {
+  __shared__ double s_w[4];
+  const double *v = V + (uint64_t)blockIdx.x * n, *g = GV + (uint64_t)blockIdx.x * n;
+  double s = 0.0;
+  for (uint32_t i = threadIdx.x; i < n; i += 256) s += v[i] * g[i];
+  s = block_sum_256(s, s_w);
+  if (threadIdx.x == 0) lambda[blockIdx.x] = s;
 }
 
 // *dead_out: the pivots at or below the tolerance (their columns are zeroed, not pivoted around)
@@ -636,15 +666,6 @@ static int cholesky_in_place(double *d_A, uint32_t n, double *d_scratch /* n x n
   return 0;
 }
 
-__global__ __launch_bounds__(256) void jacobi_colnorm_kernel(const double *__restrict__ A, uint32_t n, double *__restrict__ lambda) {
-  __shared__ double s_w[4];
-  const double *a = A + (uint64_t)blockIdx.x * n;
-  double s = 0.0;
-  for (uint32_t i = threadIdx.x; i < n; i += 256) s += a[i] * a[i];
-  s = block_sum_256(s, s_w);
-  if (threadIdx.x == 0) lambda[blockIdx.x] = sqrt(s);
-}
-
 // d_G is overwritten; d_V receives the eigenvectors as columns (V[j*n + i] = component i of vector j), d_lambda the eigenvalues
 static int jacobi_eigen_psd_device(double *d_G, double *d_V, uint32_t n, double *d_lambda, unsigned long long *d_worst, hipStream_t st) {
   const uint32_t m = (n + 1) & ~1u;
@@ -653,15 +674,27 @@ static int jacobi_eigen_psd_device(double *d_G, double *d_V, uint32_t n, double 
   // From 32 columns up to what the register kernel holds: Jacobi on the Cholesky factor of G, no V to rotate.  (2048: on G
   // itself with V accumulated, as below that size and above it, for A/B.)
   bool on_factor = blocked && n <= 2048 && !(ctx().tune_dbg & (64 | 2048));
+  uint32_t dead = 0;
+  // G is kept: the eigenvalues are taken from it once the eigenvectors are there (below), and a factorisation with more than
+  // one dead pivot puts it back
+  DevBuf keep;
+  KPOP_TRY(keep.alloc((uint64_t)n * n * 8));
+  KPOP_HIP(hipMemcpyAsync(keep.p, d_G, (uint64_t)n * n * 8, hipMemcpyDeviceToDevice, st));
+  // what the norm of a column of G V (the size of an eigenvalue) has to exceed to count in a sweep's measure: the tolerance of
+  // a pivot of the factorisation
+  double null_norm = 0.0;
+  if (blocked) {
+    std::vector<double> diag(n);
+    KPOP_HIP(hipMemcpy2DAsync(diag.data(), 8, d_G, (size_t)(n + 1) * 8, 8, n, hipMemcpyDeviceToHost, st));
+    KPOP_HIP(hipStreamSynchronize(st));
+    for (double v : diag) null_norm = std::max(null_norm, v);
+    null_norm *= 1e-13;
+  }
   if (on_factor) {
     // The factorisation does not pivot: a pivot at the rounding floor is declared dead and its column zeroed.  A Gram matrix
     // of standardised residuals has ONE such direction by construction (the trivial axis); MORE of them mean near-dependent
     // columns (near-duplicate classes), where the couplings dropped with the dead columns would show in the eigenvectors at
     // ~1e-7 relative, not 1e-13.  Then G is put back and the iteration runs on G itself, as it does above 2,048.
-    DevBuf keep;
-    KPOP_TRY(keep.alloc((uint64_t)n * n * 8));
-    KPOP_HIP(hipMemcpyAsync(keep.p, d_G, (uint64_t)n * n * 8, hipMemcpyDeviceToDevice, st));
-    uint32_t dead = 0;
     KPOP_TRY(cholesky_in_place(d_G, n, d_V, st, &dead));
     if (dead > 1 && !(ctx().tune_dbg & (1 << 29))) {  // (1 << 29: stay on the factor, for A/B)
       if (getenv("KPOP_JACOBI_TRACE")) fprintf(stderr, "[jacobi] %u pivots at the rounding floor: the iteration runs on G, not on its factor\n", dead);
@@ -670,56 +703,116 @@ static int jacobi_eigen_psd_device(double *d_G, double *d_V, uint32_t n, double 
       on_factor = false;
     }
   }
-  if (!on_factor) {
+  const uint32_t rows = (ctx().tune_dbg & 64) ? 0u : div_up(n, 256);  // (64: the looped kernel, for A/B)
+  int sweeps = 0;
+  double w_last = 0.0;
+  // sweeps until the columns of d_G are orthogonal: of the factor (no V), or of G V with V rotated along
+  auto iterate = [&](bool factor, bool *converged) -> int {
+    const double null_sq = factor ? 0.0 : null_norm * null_norm;
+    double w_before = 1.0;
+    *converged = false;
+    for (int sweep = 0; sweep < 60; ++sweep) {
+      KPOP_HIP(hipMemsetAsync(d_worst, 0, 8, st));
+      if (blocked) {
+        for (uint32_t step = 0; step + 1 < m_blk; ++step) {
+          const int inner = (ctx().tune_dbg & 15) ? (int)(ctx().tune_dbg & 15) : 1;
+          const dim3 grid(m_blk / 2), block(256);
+          unsigned long long *w = d_worst;
+          switch (rows) {
+#define KPOP_JACOBI_ROWS(R)                                                                                         \
+  case R:                                                                                                           \
+    if (factor) jacobi_block_step_reg_kernel<R, false><<<grid, block, 0, st>>>(d_G, d_V, n, m_blk, step, w, inner, null_sq); \
+    else jacobi_block_step_reg_kernel<R, true><<<grid, block, 0, st>>>(d_G, d_V, n, m_blk, step, w, inner, null_sq);         \
+    break;
+            KPOP_JACOBI_ROWS(1) KPOP_JACOBI_ROWS(2) KPOP_JACOBI_ROWS(3) KPOP_JACOBI_ROWS(4)
+            KPOP_JACOBI_ROWS(5) KPOP_JACOBI_ROWS(6) KPOP_JACOBI_ROWS(7) KPOP_JACOBI_ROWS(8)
+#undef KPOP_JACOBI_ROWS
+            default: jacobi_block_step_kernel<256><<<grid, block, 0, st>>>(d_G, d_V, n, m_blk, step, w, inner, null_sq);
+          }
+          KPOP_LAUNCH_CHECK();
+        }
+      } else
+        for (uint32_t step = 0; step + 1 < m; ++step) {
+          jacobi_step_kernel<<<dim3(m / 2), dim3(256), 0, st>>>(d_G, d_V, n, m, step, d_worst);
+          KPOP_LAUNCH_CHECK();
+        }
+      double w = 0.0;
+      KPOP_HIP(hipMemcpyAsync(&w, d_worst, 8, hipMemcpyDeviceToHost, st));
+      KPOP_HIP(hipStreamSynchronize(st));
+      if (getenv("KPOP_JACOBI_TRACE")) fprintf(stderr, "[jacobi] sweep %d: largest |cos| between two columns %.3e\n", sweeps, w);
+      ++sweeps;
+      w_last = w;
+      // done at 1e-15 -- or at the rounding floor, which for some matrices sits a little above that: below 1e-13 a sweep that
+      // does not halve the largest cosine any more is rotating noise (the quadratic phase squares it every sweep)
+      if (w < 1e-15 || (w < 1e-13 && w > 0.5 * w_before)) {
+        *converged = true;
+        break;
+      }
+      w_before = w;
+    }
+    return 0;
+  };
+  bool converged = true, done = false;
+  int polish_from = 0;
+  if (on_factor) {
+    KPOP_TRY(iterate(true, &converged));
+    // The factor's columns over their norms are the eigenvectors of L L', which is G only to the factorisation's backward error:
+    // n roundings of the largest diagonal entry in the last pivots (the Schur complement of a matrix with a null direction
+    // cancels to nothing there), 2e-14 of the largest eigenvalue measured at 1,025 columns and more, twenty times what an
+    // eigen-decomposition of G itself leaves.  So the iteration ends ON G: from A = G V with these vectors, whose columns are
+    // orthogonal to ~1e-12 already -- two or three sweeps with V rotated along.  (1 << 23: leave that out, for A/B.)
+    jacobi_unit_columns_kernel<<<dim3(n), dim3(256), 0, st>>>(d_G, n, d_V);
+    KPOP_LAUNCH_CHECK();
+    done = (ctx().tune_dbg & (1 << 23)) != 0;
+    if (!done) {
+      KPOP_TRY(gemm_f64<false>(d_V, n, keep.as<double>(), n, d_G, n, n, n, 1, nullptr, 0, st));
+      polish_from = sweeps;
+    }
+  } else {
     jacobi_identity_kernel<<<dim3(std::min<uint32_t>(div_up((uint64_t)n * n, 256), 4096)), dim3(256), 0, st>>>(d_V, n);
     KPOP_LAUNCH_CHECK();
   }
-  double w_before = 1.0;
-  bool converged = false;
-  for (int sweep = 0; sweep < 60; ++sweep) {
-    KPOP_HIP(hipMemsetAsync(d_worst, 0, 8, st));
-    if (blocked) {
-      for (uint32_t step = 0; step + 1 < m_blk; ++step) {
-        const int inner = (ctx().tune_dbg & 15) ? (int)(ctx().tune_dbg & 15) : 1;
-        const dim3 grid(m_blk / 2), block(256);
-        unsigned long long *w = d_worst;
-        switch ((ctx().tune_dbg & 64) ? 0u : div_up(n, 256)) {  // (64: the looped kernel, for A/B)
-#define KPOP_JACOBI_ROWS(R)                                                                                           \
-  case R:                                                                                                             \
-    if (on_factor) jacobi_block_step_reg_kernel<R, false><<<grid, block, 0, st>>>(d_G, d_V, n, m_blk, step, w, inner); \
-    else jacobi_block_step_reg_kernel<R, true><<<grid, block, 0, st>>>(d_G, d_V, n, m_blk, step, w, inner);           \
-    break;
-          KPOP_JACOBI_ROWS(1) KPOP_JACOBI_ROWS(2) KPOP_JACOBI_ROWS(3) KPOP_JACOBI_ROWS(4)
-          KPOP_JACOBI_ROWS(5) KPOP_JACOBI_ROWS(6) KPOP_JACOBI_ROWS(7) KPOP_JACOBI_ROWS(8)
-#undef KPOP_JACOBI_ROWS
-          default: jacobi_block_step_kernel<256><<<grid, block, 0, st>>>(d_G, d_V, n, m_blk, step, w, inner);
-        }
-        KPOP_LAUNCH_CHECK();
-      }
-    } else
-    for (uint32_t step = 0; step + 1 < m; ++step) {
-      jacobi_step_kernel<<<dim3(m / 2), dim3(256), 0, st>>>(d_G, d_V, n, m, step, d_worst);
-      KPOP_LAUNCH_CHECK();
-    }
-    double w = 0.0;
-    KPOP_HIP(hipMemcpyAsync(&w, d_worst, 8, hipMemcpyDeviceToHost, st));
-    KPOP_HIP(hipStreamSynchronize(st));
-    if (getenv("KPOP_JACOBI_TRACE")) fprintf(stderr, "[jacobi] sweep %d: largest |cos| between two columns %.3e\n", sweep, w);
-    // done at 1e-15 -- or at the rounding floor, which for some matrices sits a little above that: below 1e-13 a sweep that
-    // does not halve the largest cosine any more is rotating noise (the quadratic phase squares it every sweep)
-    if (w < 1e-15 || (w < 1e-13 && w > 0.5 * w_before)) {
-      converged = true;
-      break;
-    }
-    w_before = w;
+  if (!done) {
+    bool c2 = false;
+    KPOP_TRY(iterate(false, &c2));
+    converged = converged && c2;
   }
   // (sixty sweeps have always been enough -- eight to twelve are typical --; a matrix that is not done by then is reported,
   // not passed on in silence: the caller's results are then only as orthogonal as the figure says)
   if (!converged)
-    fprintf(stderr, "[kpop] warning: the one-sided Jacobi iteration stopped after 60 sweeps with |cos| = %.3e between two columns\n", w_before);
-  if (on_factor) jacobi_unit_columns_kernel<<<dim3(n), dim3(256), 0, st>>>(d_G, n, d_V, d_lambda);
-  else jacobi_colnorm_kernel<<<dim3(n), dim3(256), 0, st>>>(d_G, n, d_lambda);
+    fprintf(stderr, "[kpop] warning: the one-sided Jacobi iteration stopped after 60 sweeps with |cos| = %.3e between two columns\n", w_last);
+  {  // what kpop_debug_ca reports
+    uint64_t *dbg = ctx().ca_debug, w_bits;
+    memcpy(&w_bits, &w_last, 8);
+    dbg[0] = blocked;
+    dbg[1] = on_factor;
+    dbg[2] = dead;
+    dbg[3] = !blocked ? 0u : (rows >= 1 && rows <= 8) ? rows : 9u;
+    dbg[4] = (uint64_t)sweeps;
+    dbg[5] = converged;
+    dbg[6] = w_bits;
+    dbg[7] = on_factor && !done ? (uint64_t)(sweeps - polish_from) : 0;
+  }
+  // What is read from the iteration is the DIRECTIONS of V alone.  A column has been through thousands of 8 x 8 rotations by now
+  // (sweeps x steps), every one orthogonal only to rounding and the same for all of its rows: the norms of the rotated columns
+  // had drifted by 1.3e-13 relative at 255 columns after 11 sweeps, and V is as far from orthonormal as that (8e-14 between two
+  // columns at 2,049 after 16 sweeps), where the directions are right to 1e-15.  So V takes one Newton-Schulz step towards the
+  // nearest orthonormal matrix, V (3 I - V'V) / 2 -- a departure e becomes e^2; vectors of a null direction that are zero stay
+  // zero --, and the eigenvalues are the Rayleigh quotients v' G v against the G that was kept (second order in what is left of
+  // the directions' error).  Three n x n x n products on the matrix cores; d_G is done with and takes the first and the last.
+  if (!done) {
+    DevBuf half;
+    KPOP_TRY(half.alloc((uint64_t)n * n * 8));
+    KPOP_TRY(gemm_f64<true>(d_V, n, d_V, n, d_G, n, n, n, 1, nullptr, 0, st));                 // V V' (rows of d_V are the vectors)
+    KPOP_TRY(gemm_f64<false>(d_V, n, d_G, n, half.as<double>(), n, n, n, 1, nullptr, 0, st));  // its product with every vector
+    jacobi_newton_schulz_kernel<<<dim3(std::min<uint32_t>(div_up((uint64_t)n * n, 256), 4096)), dim3(256), 0, st>>>(d_V, half.as<double>(), n);
+    KPOP_LAUNCH_CHECK();
+    KPOP_HIP(hipStreamSynchronize(st));  // (`half` goes with this scope)
+  }
+  KPOP_TRY(gemm_f64<false>(d_V, n, keep.as<double>(), n, d_G, n, n, n, 1, nullptr, 0, st));
+  jacobi_rayleigh_kernel<<<dim3(n), dim3(256), 0, st>>>(d_V, d_G, n, d_lambda);
   KPOP_LAUNCH_CHECK();
+  KPOP_HIP(hipStreamSynchronize(st));  // (`keep` goes with this frame)
   return 0;
 }
 
@@ -1066,6 +1159,14 @@ extern "C" int kpop_ca(const double *counts, uint64_t n_kmers, uint32_t n_spectr
   }
   tm.mark("release of the table");
   return rc;
+}
+
+extern "C" int kpop_debug_ca(uint64_t *out) {
+  KPOP_TRY(require_init());
+  if (!out) KPOP_FAIL(KPOP_ERR_INVALID, "kpop_debug_ca: null argument");
+  Context &c = ctx();
+  for (int i = 0; i < 8; ++i) out[i] = c.ca_debug[i];
+  return KPOP_OK;
 }
 
 extern "C" uint64_t kpop_dev_ca_workspace_bytes(uint64_t n_kmers, uint32_t n_spectra) {

@@ -115,6 +115,7 @@ struct Context {
   //   1024             distance_rowwise: the 256-row staging (two wavefronts a SIMD) where 128 rows would do
   //   1 << 28          CSR twist: one wavefront per spectrum even for a few very long spectra (same bits as the segmented launch)
   //   1 << 29          ca: stay on the Cholesky factor however many pivots were at the rounding floor
+  //   1 << 23          ca: the factor's eigenvectors as they are, without the closing sweeps on G
   //   1 << 30          summaries against <= 256 rows: round 3's kernel, one row of a wavefront at a time
   int tune_dbg = 0;
   int tune_dense = 2;    // the matrix-core routes of the twist: 2 (default) chosen by the batch -- assemblies through count_twist_tile_kernel (consensus on the matrix cores + residual gather), small-k assemblies through the dense image, dense spectra through the contraction --, 1 kpop_twist always dense, 0 never (the sparse mat-vec in the reference's order of additions everywhere)
@@ -141,6 +142,9 @@ struct Context {
   int tune_distill_band = 0;  // k-mers a band of kpop_dev_counter_distill at most (0: what the workspace holds); same results
   int tune_distill_clock = 0; // 1: distill drains its stream after every band and keeps the time of its three phases (kpop_debug_distill_clocks)
   double distill_ms[3] = {0., 0., 0.};
+  // what the eigen-solver of the slot's last kpop_ca / kpop_dev_ca did (kpop_debug_ca): blocked, on the factor, dead pivots, kernel
+  // (0 plain steps, 1..8 ROWS of the register kernel, 9 the looped kernel), sweeps, converged, the last largest cosine's bits, the sweeps on G that closed a run on the factor
+  uint64_t ca_debug[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   int tune_histlds = 1;  // ... staged through LDS: private tables (k <= 7), sorted chunks of assemblies (0: direct atomics; 2: always sort the chunks)
 };
 constexpr int kMaxSlots = 16;
