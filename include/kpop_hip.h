@@ -111,9 +111,21 @@ int kpop_device_count(void);        /* >=0, or negative kpop_status */
 const char *kpop_last_error(void);
 const char *kpop_version(void);
 int kpop_synchronize(void *stream);
-/* performance knobs for A/B measurements (results are identical for every setting):
-   "unroll" 8|16 row loads in flight per wave; "nt" row loads 0 plain | 1 non-temporal | 2 chosen by the size of the
-   twister (default); "seg" windows per segment of the genome kernel, 0 = sized to an XCD's L2 (default); "hist" 1 (default) | 0: the
+/* performance knobs for A/B measurements.  A value outside what is listed is KPOP_ERR_INVALID.  What a setting may do to RESULTS, knob by
+   knob (tests/tune_contract.py keeps this as a table, tests/test_gpu_tune_contract.py and the tests it names hold the kernels to it):
+     the SAME BITS as the default's, every setting: "unroll", "nt", "ldspad", "pipeprio", "tilewide" (up to 64 dimensions), "hist", "histlds",
+       "histguess", "blocksort", "class_set", "summary_mfma_lists", "summary_lanes", "distill_band";
+     another ORDER of the same additions -- equal to the reference within 1e-12 of the result's scale (what the tests enforce), not bit for
+       bit: "seg", "dense", "tilepipe", "tileg", "tilecap_mb", "direct" (a twister that lacks rows; a complete one: the same bits).  Measured,
+       as max|got - reference| over max(max|reference|, 1): "seg" 64 2.6e-15, 1024 6.2e-15, 16384 1.3e-14, the default's own segments 1.2e-14
+       (sequences of up to 40,000 bases, 24 to 300 dimensions); "tileg" 32 and 64 under "tilepipe" 0 1.2e-14 (70 assemblies of 3 kb, 40 to 130);
+     the matrix cores' APPROXIMATION of distances, and what chooses among its paths -- distances <= 1e-12 relative; a summary's medians, MADs
+       and neighbour lists bit for bit, its mean and standard deviation sums of approximate values (1e-13 relative): "distance_mfma",
+       "summary_mfma", "summary2", "summary_sample", "summary_rawref", "summary_pass";
+     nothing (instrumentation): "summary_audit", "distill_clock"; and "dbg", development switches under some of which results are wrong.
+   "unroll" 8 (default) | 16 row loads in flight per wave; "nt" row loads 0 plain | 1 non-temporal | 2 chosen by the size of the
+   twister (default); "seg" 0 (default) | 64..16384 in steps of 64: windows per segment of the genome kernel, 0 = sized to an XCD's L2 (with
+   a value set the tile route is off: the streaming kernel alone, its partial sums cut where the segments end); "hist" 1 (default) | 0: the
    merged spectrum of kpop_count_reads(per_read = 0) by atomic histogram where the hashes fit 26 bits, or always by sort;
    "histlds" 1 (default) | 0 | 2 | 3 | 4: that histogram staged through LDS as the batch suggests (private tables up to k = 7;
    (hash, count) tables over the same stretch of 64 assemblies of one organism; for what does not repeat -- a read set,
@@ -152,16 +164,21 @@ int kpop_synchronize(void *stream);
    "tilepipe" 1 (default) | 0: the tile route's kernel with producer and consumer wavefronts (tile_pipe.h; beyond 64 dimensions its three-stage
    form: producers / MFMA wavefronts / gather wavefronts), or round 4's; "tilewide" 0 (default) | 1: that three-stage form at any number of
    dimensions (up to 64: the same bits); "tilecap_mb" 0 (default: 4 GiB per 64 columns, a quarter of the device at most) | MiB: the per-slot tables
-   a call of that route may take before the batch goes through in sub-batches of sequences; "pipeprio" 1 (default) | 0..3: issue priority of its MFMA wavefronts;
+   a call of that route may take before the batch goes through in sub-batches of sequences; "pipeprio" 1 (default) | 0..7: the low two bits are
+   the issue priority of its MFMA wavefronts, bit 2 is accepted and read by nothing (4..7 run what 0..3 run);
+   "tileg" 64 (default) | 32: sequences a chunk of round 4's kernel -- one block of 1,024 threads a CU or two of 512 (measured slower) --, read
+   under "tilepipe" 0 only; "blocksort" 1 (default) | 0: kpop_count_reads(per_read = 1) on sequences of 513..32,768 windows sorts each in the LDS
+   of a block of its own, or all of them in one device-wide sort;
    "dense" 2 (default) | 1 | 0: the matrix-core routes of the twist.  2: chosen by the batch -- sequences of more than 512
    windows (assemblies, k <= 15) go through count_twist_tile_kernel: the CONSENSUS rows of a stretch of 64 sequences x 512
    windows (the rows of four seed sequences, an LDS set) are multiplied on the f64 matrix cores, the rows private to one
    sequence are gathered per sequence (tile_residual_kernel), stretches that share little with their seeds stay with the
    streaming kernel; kpop_count_twist's batches of assemblies at small k go through the dense image of their
    counts (kpop_dev_count_twist_dense); kpop_twist takes the dense contraction when the spectra are dense enough.  1: kpop_twist
-   always by the dense contraction.  0: opt out -- the sparse mat-vec in the reference's order of additions everywhere.  The
-   one knob that changes results, in the last bits (<= 2e-15 relative measured; north_star allows 1e-5); "ldspad" bytes of
-   extra LDS per block of the fused reads kernel (an occupancy probe); "dbg" development switches (also KPOP_TUNE_DBG)  */
+   always by the dense contraction (a twister small enough for the dense image).  0: opt out -- the sparse mat-vec in the reference's
+   order of additions everywhere.  Results change in the last bits (<= 2e-15 relative measured; north_star allows 1e-5);
+   "ldspad" 0 (default) | up to 65536: bytes of extra LDS per block of the fused reads kernel (an occupancy probe; a launch that no longer fits
+   the CU's LDS fails with KPOP_ERR_HIP); "dbg" development switches (also KPOP_TUNE_DBG)  */
 int kpop_tune(const char *key, int value);
 /* development: the phase clocks count_twist_tile_kernel adds up under kpop_tune("dbg", 16 << 24) (s_memtime ticks of thread 0 of
    every block, eight phases in out[0..7]; tools/probes/ab_tile_kernel.py prints them) and, under kpop_tune("dbg", 32 << 24), the

@@ -78,7 +78,9 @@ def dev_count_twist_packed(tw, d_codes, d_invalid, d_offsets, n_reads, n_bases, 
 
 
 def tune(key, value):
-    """Performance knobs for A/B runs (kpop_tune); results do not depend on them."""
+    """Performance knobs for A/B runs (kpop_tune, include/kpop_hip.h).  Most leave every bit of the results alone; "seg", "dense", "tilepipe",
+    "tileg", "tilecap_mb" and "direct" change the order of additions (1e-12 of the result's scale), "distance_mfma" and the "summary*" family
+    choose among the matrix cores' approximations; the header says which knob is which, tests/tune_contract.py keeps the table."""
     check(_lib.load().kpop_tune(key.encode(), int(value)))
 
 
