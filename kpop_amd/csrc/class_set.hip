@@ -19,6 +19,7 @@
 
 #include "common.h"
 #include "space_ops.h"
+#include "distance_routes.h"
 
 namespace kpop {
 

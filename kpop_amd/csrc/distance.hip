@@ -17,6 +17,7 @@
 #include <math.h>
 
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #include <string.h>
@@ -26,7 +27,8 @@
 #include "radix_sort.h"
 #include "space_ops.h"
 #include "row_norms.h"
-#include "refset.h"
+#include "distance_routes.h"
+#include "summary_layout.h"
 #include "wave_sort.h"
 
 namespace kpop {
@@ -606,8 +608,7 @@ __global__ __launch_bounds__(64 * kSummaryWaves) void distance_summary_wave_kern
 
 template <int KIND, bool PRE, int R, bool TAIL>
 static int launch_summary_wave_r(const double *a, uint32_t r1, const double *b, uint32_t r2, uint32_t n_dims, const double *metric,
-                                 double p, uint32_t req_len, uint32_t max_neighbours, double *out_stats, uint32_t *out_n,
-                                 uint32_t *out_idx, double *out_dist, double *out_z, hipStream_t st) {
+                                 double p, const SummaryOut &out, hipStream_t st) {
   const uint32_t per_wave = ((uint32_t)(64 * (R + (TAIL ? 1 : 0))) * 20 + (PRE ? 0u : n_dims * 8) + 15) & ~15u;
   const size_t shared = PRE ? 0 : ((size_t)n_dims * r1 + n_dims) * 8;
   // as many waves per block as the LDS left beside the shared operand allows: two blocks per CU (78 KB each) while eight
@@ -625,7 +626,7 @@ static int launch_summary_wave_r(const double *a, uint32_t r1, const double *b, 
   }
   const uint32_t blocks = std::min<uint32_t>(div_up(r2, waves), (uint32_t)ctx().n_cus * (two ? 2 : 1));
   distance_summary_wave_kernel<KIND, PRE, R, TAIL><<<dim3(blocks), dim3(64 * waves), smem, st>>>(
-      a, r1, b, r2, n_dims, metric, p, req_len, max_neighbours, out_stats, out_n, out_idx, out_dist, out_z, (ctx().tune_dbg >> 16) & 15);
+      a, r1, b, r2, n_dims, metric, p, out.req_len(r1), out.max_neighbours, out.stats, out.n, out.idx, out.dist, out.z, (ctx().tune_dbg >> 16) & 15);
   KPOP_LAUNCH_CHECK();
   return 0;
 }
@@ -980,8 +981,7 @@ static inline bool summary_fits_batch(uint32_t r1, uint32_t n_dims, bool pre, in
 
 template <int KIND, bool PRE, int R, bool TAIL>
 static int launch_summary_batch_r(const double *a, uint32_t r1, const double *b, uint32_t r2, uint32_t n_dims, const double *metric,
-                                  double p, uint32_t req_len, uint32_t max_neighbours, double *out_stats, uint32_t *out_n,
-                                  uint32_t *out_idx, double *out_dist, double *out_z, hipStream_t st, const double *nb) {
+                                  double p, const SummaryOut &out, hipStream_t st, const double *nb) {
   constexpr int JB = summary_batch_rows<R, TAIL>();
   const size_t per_wave = summary_batch_per_wave(r1, n_dims, PRE, JB);
   const size_t shared = PRE ? 0 : ((size_t)n_dims * r1 + n_dims) * 8;
@@ -999,8 +999,8 @@ static int launch_summary_batch_r(const double *a, uint32_t r1, const double *b,
   }
   const uint32_t blocks = std::min<uint32_t>(div_up(div_up(r2, JB), waves), (uint32_t)ctx().n_cus * (two ? 2 : 1));
   distance_summary_batch_kernel<KIND, PRE, R, TAIL, JB><<<dim3(blocks), dim3(64 * waves), smem, st>>>(
-      a, r1, b, r2, n_dims, metric, p, req_len, max_neighbours, summary_batch_stride(r1), (uint32_t)per_wave, out_stats, out_n, out_idx,
-      out_dist, out_z, (ctx().tune_dbg >> 16) & 15, PRE ? nullptr : nb);
+      a, r1, b, r2, n_dims, metric, p, out.req_len(r1), out.max_neighbours, summary_batch_stride(r1), (uint32_t)per_wave, out.stats, out.n, out.idx,
+      out.dist, out.z, (ctx().tune_dbg >> 16) & 15, PRE ? nullptr : nb);
   KPOP_LAUNCH_CHECK();
   return 0;
 }
@@ -1038,13 +1038,10 @@ static int summary_batch_case(uint32_t r1, uint32_t n_dims, bool pre) {
 
 template <int KIND, bool PRE>
 static int launch_summary_wave(const double *a, uint32_t r1, const double *b, uint32_t r2, uint32_t n_dims, const double *metric,
-                               double p, uint32_t req_len, uint32_t max_neighbours, double *out_stats, uint32_t *out_n,
-                               uint32_t *out_idx, double *out_dist, double *out_z, hipStream_t st, const double *nb = nullptr) {
-#define KPOP_WAVE(RR, TT) \
-  return launch_summary_wave_r<KIND, PRE, RR, TT>(a, r1, b, r2, n_dims, metric, p, req_len, max_neighbours, out_stats, out_n, out_idx, out_dist, out_z, st)
+                               double p, const SummaryOut &out, hipStream_t st, const double *nb = nullptr) {
+#define KPOP_WAVE(RR, TT) return launch_summary_wave_r<KIND, PRE, RR, TT>(a, r1, b, r2, n_dims, metric, p, out, st)
   const bool tails = !(ctx().tune_dbg & 32768);  // (32768: the doubled network for a few columns beyond 64 R, for A/B)
-#define KPOP_BATCH(RR, TT) \
-  return launch_summary_batch_r<KIND, PRE, RR, TT>(a, r1, b, r2, n_dims, metric, p, req_len, max_neighbours, out_stats, out_n, out_idx, out_dist, out_z, st, nb)
+#define KPOP_BATCH(RR, TT) return launch_summary_batch_r<KIND, PRE, RR, TT>(a, r1, b, r2, n_dims, metric, p, out, st, nb)
   switch (summary_batch_case(r1, n_dims, PRE)) {
     case 1: KPOP_BATCH(1, false);
     case 2: KPOP_BATCH(1, true);
@@ -1083,29 +1080,28 @@ static DistWork carve(void *work, uint32_t r1, uint32_t r2, uint32_t n_dims, con
   return d;
 }
 
+static DistWork carve(const DistOperands &o) { return carve(o.work, o.r1, o.r2, o.n_dims, o.prep); }
+
 template <int KIND>
-static int prepare_operands(const double *m1, uint32_t r1, const double *m2, uint32_t r2, uint32_t n_dims,
-                            const double *metric, double p, int normalize, void *work, const double **a,
-                            const double **b, hipStream_t st, kpop_refset *prep = nullptr) {
-  if (!normalize) {  // n1 = n2 = 1 (lib/Matrix.ml:201-202): x /. 1. = x
-    *a = m1;
-    *b = m2;
+static int prepare_operands(const DistOperands &o, const double **a, const double **b) {
+  if (!o.normalize) {  // n1 = n2 = 1 (lib/Matrix.ml:201-202): x /. 1. = x
+    *a = o.m1;
+    *b = o.m2;
     return 0;
   }
-  DistWork w = carve(work, r1, r2, n_dims, prep);
-  if (prep) {  // the set keeps its normalised copy (the same quotients): the query rows alone are divided here
-    KPOP_TRY(prep->divided(st, a));
-    KPOP_TRY(launch_row_norms_pair<KIND>(nullptr, 0, nullptr, nullptr, r2 ? m2 : nullptr, r2, w.n2, w.b, n_dims, metric, p, st));
+  DistWork w = carve(o);
+  if (o.prep) {  // the set keeps its normalised copy (the same quotients): the query rows alone are divided here
+    KPOP_TRY(o.prep->divided(o.st, a));
+    KPOP_TRY(launch_row_norms_pair<KIND>(nullptr, 0, nullptr, nullptr, o.r2 ? o.m2 : nullptr, o.r2, w.n2, w.b, o.n_dims, o.metric, o.p, o.st));
     *b = w.b;
     return 0;
   }
-  KPOP_TRY(launch_row_norms_pair<KIND>(r1 ? m1 : nullptr, r1, w.n1, w.a, r2 ? m2 : nullptr, r2, w.n2, w.b, n_dims, metric, p, st));
+  KPOP_TRY(launch_row_norms_pair<KIND>(o.r1 ? o.m1 : nullptr, o.r1, w.n1, w.a, o.r2 ? o.m2 : nullptr, o.r2, w.n2, w.b, o.n_dims, o.metric, o.p, o.st));
   *a = w.a;
   *b = w.b;
   return 0;
 }
 
-// launches the rowwise kernel on prepared (normalised) operands
 // ---------------------------------------------------------------------------
 // long rows (n_dims >= kLongD): norms and distances summed slab by slab
 // ---------------------------------------------------------------------------
@@ -1164,6 +1160,7 @@ __global__ void reduce_slabs_kernel(const double *__restrict__ partial, uint64_t
   out[e] = scale_distance<KIND>(acc, p);
 }
 
+// launches the rowwise kernel on prepared (normalised) operands; na / nb: operands as they are, divided by these norms as they are staged
 template <int KIND>
 static int rowwise_block(const double *a, uint32_t r1, const double *b, uint32_t r2, uint32_t n_dims, const double *metric,
                          double p, double *out, hipStream_t st, const double *na = nullptr, const double *nb = nullptr,
@@ -1191,34 +1188,27 @@ static int rowwise_block(const double *a, uint32_t r1, const double *b, uint32_t
   const uint32_t rows_per_launch = 65535u * TJ;  // m2 rows ride on grid.y
   for (uint32_t j0 = 0; j0 < r2; j0 += rows_per_launch) {
     const uint32_t nr = std::min(rows_per_launch, r2 - j0);
-    if (tall && TJ <= 128 && !(ctx().tune_dbg & 1024))  // (1024: the 256-row staging with two wavefronts a SIMD, for A/B)
-      distance_rowwise_kernel<KIND, false, 8, 128><<<dim3(div_up(r1, w), div_up(nr, TJ)), dim3(256), 0, st>>>(
-          a, w, r1, b + (uint64_t)j0 * n_dims, nr, n_dims, metric, p, out + (uint64_t)j0 * r1, n_cg, n_rg, 0, na, nb ? nb + j0 : nullptr, gate);
-    else if (tall)
-      distance_rowwise_kernel<KIND, false, 8><<<dim3(div_up(r1, w), div_up(nr, TJ)), dim3(256), 0, st>>>(
-          a, w, r1, b + (uint64_t)j0 * n_dims, nr, n_dims, metric, p, out + (uint64_t)j0 * r1, n_cg, n_rg, 0, na, nb ? nb + j0 : nullptr, gate);
-    else
-      distance_rowwise_kernel<KIND><<<dim3(div_up(r1, w), div_up(nr, TJ)), dim3(256), 0, st>>>(
-          a, w, r1, b + (uint64_t)j0 * n_dims, nr, n_dims, metric, p, out + (uint64_t)j0 * r1, n_cg, n_rg, 0, na, nb ? nb + j0 : nullptr, gate);
+#define KPOP_ROWWISE(...) \
+  distance_rowwise_kernel<KIND, __VA_ARGS__><<<dim3(div_up(r1, w), div_up(nr, TJ)), dim3(256), 0, st>>>( \
+      a, w, r1, b + (uint64_t)j0 * n_dims, nr, n_dims, metric, p, out + (uint64_t)j0 * r1, n_cg, n_rg, 0, na, nb ? nb + j0 : nullptr, gate)
+    if (tall && TJ <= 128 && !(ctx().tune_dbg & 1024)) KPOP_ROWWISE(false, 8, 128);  // (1024: the 256-row staging with two wavefronts a SIMD, for A/B)
+    else if (tall) KPOP_ROWWISE(false, 8);
+    else KPOP_ROWWISE(false);
+#undef KPOP_ROWWISE
     KPOP_LAUNCH_CHECK();
   }
   return 0;
 }
 
-// distance_mfma.hip: every pair's distance as a tiled contraction on the f64 matrix cores
-bool distance_mfma_applies(int kind, uint32_t r1, uint32_t r2, uint32_t n_dims);
-int launch_distance_rowwise_mfma(int kind, const double *a, uint32_t r1, const double *b, uint32_t r2, uint32_t n_dims, const double *metric, double p, double *out,
-                                 hipStream_t st, const double *n1, const double *n2, const double *s1, const double *s2);
-
-// class_set.hip: many rows against a small set of classes, a row a lane
-bool class_set_applies(int kind, uint32_t r1, uint32_t r2, uint32_t n_dims, uint64_t room_doubles);
-int launch_class_set_distance(int kind, const double *m1, uint32_t r1, const double *norms1, double *n1_out, const double *m2, uint32_t r2, double *n2,
-                              uint32_t n_dims, const double *metric, double p, bool divide, double *room, double *out, hipStream_t st);
-
 template <int KIND>
-static int rowwise_impl(const double *m1, uint32_t r1, const double *m2, uint32_t r2, uint32_t n_dims,
-                        const double *metric, double p, int normalize, void *work, double *out, hipStream_t st,
-                        const double *norms1 = nullptr, kpop_refset *prep = nullptr) {
+static int rowwise_impl(const DistOperands &o, double *out, const double *norms1 = nullptr) {
+  const double *m1 = o.m1, *m2 = o.m2, *metric = o.metric;
+  const uint32_t r1 = o.r1, r2 = o.r2, n_dims = o.n_dims;
+  const double p = o.p;
+  const int normalize = o.normalize;
+  void *work = o.work;
+  hipStream_t st = o.st;
+  kpop_refset *prep = o.prep;
   // prep: the first operand is a resident set (refset.h) -- what it holds is not computed again, everything else runs as without it
   if (prep && normalize) KPOP_TRY(prep->prepared(st));
   if (n_dims >= kLongD) {  // spectral distances: a few rows over millions of k-mers
@@ -1263,7 +1253,7 @@ static int rowwise_impl(const double *m1, uint32_t r1, const double *m2, uint32_
     // (the room of the operands' copies, DistWork::a and ::b, which this path does not otherwise use; a set's workspace has ::b alone)
     const uint64_t room = work ? ((uint64_t)r2 + (prep ? 0u : r1)) * n_dims : 0;
     if (class_set_applies(KIND, r1, r2, n_dims, room) && !(!normalize && distance_mfma_applies(KIND, r1, r2, n_dims))) {
-      DistWork w = carve(work, r1, r2, n_dims, prep);
+      DistWork w = carve(o);
       if (prep && normalize) norms1 = prep->n1;
       return launch_class_set_distance(KIND, m1, r1, norms1, prep ? nullptr : w.n1, m2, r2, w.n2, n_dims, metric, p, normalize != 0, prep ? w.b : w.a, out, st);
     }
@@ -1279,66 +1269,22 @@ static int rowwise_impl(const double *m1, uint32_t r1, const double *m2, uint32_
       if (!normalize) return launch_distance_rowwise_mfma(KIND, m1, r1, m2, r2, n_dims, metric, p, out, st, nullptr, nullptr, nullptr, nullptr);
       // (the norms' pass hands over the rows' sums of squares as well -- the same sums before their scale: the larger operand is read ONCE
       // before the contraction; they go where the normalised copies used to)
-      DistWork w = carve(work, r1, r2, n_dims, prep);
+      DistWork w = carve(o);
       KPOP_TRY(launch_row_norms_pair<KIND>(prep ? nullptr : m1, r1, w.n1, nullptr, m2, r2, w.n2, nullptr, n_dims, metric, p, st, w.a, w.b));
       if (prep) return launch_distance_rowwise_mfma(KIND, m1, r1, m2, r2, n_dims, metric, p, out, st, prep->n1, w.n2, prep->s_raw, w.b);
       return launch_distance_rowwise_mfma(KIND, m1, r1, m2, r2, n_dims, metric, p, out, st, norms1 ? norms1 : w.n1, w.n2, w.a, w.b);
     }
     const double *a, *b;
-    KPOP_TRY(prepare_operands<KIND>(m1, r1, m2, r2, n_dims, metric, p, normalize, work, &a, &b, st, prep));
+    KPOP_TRY(prepare_operands<KIND>(o, &a, &b));
     return rowwise_block<KIND>(a, r1, b, r2, n_dims, metric, p, out, st);
   }
   // norms only; the rowwise kernel divides as it stages the rows
-  DistWork w = carve(work, r1, r2, n_dims, prep);
+  DistWork w = carve(o);
   if (prep) norms1 = prep->n1;
   // (a caller that keeps the first operand brings its norms along: kpop_dev_distance_rowwise_norms, or a resident set)
   KPOP_TRY(launch_row_norms_pair<KIND>((r1 && !norms1) ? m1 : nullptr, r1, w.n1, nullptr, r2 ? m2 : nullptr, r2, w.n2, nullptr, n_dims, metric, p, st));
   return rowwise_block<KIND>(m1, r1, m2, r2, n_dims, metric, p, out, st, norms1 ? norms1 : w.n1, w.n2);
 }
-
-// summary_large.hip
-int launch_summary_large(const double *rows, uint32_t n_rows, uint32_t r1, uint32_t row0, uint32_t keep_at_most,
-                         uint32_t max_neighbours, double *out_stats, uint32_t *out_n, uint32_t *out_idx,
-                         double *out_dist, double *out_z, hipStream_t st, void *scratch, SummaryLists *lists = nullptr, bool plain_rows = false,
-                         const double *srow = nullptr, uint32_t srow_n = 0);
-uint64_t summary_large_scratch_bytes(uint32_t n_rows, uint32_t r1);
-bool summary_fused_applies(uint32_t r1, uint32_t keep_at_most);
-uint32_t summary_fused_sample_rows(uint32_t r1);
-uint64_t summary_fused_scratch_bytes(uint32_t n_rows, uint32_t r1);
-uint64_t summary_select_scratch_bytes(uint32_t n_rows, uint32_t r1);
-int launch_sample_gather(const double *a, uint32_t r1, uint32_t n_dims, uint32_t s, double *out, hipStream_t st);
-int launch_summary_fused(int kind, const double *a, uint32_t r1, const double *b, uint32_t n_rows, uint32_t n_dims, const double *metric, double p,
-                         const double *srow, uint32_t s, uint32_t row0, uint32_t keep_at_most, uint32_t max_neighbours, double *out_stats,
-                         uint32_t *out_n, uint32_t *out_idx, double *out_dist, double *out_z, double *seg, void *scratch, hipStream_t st,
-                         const uint32_t **gate);
-// distance_mfma.hip: the large-reference summary's distances on the matrix cores, and what makes its results exact again
-bool summary_mfma_applies(int kind, uint32_t r1, uint32_t n_dims, uint32_t keep_at_most, uint32_t max_neighbours);
-uint64_t summary_mfma_scratch_bytes(uint32_t q, uint32_t r1, uint32_t n_dims);
-int launch_mfma_reference_norms(const double *a, uint32_t r1, uint32_t n_dims, const double *metric, void *scratch, uint32_t q_room, hipStream_t st,
-                                const double *na = nullptr, const double *s_raw = nullptr);
-int launch_mfma_copy_reference_norms(const void *from, void *to, uint32_t r1, uint32_t n_dims, uint32_t q_room, hipStream_t st);
-int launch_distance_rows_mfma(int kind, const double *a, uint32_t r1, const double *b, uint32_t q, uint32_t n_dims, const double *metric, double *rows,
-                              void *scratch, uint32_t q_room, hipStream_t st, bool a_raw = false, const RefScalars *ref = nullptr);
-int launch_summary_refine(int kind, const double *rows, const double *a, uint32_t r1, const double *b, uint32_t q, uint32_t n_dims, const double *metric,
-                          double p, uint32_t row0, uint32_t keep_at_most, uint32_t max_neighbours, double *out_stats, uint32_t *out_n, uint32_t *out_idx,
-                          double *out_dist, double *out_z, void *scratch, uint32_t q_room, hipStream_t st, const SummaryLists &lists, const uint32_t **gate,
-                          const void **row_counts, const double *na = nullptr, const RefScalars *ref = nullptr);
-int launch_summary_flagged_rows(const double *rows, uint32_t n_rows, uint32_t r1, uint32_t row0, uint32_t keep_at_most, uint32_t max_neighbours,
-                                double *out_stats, uint32_t *out_n, uint32_t *out_idx, double *out_dist, double *out_z, const void *flags, hipStream_t st);
-// ... the same without distance rows: the summary's pass inside the contraction (summary_large.hip / distance_mfma.hip)
-bool summary_select_mfma_applies(uint32_t r1, uint32_t keep_at_most);
-int launch_mfma_query_prep(const double *b, uint32_t q, uint32_t r1, uint32_t n_dims, const double *metric, void *scratch, uint32_t q_room, hipStream_t st);
-int launch_rows_mfma_against(int kind, const double *as, const double *sas, uint32_t s, uint32_t q, uint32_t n_dims, double *rows, void *scratch, uint32_t q_room,
-                             uint32_t r1, hipStream_t st, const double *ias = nullptr);
-int launch_mfma_sample_scalars(const void *scratch, uint32_t q_room, uint32_t r1, uint32_t n_dims, uint32_t s, double *sas, double *ias, hipStream_t st);
-int launch_row_sumsq(const double *x, uint32_t rows, uint32_t n_dims, const double *metric, double *out, hipStream_t st);
-int launch_summary_fused_mfma(int kind, const double *a, uint32_t r1, uint32_t n_rows, uint32_t n_dims, const double *srow, uint32_t s, uint32_t row0,
-                              uint32_t keep_at_most, uint32_t max_neighbours, double *out_stats, uint32_t *out_n, uint32_t *out_idx, double *out_dist,
-                              double *out_z, double *seg, uint32_t *seg_i, void *scratch, const void *mscratch, uint32_t q_room, hipStream_t st,
-                              SummaryLists *lists, const RefScalars *ref = nullptr);
-int launch_summary_failed_rows(const double *rows, uint32_t n_rows, uint32_t r1, uint32_t row0, uint32_t keep_at_most, uint32_t max_neighbours,
-                               double *out_stats, uint32_t *out_n, uint32_t *out_idx, double *out_dist, double *out_z, void *scratch,
-                               hipStream_t st);
 
 // kpop_tune("summary_audit", 1): the rows a chunk leaves to the exact fall-back are counted (a synchronisation and a 4-byte copy a chunk:
 // for tests and probes -- a fall-back that runs when it should not costs 4 ms a chunk and changes no result, so nothing else shows it)
@@ -1358,19 +1304,21 @@ extern "C" int kpop_debug_summary_fallbacks(uint64_t *rows) {
   return KPOP_OK;
 }
 
-// r1 > kSummaryMaxR1: query rows in chunks, distance rows of a chunk in the library workspace
+// r1 > kSummaryMaxR1: query rows in chunks, distance rows of a chunk in the library workspace (its layouts: summary_layout.h)
 template <int KIND>
-static int summary_large_impl(const double *m1, uint32_t r1, const double *m2, uint32_t r2, uint32_t n_dims,
-                              const double *metric, double p, int normalize, uint32_t keep_at_most,
-                              uint32_t max_neighbours, void *work, double *out_stats, uint32_t *out_n,
-                              uint32_t *out_idx, double *out_dist, double *out_z, hipStream_t st, kpop_refset *prep = nullptr) {
+static int summary_large_impl(const DistOperands &o, const SummaryOut &out) {
   // prep: the reference rows are a resident set (refset.h); its norms, scalars, copy and sample are read, not made again -- the same
   // kernels made them, over the same rows
+  const double *m1 = o.m1, *m2 = o.m2, *metric = o.metric;
+  const uint32_t r1 = o.r1, r2 = o.r2, n_dims = o.n_dims;
+  const double p = o.p;
+  hipStream_t st = o.st;
+  kpop_refset *prep = o.prep;
   const double *a, *b;
   const uint64_t budget = 4096ull << 20;
-  if (prep && normalize) KPOP_TRY(prep->prepared(st));
-  const bool mfma = summary_mfma_applies(KIND, r1, n_dims, keep_at_most, max_neighbours);
-  const bool mfma_select = mfma && ctx().tune_summary_mfma == 2 && n_dims <= 128 && summary_select_mfma_applies(r1, keep_at_most);
+  if (prep && o.normalize) KPOP_TRY(prep->prepared(st));
+  const bool mfma = summary_mfma_applies(KIND, r1, n_dims, out.keep_at_most, out.max_neighbours);
+  const bool select = mfma && ctx().tune_summary_mfma == 2 && n_dims <= 128 && summary_select_mfma_applies(r1, out.keep_at_most);
   // The matrix-core path (its default form) takes the REFERENCE set as it is: no normalised copy of it is made (8.5 GB read and written
   // for 650,000 x 1,635, a quarter of a 256-row call) -- the norms' pass keeps the rows' sums of squares, a dot product is scaled by the
   // norm's reciprocal where it comes out, the exact chains of the refinement and of the fall-back divide element by element as the copy
@@ -1378,8 +1326,8 @@ static int summary_large_impl(const double *m1, uint32_t r1, const double *m2, u
   const double *na = nullptr, *s_raw = nullptr;  // the reference rows' norms and raw sums of squares when `a` is NOT divided
   RefScalars ref_store;
   const RefScalars *ref = nullptr;  // the reference rows' scalars of the matrix-core routes, when a set holds them
-  if (mfma && !mfma_select && normalize && ctx().tune_summary_rawref) {
-    DistWork w = carve(work, r1, r2, n_dims, prep);
+  if (mfma && !select && o.normalize && ctx().tune_summary_rawref) {
+    DistWork w = carve(o);
     KPOP_TRY(launch_row_norms_pair<KIND>(prep ? nullptr : m1, r1, w.n1, nullptr, m2, r2, w.n2, w.b, n_dims, metric, p, st, w.a, nullptr));
     a = m1;
     b = w.b;
@@ -1390,7 +1338,7 @@ static int summary_large_impl(const double *m1, uint32_t r1, const double *m2, u
       ref = &ref_store;
     }
   } else {
-    KPOP_TRY(prepare_operands<KIND>(m1, r1, m2, r2, n_dims, metric, p, normalize, work, &a, &b, st, prep));
+    KPOP_TRY(prepare_operands<KIND>(o, &a, &b));
     if (prep && mfma) {  // sums of squares of the operand the contraction reads (row_sumsq_kernel's own arithmetic)
       KPOP_TRY(prep->scalars_of(a, st, &ref_store));
       ref = &ref_store;
@@ -1400,156 +1348,90 @@ static int summary_large_impl(const double *m1, uint32_t r1, const double *m2, u
     // the distances on the matrix cores, approximately, to LOCATE what the summary reports; what is reported is recomputed with the
     // reference's chain (distance_mfma.hip).  Rows the refinement cannot vouch for: exact distance rows and the one-block-per-row
     // kernel over them, both launched whatever happened and both returning at once when nothing was flagged.
-    // Up to 128 dimensions and under kpop_tune("summary_mfma", 2) (not the default: measured slower, common.h) no approximate row is WRITTEN either: thresholds from the
+    // Up to 128 dimensions and under kpop_tune("summary_mfma", 2) (`select`; not the default: measured slower, common.h) no approximate row is WRITTEN either: thresholds from the
     // distances to a sample of the reference rows, then ONE kernel that classifies every distance in the accumulators' registers
     // (summary_select_mfma_kernel); beyond, and under kpop_tune("summary_mfma", 1), round 5's path: rows, then the summary's pass over them.
-    const bool select = mfma_select;
+    // The brackets and bands of that pass from the query rows' distances to a SAMPLE OF THE REFERENCE ROWS (even spacing), whatever the layout of the
+    // database (launch_summary_large); kpop_tune("summary_sample", 0): from runs of the distance rows, as until late in round 6
+    const bool row_sample = !select && ctx().tune_summary_sample == 1;
+    // (beyond 128 dimensions half the sample: its contraction is s / r1 of the main one -- a tenth for 650,000 rows -- while the candidates its
+    // wider brackets add, 12 -> 17 % of a row, cost little beside a contraction of 1,635 dimensions)
+    const uint32_t s_rows = !(select || row_sample) ? 0u : std::min(row_sample && n_dims > 128 ? 32768u : ~0u, summary_fused_sample_rows(r1));
     uint32_t chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(r2, 2 * budget / ((uint64_t)r1 * 8)));  // (1,024 rows against a million)
     if (chunk > 128) chunk = chunk / 128 * 128;
     // TWO LANES (kpop_tune("summary_lanes", 2); 512 query rows and more): batches of 256 rows alternately on the caller's stream and on one of
     // the library's own, a lane's contraction waiting for the other lane's.  Meant to run a batch's sample / finish / refinement kernels (one
     // block a row, a block a CU, chains of dependent steps) under the next batch's contraction and pass; measured level with one batch after
     // the other (common.h), which stays the default.  Results do not depend on the lanes: every row is its own computation.
-    const bool two_lanes = !select && ctx().tune_summary_lanes == 2 && r2 >= 512 && chunk >= 512;
-    if (two_lanes) {
-      chunk = 256;
-      const uint64_t row_bytes = ((uint64_t)chunk * r1 * 8 + 255) & ~255ull;
-      const uint64_t sum_bytes = (summary_large_scratch_bytes(chunk, r1) + 511) & ~255ull, m_bytes = (summary_mfma_scratch_bytes(chunk, r1, n_dims) + 511) & ~255ull;
-      const bool row_sample2 = ctx().tune_summary_sample == 1;  // (the brackets from a sample of the reference rows: see the one-lane form below)
-      const uint32_t s_rows2 = row_sample2 ? (n_dims > 128 ? std::min(32768u, summary_fused_sample_rows(r1)) : summary_fused_sample_rows(r1)) : 0u;
-      const uint64_t srow2_bytes = ((uint64_t)chunk * s_rows2 * 8 + 255) & ~255ull, as2_bytes = ((uint64_t)s_rows2 * n_dims * 8 + 255) & ~255ull,
-                     sas2_bytes = ((uint64_t)s_rows2 * 8 + 255) & ~255ull;
-      const uint64_t lane_bytes = row_bytes + sum_bytes + m_bytes + srow2_bytes + 256;
-      void *ws = nullptr;
-      KPOP_TRY(ctx().ws_for(st).ensure(2 * lane_bytes + as2_bytes + 2 * sas2_bytes + 512, &ws));
-      Context::AuxLane *aux = nullptr;
-      KPOP_TRY(ctx().aux_for(st, &aux));
-      char *wp = reinterpret_cast<char *>(ws);
-      struct Lane {
-        hipStream_t s;
-        double *rows;
-        void *scratch, *mscratch;
-        double *srow;
-      } lane[2];
-      for (int l = 0; l < 2; ++l) {
-        char *base = wp + (uint64_t)l * lane_bytes;
-        lane[l] = Lane{l ? aux->stream : st, reinterpret_cast<double *>(base), base + row_bytes, base + row_bytes + sum_bytes,
-                       reinterpret_cast<double *>(base + row_bytes + sum_bytes + m_bytes)};
-      }
-      double *a_s2 = reinterpret_cast<double *>(wp + 2 * lane_bytes), *sa_s2 = reinterpret_cast<double *>(wp + 2 * lane_bytes + as2_bytes),
-             *ia_s2 = na ? reinterpret_cast<double *>(wp + 2 * lane_bytes + as2_bytes + sas2_bytes) : nullptr;
-      const double *as2 = a_s2, *sas2 = sa_s2, *ias2 = ia_s2;
-      if (ref) {  // (both lanes read the set's scalars and its sample: nothing to make, nothing to copy)
-        if (row_sample2) KPOP_TRY(prep->sample(a, s_rows2, kSampleGathered, ref, st, &as2, &sas2, &ias2));
-      } else {
-        KPOP_TRY(launch_mfma_reference_norms(a, r1, n_dims, metric, lane[0].mscratch, chunk, st, na, s_raw));
-        KPOP_TRY(launch_mfma_copy_reference_norms(lane[0].mscratch, lane[1].mscratch, r1, n_dims, chunk, st));
-        if (row_sample2) {
-          KPOP_TRY(launch_sample_gather(a, r1, n_dims, s_rows2, a_s2, st));
-          KPOP_TRY(launch_mfma_sample_scalars(lane[0].mscratch, chunk, r1, n_dims, s_rows2, sa_s2, ia_s2, st));
-        }
-      }
-      KPOP_HIP(hipEventRecord(aux->fork, st));
-      KPOP_HIP(hipStreamWaitEvent(aux->stream, aux->fork, 0));
-      int rc = 0;
-      uint32_t bi = 0;
-      for (uint32_t q0 = 0; q0 < r2 && !rc; q0 += chunk, ++bi) {
-        const Lane &L = lane[bi & 1u];
-        const uint32_t q = std::min(chunk, r2 - q0);
-        const double *bq = b + (uint64_t)q0 * n_dims;
-        SummaryLists lists;
-        const uint32_t *gate = nullptr;
-        const void *flags = nullptr;
-        auto batch = [&]() -> int {
-          if (bi > 0) KPOP_HIP(hipStreamWaitEvent(L.s, aux->step[(bi - 1) & 1u], 0));  // this batch's contraction after the one before it
-          KPOP_TRY(launch_distance_rows_mfma(KIND, a, r1, bq, q, n_dims, metric, L.rows, L.mscratch, chunk, L.s, na != nullptr, ref));
-          KPOP_HIP(hipEventRecord(aux->step[bi & 1u], L.s));
-          if (row_sample2) KPOP_TRY(launch_rows_mfma_against(KIND, as2, sas2, s_rows2, q, n_dims, L.srow, L.mscratch, chunk, r1, L.s, ias2));
-          KPOP_TRY(launch_summary_large(L.rows, q, r1, q0, keep_at_most, max_neighbours, out_stats, out_n, out_idx, out_dist, out_z, L.s, L.scratch, &lists, true,
-                                        row_sample2 ? L.srow : nullptr, s_rows2));
-          KPOP_TRY(launch_summary_refine(KIND, L.rows, a, r1, bq, q, n_dims, metric, p, q0, keep_at_most, max_neighbours, out_stats, out_n, out_idx, out_dist, out_z,
-                                         L.mscratch, chunk, L.s, lists, &gate, &flags, na, ref));
-          KPOP_TRY(audit_fallback(gate, L.s));
-          KPOP_TRY(audit_fallback(lists.n_failed, L.s));
-          KPOP_TRY(rowwise_block<KIND>(a, r1, bq, q, n_dims, metric, p, L.rows, L.s, na, nullptr, gate));  // (na: the kernel divides the reference rows as it stages them)
-          KPOP_TRY(launch_summary_flagged_rows(L.rows, q, r1, q0, keep_at_most, max_neighbours, out_stats, out_n, out_idx, out_dist, out_z, flags, L.s));
-          return 0;
-        };
-        rc = batch();
-      }
-      // the join, whatever happened: the caller's stream goes on only when the library's own has drained
-      const hipError_t e1 = hipEventRecord(aux->join, aux->stream), e2 = hipStreamWaitEvent(st, aux->join, 0);
-      if (rc) return rc;
-      if (e1 != hipSuccess || e2 != hipSuccess) KPOP_FAIL(KPOP_ERR_HIP, "kpop_dev_distance_summary: joining the second lane: %s", hipGetErrorString(e1 != hipSuccess ? e1 : e2));
-      return 0;
-    }
+    const uint32_t n_lanes = (!select && ctx().tune_summary_lanes == 2 && r2 >= 512 && chunk >= 512) ? 2 : 1;
+    if (n_lanes == 2) chunk = 256;
+    const MfmaShape shape{chunk, r1, n_dims, s_rows, n_lanes, select,
+                          std::max(summary_large_scratch_bytes(chunk, r1), select ? summary_select_scratch_bytes(chunk, r1) : 0),
+                          summary_mfma_scratch_bytes(chunk, r1, n_dims)};
     void *ws = nullptr;
-    // the brackets and bands from the query rows' distances to a SAMPLE OF THE REFERENCE ROWS (even spacing), whatever the layout of the database
-    // (launch_summary_large); kpop_tune("summary_sample", 0): from runs of the distance rows, as until late in round 6
-    const bool row_sample = !select && ctx().tune_summary_sample == 1;
-    // (beyond 128 dimensions half the sample: its contraction is s / r1 of the main one -- a tenth for 650,000 rows -- while the candidates its
-    // wider brackets add, 12 -> 17 % of a row, cost little beside a contraction of 1,635 dimensions)
-    const uint32_t s_rows = select ? summary_fused_sample_rows(r1) : row_sample ? (n_dims > 128 ? std::min(32768u, summary_fused_sample_rows(r1)) : summary_fused_sample_rows(r1)) : 0;
-    const uint64_t r1_seg = select ? (((uint64_t)r1 + 2047) & ~2047ull) : r1;  // (the select kernel's segments: a row rounded up to whole stripes of 2,048)
-    const uint64_t row_bytes = ((uint64_t)chunk * r1_seg * 8 + 255) & ~255ull, segi_bytes = select ? (((uint64_t)chunk * r1_seg * 4 + 255) & ~255ull) : 0;
-    const uint64_t sum_bytes = (std::max(summary_large_scratch_bytes(chunk, r1), select ? summary_select_scratch_bytes(chunk, r1) : 0) + 511) & ~255ull;
-    const uint64_t m_bytes = (summary_mfma_scratch_bytes(chunk, r1, n_dims) + 511) & ~255ull;
-    const uint64_t as_bytes = ((uint64_t)s_rows * n_dims * 8 + 255) & ~255ull, sas_bytes = 2 * (((uint64_t)s_rows * 8 + 255) & ~255ull),  // (sums of squares, reciprocals)
-                   srow_bytes = ((uint64_t)chunk * s_rows * 8 + 255) & ~255ull;
-    KPOP_TRY(ctx().ws_for(st).ensure(row_bytes + segi_bytes + sum_bytes + m_bytes + as_bytes + sas_bytes + srow_bytes + 512, &ws));
-    char *wp = reinterpret_cast<char *>(ws);
-    double *rows = reinterpret_cast<double *>(wp);
-    uint32_t *seg_i = reinterpret_cast<uint32_t *>(wp + row_bytes);
-    void *scratch = wp + row_bytes + segi_bytes, *mscratch = wp + row_bytes + segi_bytes + sum_bytes;
-    double *a_s = reinterpret_cast<double *>(wp + row_bytes + segi_bytes + sum_bytes + m_bytes);
-    double *sa_s = reinterpret_cast<double *>(wp + row_bytes + segi_bytes + sum_bytes + m_bytes + as_bytes);
-    double *srow = reinterpret_cast<double *>(wp + row_bytes + segi_bytes + sum_bytes + m_bytes + as_bytes + sas_bytes);
-    if (!ref) KPOP_TRY(launch_mfma_reference_norms(a, r1, n_dims, metric, mscratch, chunk, st, na, s_raw));
-    const double *ia_s = nullptr;
-    if (ref && (row_sample || select)) {  // (a set keeps its sample and the sample's scalars: once, not once a call)
-      const double *as_set = nullptr, *sas_set = nullptr;
-      KPOP_TRY(prep->sample(a, s_rows, select ? kSampleSumsq : kSampleGathered, ref, st, &as_set, &sas_set, &ia_s));
-      a_s = const_cast<double *>(as_set);
-      sa_s = const_cast<double *>(sas_set);
-    } else if (row_sample) {  // the sample of the reference rows, its sums of squares and (the set taken as it is) its norms' reciprocals: once a call
-      KPOP_TRY(launch_sample_gather(a, r1, n_dims, s_rows, a_s, st));
-      double *ia_w = na ? sa_s + (sas_bytes / 16) : nullptr;
-      KPOP_TRY(launch_mfma_sample_scalars(mscratch, chunk, r1, n_dims, s_rows, sa_s, ia_w, st));
-      ia_s = ia_w;
-    } else if (select) {  // the sample of the reference rows and its norms: once a call
-      KPOP_TRY(launch_sample_gather(a, r1, n_dims, s_rows, a_s, st));
-      KPOP_TRY(launch_row_sumsq(a_s, s_rows, n_dims, metric, sa_s, st));
+    KPOP_TRY(ctx().ws_for(st).ensure(carve_summary_mfma(nullptr, shape).bytes, &ws));
+    const MfmaWork W = carve_summary_mfma(ws, shape);
+    Context::AuxLane *aux = nullptr;  // (the second lane's stream and the events between the two)
+    if (n_lanes == 2) KPOP_TRY(ctx().aux_for(st, &aux));
+    const hipStream_t lane_st[2] = {st, aux ? aux->stream : st};
+    // once a call: the reference rows' scalars (a set holds its own: both lanes read them, nothing to make, nothing to copy) ...
+    if (!ref) {
+      KPOP_TRY(launch_mfma_reference_norms(a, r1, n_dims, metric, W.lane[0].mscratch, chunk, st, na, s_raw));
+      if (n_lanes == 2) KPOP_TRY(launch_mfma_copy_reference_norms(W.lane[0].mscratch, W.lane[1].mscratch, r1, n_dims, chunk, st));
     }
-    for (uint32_t q0 = 0; q0 < r2; q0 += chunk) {
-      const uint32_t q = std::min(chunk, r2 - q0);
+    // ... and the sample of the reference rows with its sums of squares and (the set taken as it is) its norms' reciprocals
+    const double *a_s = W.a_s, *sa_s = W.sa_s, *ia_s = na ? W.ia_s : nullptr;
+    if (ref && s_rows) {  // (a set keeps its sample and the sample's scalars: once, not once a call)
+      KPOP_TRY(prep->sample(a, s_rows, select ? kSampleSumsq : kSampleGathered, ref, st, &a_s, &sa_s, &ia_s));
+    } else if (s_rows) {
+      KPOP_TRY(launch_sample_gather(a, r1, n_dims, s_rows, W.a_s, st));
+      if (select) KPOP_TRY(launch_row_sumsq(W.a_s, s_rows, n_dims, metric, W.sa_s, st));
+      else KPOP_TRY(launch_mfma_sample_scalars(W.lane[0].mscratch, chunk, r1, n_dims, s_rows, W.sa_s, na ? W.ia_s : nullptr, st));
+    }
+    // a batch of q query rows from q0 on lane l; after / done (two lanes): its contraction waits for `after`, `done` is recorded behind it
+    auto mfma_batch = [&](uint32_t l, uint32_t q0, uint32_t q, hipEvent_t after, hipEvent_t done) -> int {
+      const MfmaWork::Lane &L = W.lane[l];
+      const hipStream_t ls = lane_st[l];
       const double *bq = b + (uint64_t)q0 * n_dims;
       SummaryLists lists;
       const uint32_t *gate = nullptr;
       const void *flags = nullptr;
+      if (after) KPOP_HIP(hipStreamWaitEvent(ls, after, 0));  // this batch's contraction after the one before it
       if (select) {
-        KPOP_TRY(launch_mfma_query_prep(bq, q, r1, n_dims, metric, mscratch, chunk, st));
-        KPOP_TRY(launch_rows_mfma_against(KIND, a_s, sa_s, s_rows, q, n_dims, srow, mscratch, chunk, r1, st));
-        KPOP_TRY(launch_summary_fused_mfma(KIND, a, r1, q, n_dims, srow, s_rows, q0, keep_at_most, max_neighbours, out_stats, out_n, out_idx, out_dist, out_z, rows,
-                                           seg_i, scratch, mscratch, chunk, st, &lists, ref));
-        KPOP_TRY(launch_summary_refine(KIND, nullptr, a, r1, bq, q, n_dims, metric, p, q0, keep_at_most, max_neighbours, out_stats, out_n, out_idx, out_dist,
-                                       out_z, mscratch, chunk, st, lists, &gate, &flags, nullptr, ref));
-        KPOP_TRY(audit_fallback(gate, st));
+        KPOP_TRY(launch_mfma_query_prep(bq, q, r1, n_dims, metric, L.mscratch, chunk, ls));
+        KPOP_TRY(launch_rows_mfma_against(KIND, a_s, sa_s, s_rows, q, n_dims, L.srow, L.mscratch, chunk, r1, ls));
+        KPOP_TRY(launch_summary_fused_mfma(KIND, a, r1, q, n_dims, L.srow, s_rows, q0, out, L.rows, L.seg_i, L.scratch, L.mscratch, chunk, ls, &lists, ref));
+        KPOP_TRY(launch_summary_refine(KIND, nullptr, a, r1, bq, q, n_dims, metric, p, q0, out, L.mscratch, chunk, ls, lists, &gate, &flags, nullptr, ref));
+        KPOP_TRY(audit_fallback(gate, ls));
       } else {
-        KPOP_TRY(launch_distance_rows_mfma(KIND, a, r1, bq, q, n_dims, metric, rows, mscratch, chunk, st, na != nullptr, ref));
-        if (row_sample) KPOP_TRY(launch_rows_mfma_against(KIND, a_s, sa_s, s_rows, q, n_dims, srow, mscratch, chunk, r1, st, ia_s));  // (the chunk's query rows are prepared: the call above)
-        KPOP_TRY(launch_summary_large(rows, q, r1, q0, keep_at_most, max_neighbours, out_stats, out_n, out_idx, out_dist, out_z, st, scratch, &lists, true,
-                                      row_sample ? srow : nullptr, s_rows));
-        KPOP_TRY(launch_summary_refine(KIND, rows, a, r1, bq, q, n_dims, metric, p, q0, keep_at_most, max_neighbours, out_stats, out_n, out_idx, out_dist,
-                                       out_z, mscratch, chunk, st, lists, &gate, &flags, na, ref));
-        KPOP_TRY(audit_fallback(gate, st));
-        KPOP_TRY(audit_fallback(lists.n_failed, st));  // (rows whose sample-based brackets missed: the ten-pass kernel's)
+        KPOP_TRY(launch_distance_rows_mfma(KIND, a, r1, bq, q, n_dims, metric, L.rows, L.mscratch, chunk, ls, na != nullptr, ref));
+        if (done) KPOP_HIP(hipEventRecord(done, ls));
+        if (row_sample) KPOP_TRY(launch_rows_mfma_against(KIND, a_s, sa_s, s_rows, q, n_dims, L.srow, L.mscratch, chunk, r1, ls, ia_s));  // (the batch's query rows are prepared: the call above)
+        KPOP_TRY(launch_summary_large(L.rows, q, r1, q0, out, ls, L.scratch, &lists, true, row_sample ? L.srow : nullptr, s_rows));
+        KPOP_TRY(launch_summary_refine(KIND, L.rows, a, r1, bq, q, n_dims, metric, p, q0, out, L.mscratch, chunk, ls, lists, &gate, &flags, na, ref));
+        KPOP_TRY(audit_fallback(gate, ls));
+        KPOP_TRY(audit_fallback(lists.n_failed, ls));  // (rows whose sample-based brackets missed: the ten-pass kernel's)
       }
-      KPOP_TRY(rowwise_block<KIND>(a, r1, bq, q, n_dims, metric, p, rows, st, na, nullptr, gate));  // (na: the kernel divides the reference rows as it stages them)
-      KPOP_TRY(launch_summary_flagged_rows(rows, q, r1, q0, keep_at_most, max_neighbours, out_stats, out_n, out_idx, out_dist, out_z, flags, st));
+      KPOP_TRY(rowwise_block<KIND>(a, r1, bq, q, n_dims, metric, p, L.rows, ls, na, nullptr, gate));  // (na: the kernel divides the reference rows as it stages them)
+      KPOP_TRY(launch_summary_flagged_rows(L.rows, q, r1, q0, out, flags, ls));
+      return 0;
+    };
+    if (aux) {
+      KPOP_HIP(hipEventRecord(aux->fork, st));
+      KPOP_HIP(hipStreamWaitEvent(aux->stream, aux->fork, 0));
     }
-    return 0;
+    int rc = 0;
+    uint32_t bi = 0;
+    for (uint32_t q0 = 0; q0 < r2 && !rc; q0 += chunk, ++bi)
+      rc = mfma_batch(bi % n_lanes, q0, std::min(chunk, r2 - q0), aux && bi ? aux->step[(bi - 1) & 1u] : nullptr, aux ? aux->step[bi & 1u] : nullptr);
+    if (aux) {  // the join, whatever happened: the caller's stream goes on only when the library's own has drained
+      const hipError_t e1 = hipEventRecord(aux->join, aux->stream), e2 = hipStreamWaitEvent(st, aux->join, 0);
+      if (!rc && (e1 != hipSuccess || e2 != hipSuccess))
+        KPOP_FAIL(KPOP_ERR_HIP, "kpop_dev_distance_summary: joining the second lane: %s", hipGetErrorString(e1 != hipSuccess ? e1 : e2));
+    }
+    return rc;
   }
-  if (summary_fused_applies(r1, keep_at_most)) {
+  if (summary_fused_applies(r1, out.keep_at_most)) {
     // 131,072 reference rows and more: no distance rows at all (summary_large.hip, "second step").  The workspace holds, per
     // chunk of query rows, the candidates' segments (the same room distance rows would take, mostly untouched), the sample of
     // the first operand and the distances to it, and the lists.
@@ -1557,77 +1439,54 @@ static int summary_large_impl(const double *m1, uint32_t r1, const double *m2, u
     const uint64_t fixed = (((uint64_t)s * n_dims * 8 + 255) & ~255ull) + (1u << 20);
     uint32_t chunk = r2;
     while (chunk > 1 && fixed + (uint64_t)chunk * ((uint64_t)r1 + s) * 8 + summary_fused_scratch_bytes(chunk, r1) > budget) chunk = chunk > 256 ? (chunk - 1) / 256 * 256 : chunk / 2;
-    const uint64_t bytes_seg = ((uint64_t)chunk * r1 * 8 + 255) & ~255ull, bytes_as = ((uint64_t)s * n_dims * 8 + 255) & ~255ull,
-                   bytes_srow = ((uint64_t)chunk * s * 8 + 255) & ~255ull;
+    const uint64_t lists_bytes = summary_fused_scratch_bytes(chunk, r1);
     void *ws = nullptr;
-    KPOP_TRY(ctx().ws_for(st).ensure(bytes_seg + bytes_as + bytes_srow + summary_fused_scratch_bytes(chunk, r1), &ws));
-    char *wp = reinterpret_cast<char *>(ws);
-    double *seg = reinterpret_cast<double *>(wp), *a_s = reinterpret_cast<double *>(wp + bytes_seg),
-           *srow = reinterpret_cast<double *>(wp + bytes_seg + bytes_as);
-    void *scratch = wp + bytes_seg + bytes_as + bytes_srow;
-    if (prep) {
-      const double *as_set = nullptr;
-      KPOP_TRY(prep->sample(a, s, kSampleRowsOnly, nullptr, st, &as_set, nullptr, nullptr));
-      a_s = const_cast<double *>(as_set);
-    } else {
-      KPOP_TRY(launch_sample_gather(a, r1, n_dims, s, a_s, st));
-    }
+    KPOP_TRY(ctx().ws_for(st).ensure(carve_summary_fused(nullptr, chunk, r1, n_dims, s, lists_bytes).bytes, &ws));
+    const FusedWork W = carve_summary_fused(ws, chunk, r1, n_dims, s, lists_bytes);
+    const double *a_s = W.a_s;
+    if (prep) KPOP_TRY(prep->sample(a, s, kSampleRowsOnly, nullptr, st, &a_s, nullptr, nullptr));
+    else KPOP_TRY(launch_sample_gather(a, r1, n_dims, s, W.a_s, st));
     for (uint32_t q0 = 0; q0 < r2; q0 += chunk) {
       const uint32_t q = std::min(chunk, r2 - q0);
       const double *bq = b + (uint64_t)q0 * n_dims;
-      KPOP_TRY(rowwise_block<KIND>(a_s, s, bq, q, n_dims, metric, p, srow, st));
+      KPOP_TRY(rowwise_block<KIND>(a_s, s, bq, q, n_dims, metric, p, W.srow, st));
       const uint32_t *gate = nullptr;
-      KPOP_TRY(launch_summary_fused(KIND, a, r1, bq, q, n_dims, metric, p, srow, s, q0, keep_at_most, max_neighbours, out_stats, out_n, out_idx,
-                                    out_dist, out_z, seg, scratch, st, &gate));
+      KPOP_TRY(launch_summary_fused(KIND, a, r1, bq, q, n_dims, metric, p, W.srow, s, q0, out, W.seg, W.scratch, st, &gate));
       KPOP_TRY(audit_fallback(gate, st));
       // the rows it flagged (a bracket that missed, a list that overflowed): their distance rows into the segments' room and the
       // one-block-per-row kernel over them -- both launched whatever happened, both return at once when nothing was flagged
-      KPOP_TRY(rowwise_block<KIND>(a, r1, bq, q, n_dims, metric, p, seg, st, nullptr, nullptr, gate));
-      KPOP_TRY(launch_summary_failed_rows(seg, q, r1, q0, keep_at_most, max_neighbours, out_stats, out_n, out_idx, out_dist, out_z, scratch, st));
+      KPOP_TRY(rowwise_block<KIND>(a, r1, bq, q, n_dims, metric, p, W.seg, st, nullptr, nullptr, gate));
+      KPOP_TRY(launch_summary_failed_rows(W.seg, q, r1, q0, out, W.scratch, st));
     }
     return 0;
   }
   // distance rows of a chunk of queries live in the library workspace: enough of them (one 1024-thread block each) to
   // put two blocks on every CU when the first operand is large
   const uint32_t chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(r2, budget / ((uint64_t)r1 * 8)));
-  void *ws = nullptr;
-  const uint64_t row_bytes = ((uint64_t)chunk * r1 * 8 + 255) & ~255ull;
   // (262,144 reference rows and more: the brackets and bands from the query rows' distances to a sample of the REFERENCE ROWS at even spacing,
   // as in the matrix-core form above -- the same chain for every pair, a sixteenth of the distances again or less; runs of the distance rows
   // speak for a few lineages of a database laid out lineage by lineage.  kpop_tune("summary_sample", 0): the runs)
   const uint32_t s_rows = (ctx().tune_summary_sample == 1 && ctx().tune_summary2 == 1 && r1 >= 262144) ? summary_fused_sample_rows(r1) : 0;
-  const uint64_t as_bytes = ((uint64_t)s_rows * n_dims * 8 + 255) & ~255ull, srow_bytes = ((uint64_t)chunk * s_rows * 8 + 255) & ~255ull;
-  const uint64_t sum_bytes = (summary_large_scratch_bytes(chunk, r1) + 511) & ~255ull;
-  KPOP_TRY(ctx().ws_for(st).ensure(row_bytes + sum_bytes + as_bytes + srow_bytes + 256, &ws));
-  double *rows = reinterpret_cast<double *>(ws);
-  void *scratch = reinterpret_cast<char *>(ws) + row_bytes;
-  double *a_s = reinterpret_cast<double *>(reinterpret_cast<char *>(ws) + row_bytes + sum_bytes);
-  double *srow = reinterpret_cast<double *>(reinterpret_cast<char *>(ws) + row_bytes + sum_bytes + as_bytes);
-  if (s_rows && prep) {
-    const double *as_set = nullptr;
-    KPOP_TRY(prep->sample(a, s_rows, kSampleRowsOnly, nullptr, st, &as_set, nullptr, nullptr));
-    a_s = const_cast<double *>(as_set);
-  } else if (s_rows) {
-    KPOP_TRY(launch_sample_gather(a, r1, n_dims, s_rows, a_s, st));
-  }
+  const uint64_t sum_bytes = summary_large_scratch_bytes(chunk, r1);
+  void *ws = nullptr;
+  KPOP_TRY(ctx().ws_for(st).ensure(carve_summary_chunked(nullptr, chunk, r1, n_dims, s_rows, sum_bytes).bytes, &ws));
+  const ChunkedWork W = carve_summary_chunked(ws, chunk, r1, n_dims, s_rows, sum_bytes);
+  const double *a_s = W.a_s;
+  if (s_rows && prep) KPOP_TRY(prep->sample(a, s_rows, kSampleRowsOnly, nullptr, st, &a_s, nullptr, nullptr));
+  else if (s_rows) KPOP_TRY(launch_sample_gather(a, r1, n_dims, s_rows, W.a_s, st));
   for (uint32_t q0 = 0; q0 < r2; q0 += chunk) {
     const uint32_t q = std::min(chunk, r2 - q0);
-    KPOP_TRY(rowwise_block<KIND>(a, r1, b + (uint64_t)q0 * n_dims, q, n_dims, metric, p, rows, st));
-    if (s_rows) KPOP_TRY(rowwise_block<KIND>(a_s, s_rows, b + (uint64_t)q0 * n_dims, q, n_dims, metric, p, srow, st));
-    KPOP_TRY(launch_summary_large(rows, q, r1, q0, keep_at_most, max_neighbours, out_stats, out_n, out_idx, out_dist,
-                                  out_z, st, scratch, nullptr, false, s_rows ? srow : nullptr, s_rows));
+    KPOP_TRY(rowwise_block<KIND>(a, r1, b + (uint64_t)q0 * n_dims, q, n_dims, metric, p, W.rows, st));
+    if (s_rows) KPOP_TRY(rowwise_block<KIND>(a_s, s_rows, b + (uint64_t)q0 * n_dims, q, n_dims, metric, p, W.srow, st));
+    KPOP_TRY(launch_summary_large(W.rows, q, r1, q0, out, st, W.scratch, nullptr, false, s_rows ? W.srow : nullptr, s_rows));
   }
   return 0;
 }
 
 template <int KIND, bool PRE>
-static int launch_summary(const double *a, uint32_t r1, const double *b, uint32_t r2, uint32_t n_dims,
-                          const double *metric, double p, uint32_t keep_at_most, uint32_t max_neighbours,
-                          double *out_stats, uint32_t *out_n, uint32_t *out_idx, double *out_dist, double *out_z,
-                          hipStream_t st, const double *nb = nullptr) {  // nb: see summary_divides_in_flight
-  if (summary_fits_wave(r1, n_dims, PRE) && ctx().tune_dbg != 4)
-    return launch_summary_wave<KIND, PRE>(a, r1, b, r2, n_dims, metric, p, keep_at_most ? keep_at_most : r1, max_neighbours, out_stats,
-                                          out_n, out_idx, out_dist, out_z, st, nb);
+static int launch_summary(const double *a, uint32_t r1, const double *b, uint32_t r2, uint32_t n_dims, const double *metric, double p,
+                          const SummaryOut &out, hipStream_t st, const double *nb = nullptr) {  // nb: see summary_divides_in_flight
+  if (summary_fits_wave(r1, n_dims, PRE) && ctx().tune_dbg != 4) return launch_summary_wave<KIND, PRE>(a, r1, b, r2, n_dims, metric, p, out, st, nb);
   uint32_t NP = 64;
   while (NP < r1) NP <<= 1;
   const size_t smem = (size_t)NP * (8 + 8 + 4);
@@ -1638,35 +1497,34 @@ static int launch_summary(const double *a, uint32_t r1, const double *b, uint32_
                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kSummaryMaxR1 * 20)));
     attr_set = true;
   }
-  const uint32_t req_len = keep_at_most ? keep_at_most : r1;  // lib/Matrix.ml:723-726,774-777
   // (a row of 4,096 slots fills the LDS of a CU by itself: 1,024 threads on its sort -- 98 -> 64 ms for 100,000 rows against
   // 4,000; below that several 256-thread blocks share a CU and more threads a block measured slower)
   const uint32_t threads = NP >= 4096 ? 1024u : 256u;
-  distance_summary_kernel<KIND, PRE><<<dim3(r2), dim3(threads), smem, st>>>(a, r1, b, r2, n_dims, metric, p, NP, req_len,
-                                                                        max_neighbours, out_stats, out_n, out_idx,
-                                                                        out_dist, out_z);
+  distance_summary_kernel<KIND, PRE><<<dim3(r2), dim3(threads), smem, st>>>(a, r1, b, r2, n_dims, metric, p, NP, out.req_len(r1), out.max_neighbours,
+                                                                        out.stats, out.n, out.idx, out.dist, out.z);
   KPOP_LAUNCH_CHECK();
   return 0;
 }
 
 template <int KIND>
-static int summary_impl(const double *m1, uint32_t r1, const double *m2, uint32_t r2, uint32_t n_dims,
-                        const double *metric, double p, int normalize, uint32_t keep_at_most, uint32_t max_neighbours,
-                        void *work, double *out_stats, uint32_t *out_n, uint32_t *out_idx, double *out_dist,
-                        double *out_z, hipStream_t st, kpop_refset *prep = nullptr) {
+static int summary_impl(const DistOperands &o, const SummaryOut &out) {
+  const double *m1 = o.m1, *m2 = o.m2, *metric = o.metric;
+  const uint32_t r1 = o.r1, r2 = o.r2, n_dims = o.n_dims;
+  const double p = o.p;
+  hipStream_t st = o.st;
+  kpop_refset *prep = o.prep;
   const double *a, *b;
-  if (prep && normalize) KPOP_TRY(prep->prepared(st));
-  if (normalize && r2 && summary_fits_wave(r1, n_dims, false) && ctx().tune_dbg != 4 && summary_batch_case(r1, n_dims, false)) {
+  if (prep && o.normalize) KPOP_TRY(prep->prepared(st));
+  if (o.normalize && r2 && summary_fits_wave(r1, n_dims, false) && ctx().tune_dbg != 4 && summary_batch_case(r1, n_dims, false)) {
     // The kernel that takes four rows of a wavefront at a time stages the second operand's rows itself: they go in as they are,
     // with their norms, and are divided on the way (the same quotients); only the few rows of the first operand get a divided copy.
-    DistWork w = carve(work, r1, r2, n_dims, prep);
+    DistWork w = carve(o);
     const double *a_div = w.a;
     if (prep) KPOP_TRY(prep->divided(st, &a_div));  // (the set's divided copy: the same quotients)
     KPOP_TRY(launch_row_norms_pair<KIND>(prep ? nullptr : m1, r1, w.n1, w.a, m2, r2, w.n2, nullptr, n_dims, metric, p, st));
-    return launch_summary<KIND, false>(a_div, r1, m2, r2, n_dims, metric, p, keep_at_most, max_neighbours, out_stats, out_n, out_idx, out_dist,
-                                       out_z, st, w.n2);
+    return launch_summary<KIND, false>(a_div, r1, m2, r2, n_dims, metric, p, out, st, w.n2);
   }
-  KPOP_TRY(prepare_operands<KIND>(m1, r1, m2, r2, n_dims, metric, p, normalize, work, &a, &b, st, prep));
+  KPOP_TRY(prepare_operands<KIND>(o, &a, &b));
   if (r1 >= 1 && r1 <= kSummaryMaxR1 && !summary_fits_wave(r1, n_dims, false) && ctx().tune_dbg != 4) {
     // A first operand that does not fit LDS (100 x 200 dimensions, 500 x 64, anything of 513..4,096 rows): the distances of
     // a chunk of second-operand rows into the workspace (the tiled kernel), then the summary over them -- one wavefront per
@@ -1679,14 +1537,11 @@ static int summary_impl(const double *m1, uint32_t r1, const double *m2, uint32_
     for (uint32_t q0 = 0; q0 < r2; q0 += chunk) {
       const uint32_t q = std::min(chunk, r2 - q0);
       KPOP_TRY(rowwise_block<KIND>(a, r1, b + (uint64_t)q0 * n_dims, q, n_dims, metric, p, rows, st));
-      KPOP_TRY((launch_summary<KIND, true>(rows, r1, nullptr, q, n_dims, metric, p, keep_at_most, max_neighbours, out_stats + (uint64_t)q0 * 4,
-                                           out_n + q0, out_idx + (uint64_t)q0 * max_neighbours, out_dist + (uint64_t)q0 * max_neighbours,
-                                           out_z + (uint64_t)q0 * max_neighbours, st)));
+      KPOP_TRY((launch_summary<KIND, true>(rows, r1, nullptr, q, n_dims, metric, p, out.from_row(q0), st)));
     }
     return 0;
   }
-  return launch_summary<KIND, false>(a, r1, b, r2, n_dims, metric, p, keep_at_most, max_neighbours, out_stats, out_n,
-                                     out_idx, out_dist, out_z, st);
+  return launch_summary<KIND, false>(a, r1, b, r2, n_dims, metric, p, out, st);
 }
 
 // out[i][c] = m[i][c] * w[c]  (Base.get_embeddings, lib/Matrix.ml:104)
@@ -1735,14 +1590,14 @@ struct LongListSource {  // where a row's distances come from
   kpop_refset *rs = nullptr;  // ... or a resident set as the first operand (kpop_refset_distance_summary)
 };
 
-static int fill_long_lists(const LongListSource &src, uint32_t r1, uint32_t r2, uint32_t max_neighbours, const double *out_stats, const uint32_t *out_n,
-                           uint32_t *out_idx, double *out_dist, double *out_z, hipStream_t st) {
+static int fill_long_lists(const LongListSource &src, uint32_t r1, uint32_t r2, const SummaryOut &out, hipStream_t st) {  // (out: host buffers, filled by the summary)
+  const uint32_t max_neighbours = out.max_neighbours;
   if (r1 <= kSummaryMaxR1 || max_neighbours <= kLargeNeighbours) return KPOP_OK;
   std::vector<uint32_t> todo;
   for (uint32_t j = 0; j < r2; ++j)
-    if (out_n[j] > kLargeNeighbours) todo.push_back(j);
+    if (out.n[j] > kLargeNeighbours) todo.push_back(j);
   if (todo.empty()) return KPOP_OK;
-  if (!out_idx || !out_dist || !out_z) KPOP_FAIL(KPOP_ERR_INVALID, "summary: neighbour outputs are null");
+  if (!out.idx || !out.dist || !out.z) KPOP_FAIL(KPOP_ERR_INVALID, "summary: neighbour outputs are null");
   DevBuf drow, dw, ka, kb, va, vb, scr;
   if (!src.d_rows) {
     KPOP_TRY(drow.alloc((uint64_t)r1 * 8));
@@ -1766,24 +1621,24 @@ static int fill_long_lists(const LongListSource &src, uint32_t r1, uint32_t r2, 
     uint64_t *sk = nullptr;
     uint32_t *sv = nullptr;
     KPOP_TRY(radix_sort_pairs_u64(ka.as<uint64_t>(), kb.as<uint64_t>(), va.as<uint32_t>(), vb.as<uint32_t>(), r1, 64, scr.p, st, &sk, &sv));
-    const uint32_t m = std::min(out_n[j], max_neighbours);
+    const uint32_t m = std::min(out.n[j], max_neighbours);
     hk.resize(m);
     KPOP_HIP(hipMemcpyAsync(hk.data(), sk, (uint64_t)m * 8, hipMemcpyDeviceToHost, st));
-    KPOP_HIP(hipMemcpyAsync(out_idx + (uint64_t)j * max_neighbours, sv, (uint64_t)m * 4, hipMemcpyDeviceToHost, st));
+    KPOP_HIP(hipMemcpyAsync(out.idx + (uint64_t)j * max_neighbours, sv, (uint64_t)m * 4, hipMemcpyDeviceToHost, st));
     KPOP_HIP(hipStreamSynchronize(st));
-    const double mean = out_stats[(uint64_t)j * 4 + 0], sd = out_stats[(uint64_t)j * 4 + 1];
+    const double mean = out.stats[(uint64_t)j * 4 + 0], sd = out.stats[(uint64_t)j * 4 + 1];
     for (uint32_t q = 0; q < m; ++q) {
       const uint64_t kq = hk[q], bq = (kq >> 63) ? (kq & 0x7FFFFFFFFFFFFFFFull) : ~kq;  // key_dist on the host
       double dq;
       memcpy(&dq, &bq, 8);
-      out_dist[(uint64_t)j * max_neighbours + q] = dq;
+      out.dist[(uint64_t)j * max_neighbours + q] = dq;
       volatile double num = dq - mean;  // (two roundings, as the kernels': no contraction)
       double zz = num / sd;
       if (zz != zz) {  // the x86 invalid-operation NaN the reference's arithmetic gives (see the kernels)
         const uint64_t nanbits = 0xFFF8000000000000ull;
         memcpy(&zz, &nanbits, 8);
       }
-      out_z[(uint64_t)j * max_neighbours + q] = zz;
+      out.z[(uint64_t)j * max_neighbours + q] = zz;
     }
   }
   return KPOP_OK;
@@ -1796,73 +1651,49 @@ static int check_kind(int kind, double p, const char *who) {
   return 0;
 }
 
-// the three kinds of every entry point; prep: the first operand is a resident set (refset.h), nullptr otherwise
-static int rowwise_by_kind(const double *d_m1, uint32_t r1, const double *d_norms1, const double *d_m2, uint32_t r2, uint32_t n_dims, const double *d_metric,
-                           int kind, double p, int normalize, void *d_work, double *d_out, hipStream_t st, kpop_refset *prep) {
+// the three kinds of every entry point: f(K), K an integral_constant of the kind
+template <class F>
+static int by_kind(int kind, F &&f) {
   switch (kind) {
-    case KPOP_EUCLIDEAN: return rowwise_impl<KPOP_EUCLIDEAN>(d_m1, r1, d_m2, r2, n_dims, d_metric, p, normalize, d_work, d_out, st, d_norms1, prep);
-    case KPOP_COSINE: return rowwise_impl<KPOP_COSINE>(d_m1, r1, d_m2, r2, n_dims, d_metric, p, normalize, d_work, d_out, st, d_norms1, prep);
-    default: return rowwise_impl<KPOP_MINKOWSKI>(d_m1, r1, d_m2, r2, n_dims, d_metric, p, normalize, d_work, d_out, st, d_norms1, prep);
+    case KPOP_EUCLIDEAN: return f(std::integral_constant<int, KPOP_EUCLIDEAN>{});
+    case KPOP_COSINE: return f(std::integral_constant<int, KPOP_COSINE>{});
+    default: return f(std::integral_constant<int, KPOP_MINKOWSKI>{});
   }
 }
-static int summary_by_kind(const double *d_m1, uint32_t r1, const double *d_m2, uint32_t r2, uint32_t n_dims, const double *d_metric, int kind, double p,
-                           int normalize, uint32_t keep_at_most, uint32_t max_neighbours, void *d_work, double *d_out_stats, uint32_t *d_out_n,
-                           uint32_t *d_out_idx, double *d_out_dist, double *d_out_z, hipStream_t st, kpop_refset *prep) {
-  if (r1 > kSummaryMaxR1) {
-    switch (kind) {
-      case KPOP_EUCLIDEAN:
-        return summary_large_impl<KPOP_EUCLIDEAN>(d_m1, r1, d_m2, r2, n_dims, d_metric, p, normalize, keep_at_most,
-                                                  max_neighbours, d_work, d_out_stats, d_out_n, d_out_idx, d_out_dist, d_out_z, st, prep);
-      case KPOP_COSINE:
-        return summary_large_impl<KPOP_COSINE>(d_m1, r1, d_m2, r2, n_dims, d_metric, p, normalize, keep_at_most,
-                                               max_neighbours, d_work, d_out_stats, d_out_n, d_out_idx, d_out_dist, d_out_z, st, prep);
-      default:
-        return summary_large_impl<KPOP_MINKOWSKI>(d_m1, r1, d_m2, r2, n_dims, d_metric, p, normalize, keep_at_most,
-                                                  max_neighbours, d_work, d_out_stats, d_out_n, d_out_idx, d_out_dist, d_out_z, st, prep);
-    }
-  }
-  switch (kind) {
-    case KPOP_EUCLIDEAN:
-      return summary_impl<KPOP_EUCLIDEAN>(d_m1, r1, d_m2, r2, n_dims, d_metric, p, normalize, keep_at_most, max_neighbours,
-                                          d_work, d_out_stats, d_out_n, d_out_idx, d_out_dist, d_out_z, st, prep);
-    case KPOP_COSINE:
-      return summary_impl<KPOP_COSINE>(d_m1, r1, d_m2, r2, n_dims, d_metric, p, normalize, keep_at_most, max_neighbours,
-                                       d_work, d_out_stats, d_out_n, d_out_idx, d_out_dist, d_out_z, st, prep);
-    default:
-      return summary_impl<KPOP_MINKOWSKI>(d_m1, r1, d_m2, r2, n_dims, d_metric, p, normalize, keep_at_most, max_neighbours,
-                                          d_work, d_out_stats, d_out_n, d_out_idx, d_out_dist, d_out_z, st, prep);
-  }
+static int rowwise_by_kind(int kind, const DistOperands &o, const double *d_norms1, double *d_out) {
+  return by_kind(kind, [&](auto K) { return rowwise_impl<decltype(K)::value>(o, d_out, d_norms1); });
+}
+static int summary_by_kind(int kind, const DistOperands &o, const SummaryOut &out) {
+  return by_kind(kind, [&](auto K) { return o.r1 > kSummaryMaxR1 ? summary_large_impl<decltype(K)::value>(o, out) : summary_impl<decltype(K)::value>(o, out); });
+}
+static DistOperands against_set(kpop_refset *rs, const double *d_m2, uint32_t r2, void *d_work, hipStream_t st) {
+  return DistOperands{rs->rows, rs->r1, d_m2, r2, rs->n_dims, rs->metric, rs->p, rs->normalize, d_work, st, rs};
 }
 
 // kpop_dev_refset_distance_rowwise / _summary (refset.hip checks the handle): the bodies of kpop_dev_distance_rowwise / _summary
 int refset_dev_rowwise(kpop_refset *rs, const double *d_m2, uint32_t r2, void *d_work, double *d_out, hipStream_t st) {
   if (rs->r1 == 0 || r2 == 0) return KPOP_OK;
   if (!d_m2 || !d_out || (rs->normalize && !d_work)) KPOP_FAIL(KPOP_ERR_INVALID, "kpop_dev_refset_distance_rowwise: null argument (the workspace is needed when normalising)");
-  return rowwise_by_kind(rs->rows, rs->r1, nullptr, d_m2, r2, rs->n_dims, rs->metric, rs->kind, rs->p, rs->normalize, d_work, d_out, st, rs);
+  return rowwise_by_kind(rs->kind, against_set(rs, d_m2, r2, d_work, st), nullptr, d_out);
 }
-int refset_dev_summary(kpop_refset *rs, const double *d_m2, uint32_t r2, uint32_t keep_at_most, uint32_t max_neighbours, void *d_work,
-                       double *d_out_stats, uint32_t *d_out_n, uint32_t *d_out_idx, double *d_out_dist, double *d_out_z, hipStream_t st) {
+int refset_dev_summary(kpop_refset *rs, const double *d_m2, uint32_t r2, void *d_work, const SummaryOut &out, hipStream_t st) {
   if (r2 == 0) return KPOP_OK;
-  if (!d_m2 || !d_out_stats || !d_out_n || (rs->normalize && !d_work)) KPOP_FAIL(KPOP_ERR_INVALID, "kpop_dev_refset_distance_summary: null argument");
-  if (max_neighbours && (!d_out_idx || !d_out_dist || !d_out_z)) KPOP_FAIL(KPOP_ERR_INVALID, "kpop_dev_refset_distance_summary: null neighbour buffers");
-  return summary_by_kind(rs->rows, rs->r1, d_m2, r2, rs->n_dims, rs->metric, rs->kind, rs->p, rs->normalize, keep_at_most, max_neighbours, d_work, d_out_stats,
-                         d_out_n, d_out_idx, d_out_dist, d_out_z, st, rs);
+  if (!d_m2 || !out.stats || !out.n || (rs->normalize && !d_work)) KPOP_FAIL(KPOP_ERR_INVALID, "kpop_dev_refset_distance_summary: null argument");
+  if (out.max_neighbours && (!out.idx || !out.dist || !out.z)) KPOP_FAIL(KPOP_ERR_INVALID, "kpop_dev_refset_distance_summary: null neighbour buffers");
+  return summary_by_kind(rs->kind, against_set(rs, d_m2, r2, d_work, st), out);
 }
 // the query rows' norms and divided copy, as prepare_operands makes them against a set (within.hip)
 int refset_query_norms(const kpop_refset *rs, const double *d_m2, uint32_t r2, double *n2, double *b_div, hipStream_t st) {
-  switch (rs->kind) {
-    case KPOP_EUCLIDEAN: return launch_row_norms_pair<KPOP_EUCLIDEAN>(nullptr, 0, nullptr, nullptr, r2 ? d_m2 : nullptr, r2, n2, b_div, rs->n_dims, rs->metric, rs->p, st);
-    case KPOP_COSINE: return launch_row_norms_pair<KPOP_COSINE>(nullptr, 0, nullptr, nullptr, r2 ? d_m2 : nullptr, r2, n2, b_div, rs->n_dims, rs->metric, rs->p, st);
-    default: return launch_row_norms_pair<KPOP_MINKOWSKI>(nullptr, 0, nullptr, nullptr, r2 ? d_m2 : nullptr, r2, n2, b_div, rs->n_dims, rs->metric, rs->p, st);
-  }
+  return by_kind(rs->kind, [&](auto K) {
+    return launch_row_norms_pair<decltype(K)::value>(nullptr, 0, nullptr, nullptr, r2 ? d_m2 : nullptr, r2, n2, b_div, rs->n_dims, rs->metric, rs->p, st);
+  });
 }
-int refset_fill_long_lists(kpop_refset *rs, const double *d_m2, uint32_t r2, uint32_t max_neighbours, const double *out_stats, const uint32_t *out_n,
-                           uint32_t *out_idx, double *out_dist, double *out_z, hipStream_t st) {
+int refset_fill_long_lists(kpop_refset *rs, const double *d_m2, uint32_t r2, const SummaryOut &out, hipStream_t st) {
   LongListSource src;
   src.rs = rs;
   src.d2 = d_m2;
   src.n_dims = rs->n_dims;
-  return fill_long_lists(src, rs->r1, r2, max_neighbours, out_stats, out_n, out_idx, out_dist, out_z, st);
+  return fill_long_lists(src, rs->r1, r2, out, st);
 }
 
 }  // namespace kpop
@@ -1892,17 +1723,10 @@ extern "C" int kpop_embeddings(const double *m, uint32_t rows, uint32_t n_dims, 
   KPOP_HIP(hipMemcpyAsync(dm.p, m, bytes, hipMemcpyHostToDevice, st));
   KPOP_HIP(hipMemcpyAsync(dmet.p, metric, (uint64_t)n_dims * 8, hipMemcpyHostToDevice, st));
   KPOP_HIP(hipMemcpyAsync(dw.p, w.data(), (uint64_t)n_dims * 8, hipMemcpyHostToDevice, st));
-  int rc;
-  if (kind == KPOP_EUCLIDEAN)
-    rc = embeddings_impl<KPOP_EUCLIDEAN>(dm.as<double>(), rows, n_dims, dmet.as<double>(), dw.as<double>(), p, normalize, ds.as<double>(),
-                                         dn.as<double>(), dout.as<double>(), st);
-  else if (kind == KPOP_COSINE)
-    rc = embeddings_impl<KPOP_COSINE>(dm.as<double>(), rows, n_dims, dmet.as<double>(), dw.as<double>(), p, normalize, ds.as<double>(),
-                                      dn.as<double>(), dout.as<double>(), st);
-  else
-    rc = embeddings_impl<KPOP_MINKOWSKI>(dm.as<double>(), rows, n_dims, dmet.as<double>(), dw.as<double>(), p, normalize, ds.as<double>(),
-                                         dn.as<double>(), dout.as<double>(), st);
-  KPOP_TRY(rc);
+  KPOP_TRY(by_kind(kind, [&](auto K) {
+    return embeddings_impl<decltype(K)::value>(dm.as<double>(), rows, n_dims, dmet.as<double>(), dw.as<double>(), p, normalize, ds.as<double>(), dn.as<double>(),
+                                               dout.as<double>(), st);
+  }));
   KPOP_HIP(hipMemcpyAsync(out, dout.p, bytes, hipMemcpyDeviceToHost, st));
   KPOP_HIP(hipStreamSynchronize(st));
   return KPOP_OK;
@@ -1927,11 +1751,10 @@ extern "C" int kpop_dev_row_norms(const double *d_m, uint32_t rows, uint32_t n_d
   if (n_dims >= kLongD) KPOP_FAIL(KPOP_ERR_UNSUPPORTED, "kpop_dev_row_norms: rows of %u dimensions or more go through kpop_dev_distance_rowwise", kLongD);
   hipStream_t st = as_stream(stream);
   const dim3 grid(div_up(rows, kNormRows)), block(256);
-  switch (kind) {
-    case KPOP_EUCLIDEAN: row_norms_kernel<KPOP_EUCLIDEAN><<<grid, block, 0, st>>>(d_m, rows, n_dims, d_metric, p, d_norms, nullptr); break;
-    case KPOP_COSINE: row_norms_kernel<KPOP_COSINE><<<grid, block, 0, st>>>(d_m, rows, n_dims, d_metric, p, d_norms, nullptr); break;
-    default: row_norms_kernel<KPOP_MINKOWSKI><<<grid, block, 0, st>>>(d_m, rows, n_dims, d_metric, p, d_norms, nullptr); break;
-  }
+  by_kind(kind, [&](auto K) {
+    row_norms_kernel<decltype(K)::value><<<grid, block, 0, st>>>(d_m, rows, n_dims, d_metric, p, d_norms, nullptr);
+    return 0;
+  });
   KPOP_LAUNCH_CHECK();
   return KPOP_OK;
 }
@@ -1951,7 +1774,7 @@ extern "C" int kpop_dev_distance_rowwise_norms(const double *d_m1, uint32_t r1, 
   if (!d_m1 || !d_m2 || !d_metric || !d_out || ((normalize || n_dims >= kLongD) && !d_work))
     KPOP_FAIL(KPOP_ERR_INVALID, "kpop_dev_distance_rowwise: null argument (the workspace is needed when normalising and for rows of %u dimensions or more)", kLongD);
   if (n_dims == 0) KPOP_FAIL(KPOP_ERR_INVALID, "kpop_dev_distance_rowwise: n_dims must be positive");
-  return rowwise_by_kind(d_m1, r1, d_norms1, d_m2, r2, n_dims, d_metric, kind, p, normalize, d_work, d_out, as_stream(stream), nullptr);
+  return rowwise_by_kind(kind, DistOperands{d_m1, r1, d_m2, r2, n_dims, d_metric, p, normalize, d_work, as_stream(stream), nullptr}, d_norms1, d_out);
 }
 
 extern "C" int kpop_dev_distance_summary(const double *d_m1, uint32_t r1, const double *d_m2, uint32_t r2,
@@ -1967,8 +1790,8 @@ extern "C" int kpop_dev_distance_summary(const double *d_m1, uint32_t r1, const 
   if (max_neighbours && (!d_out_idx || !d_out_dist || !d_out_z))
     KPOP_FAIL(KPOP_ERR_INVALID, "kpop_dev_distance_summary: null neighbour buffers");
   if (n_dims == 0) KPOP_FAIL(KPOP_ERR_INVALID, "kpop_dev_distance_summary: n_dims must be positive");
-  return summary_by_kind(d_m1, r1, d_m2, r2, n_dims, d_metric, kind, p, normalize, keep_at_most, max_neighbours, d_work, d_out_stats, d_out_n, d_out_idx,
-                         d_out_dist, d_out_z, as_stream(stream), nullptr);
+  return summary_by_kind(kind, DistOperands{d_m1, r1, d_m2, r2, n_dims, d_metric, p, normalize, d_work, as_stream(stream), nullptr},
+                         SummaryOut{d_out_stats, d_out_n, d_out_idx, d_out_dist, d_out_z, keep_at_most, max_neighbours});
 }
 
 extern "C" int kpop_dev_summarize_distances(const double *d_dist, uint32_t r2, uint32_t r1, uint32_t keep_at_most,
@@ -1979,19 +1802,18 @@ extern "C" int kpop_dev_summarize_distances(const double *d_dist, uint32_t r2, u
   if (!d_out_stats || !d_out_n || (r1 && !d_dist)) KPOP_FAIL(KPOP_ERR_INVALID, "kpop_dev_summarize_distances: null argument");
   if (max_neighbours && (!d_out_idx || !d_out_dist || !d_out_z))
     KPOP_FAIL(KPOP_ERR_INVALID, "kpop_dev_summarize_distances: null neighbour buffers");
+  hipStream_t st = as_stream(stream);
+  const SummaryOut out{d_out_stats, d_out_n, d_out_idx, d_out_dist, d_out_z, keep_at_most, max_neighbours};
   if (r1 > kSummaryMaxR1) {
     // rows in chunks of up to 512, so that the two-pass path's lists stay a few hundred megabytes
-    hipStream_t st = as_stream(stream);
     const uint32_t chunk = std::min<uint32_t>(r2, 512);
     void *scratch = nullptr;
     KPOP_TRY(ctx().ws_for(st).ensure(summary_large_scratch_bytes(chunk, r1), &scratch));
     for (uint32_t q0 = 0; q0 < r2; q0 += chunk)
-      KPOP_TRY(launch_summary_large(d_dist + (uint64_t)q0 * r1, std::min(chunk, r2 - q0), r1, q0, keep_at_most, max_neighbours, d_out_stats,
-                                    d_out_n, d_out_idx, d_out_dist, d_out_z, st, scratch));
+      KPOP_TRY(launch_summary_large(d_dist + (uint64_t)q0 * r1, std::min(chunk, r2 - q0), r1, q0, out, st, scratch));
     return KPOP_OK;
   }
-  return launch_summary<KPOP_EUCLIDEAN, true>(d_dist, r1, nullptr, r2, 1, nullptr, 2.0, keep_at_most, max_neighbours,
-                                              d_out_stats, d_out_n, d_out_idx, d_out_dist, d_out_z, as_stream(stream));
+  return launch_summary<KPOP_EUCLIDEAN, true>(d_dist, r1, nullptr, r2, 1, nullptr, 2.0, out, st);
 }
 
 // ---------------------------------------------------------------------------
@@ -2026,7 +1848,7 @@ extern "C" int kpop_summarize_distances(const double *dist, uint32_t r2, uint32_
   KPOP_HIP(hipStreamSynchronize(st));
   LongListSource src;
   src.d_rows = dd.as<double>();
-  return fill_long_lists(src, r1, r2, max_neighbours, out_stats, out_n, out_idx, out_dist, out_z, st);
+  return fill_long_lists(src, r1, r2, SummaryOut{out_stats, out_n, out_idx, out_dist, out_z, keep_at_most, max_neighbours}, st);
 }
 
 extern "C" int kpop_distance_rowwise(const double *m1, uint32_t r1, const double *m2, uint32_t r2, uint32_t n_dims,
@@ -2099,5 +1921,5 @@ extern "C" int kpop_distance_summary(const double *m1, uint32_t r1, const double
   src.kind = kind;
   src.normalize = normalize;
   src.p = p;
-  return fill_long_lists(src, r1, r2, max_neighbours, out_stats, out_n, out_idx, out_dist, out_z, st);
+  return fill_long_lists(src, r1, r2, SummaryOut{out_stats, out_n, out_idx, out_dist, out_z, keep_at_most, max_neighbours}, st);
 }

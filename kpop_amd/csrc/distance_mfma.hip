@@ -24,7 +24,7 @@
 #include "common.h"
 #include "summary_types.h"
 #include "space_ops.h"
-#include "refset.h"
+#include "distance_routes.h"
 
 namespace kpop {
 
@@ -1217,7 +1217,7 @@ int launch_distance_rowwise_mfma(int kind, const double *a, uint32_t r1, const d
   return 0;
 }
 
-// the one-kernel path's pass (declared in summary_large.hip, which owns its scratch): q query rows (their fragments and norms in the
+// the one-kernel path's pass (called by summary_large.hip, which owns its scratch): q query rows (their fragments and norms in the
 // matrix-core scratch: launch_mfma_query_prep) against all r1 reference rows, a block a (stripe, 128 query rows)
 int launch_select_mfma(int kind, const double *a, uint32_t r1, uint32_t q, uint32_t n_dims, const void *mscratch, uint32_t q_room, const FusedThr *thr, double *seg,
                        uint32_t *seg_i, StripeRec *rec, double *part, RowCounts *cnt, uint32_t *nb_idx, double *nb_d, uint32_t n_stripes, hipStream_t st, const RefScalars *ref) {
@@ -1322,22 +1322,21 @@ int launch_distance_rows_mfma(int kind, const double *a, uint32_t r1, const doub
 
 // the refinement; *gate = the device word that counts the rows left to the fall-back, *row_counts = their flags (RowCounts)
 int launch_summary_refine(int kind, const double *rows, const double *a, uint32_t r1, const double *b, uint32_t q, uint32_t n_dims, const double *metric,
-                          double p, uint32_t row0, uint32_t keep_at_most, uint32_t max_neighbours, double *out_stats, uint32_t *out_n, uint32_t *out_idx,
-                          double *out_dist, double *out_z, void *scratch, uint32_t q_room, hipStream_t st, const SummaryLists &lists, const uint32_t **gate,
-                          const void **row_counts, const double *na, const RefScalars *ref) {
+                          double p, uint32_t row0, const SummaryOut &out, void *scratch, uint32_t q_room, hipStream_t st, const SummaryLists &lists,
+                          const uint32_t **gate, const void **row_counts, const double *na, const RefScalars *ref) {
   const MfmaScratch M = carve_mfma(scratch, q_room, r1, n_dims, 0, ref);
-  const uint32_t req_len = keep_at_most ? keep_at_most : r1;
+  const uint32_t req_len = out.req_len(r1);
   // |u~ - u| <= gamma (|a|^2 + |b|^2): n_dims products and additions of the contraction and of the two norms at 2^-53 each, the
   // chain's own roundings, and a factor of ten on top
   const double gamma = 4e-15 * (double)std::max(n_dims, 16u);
   SummaryLists L = lists;
   if (!ctx().tune_summary_mfma_lists || !L.cand_i) L = SummaryLists{};
   if (kind == KPOP_EUCLIDEAN)
-    summary_refine_kernel<KPOP_EUCLIDEAN><<<dim3(q), dim3(1024), 0, st>>>(rows, a, r1, b, n_dims, metric, p, M.sb, M.smax, row0, req_len, max_neighbours, gamma, out_stats,
-                                                                          out_n, out_idx, out_dist, out_z, M.rc, M.n_failed, L, na);
+    summary_refine_kernel<KPOP_EUCLIDEAN><<<dim3(q), dim3(1024), 0, st>>>(rows, a, r1, b, n_dims, metric, p, M.sb, M.smax, row0, req_len, out.max_neighbours, gamma, out.stats,
+                                                                          out.n, out.idx, out.dist, out.z, M.rc, M.n_failed, L, na);
   else
-    summary_refine_kernel<KPOP_COSINE><<<dim3(q), dim3(1024), 0, st>>>(rows, a, r1, b, n_dims, metric, p, M.sb, M.smax, row0, req_len, max_neighbours, gamma, out_stats,
-                                                                       out_n, out_idx, out_dist, out_z, M.rc, M.n_failed, L, na);
+    summary_refine_kernel<KPOP_COSINE><<<dim3(q), dim3(1024), 0, st>>>(rows, a, r1, b, n_dims, metric, p, M.sb, M.smax, row0, req_len, out.max_neighbours, gamma, out.stats,
+                                                                       out.n, out.idx, out.dist, out.z, M.rc, M.n_failed, L, na);
   KPOP_LAUNCH_CHECK();
   *gate = M.n_failed;
   *row_counts = M.rc;

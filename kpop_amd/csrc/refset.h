@@ -1,8 +1,10 @@
 // refset.h -- kpop_refset: a first operand of the distance entry points that stays in HBM with everything about it that does
 // not depend on the query rows (refset.hip).  rowwise_impl / summary_impl / summary_large_impl (distance.hip) take a pointer to
-// one as their optional "prepared first operand" and ask it for the pieces their route would otherwise compute.
+// one as the optional "prepared first operand" of their operands (DistOperands::prep, distance_routes.h) and ask it for the pieces their
+// route would otherwise compute.
 #pragma once
 #include "common.h"
+#include "summary_types.h"
 
 namespace kpop {
 
@@ -65,16 +67,9 @@ struct kpop_refset {
 namespace kpop {
 // distance.hip: the device entry points' bodies with a prepared first operand
 int refset_dev_rowwise(kpop_refset *rs, const double *d_m2, uint32_t r2, void *d_work, double *d_out, hipStream_t st);
-int refset_dev_summary(kpop_refset *rs, const double *d_m2, uint32_t r2, uint32_t keep_at_most, uint32_t max_neighbours, void *d_work,
-                       double *d_out_stats, uint32_t *d_out_n, uint32_t *d_out_idx, double *d_out_dist, double *d_out_z, hipStream_t st);
-int refset_fill_long_lists(kpop_refset *rs, const double *d_m2, uint32_t r2, uint32_t max_neighbours, const double *out_stats, const uint32_t *out_n,
-                           uint32_t *out_idx, double *out_dist, double *out_z, hipStream_t st);
+int refset_dev_summary(kpop_refset *rs, const double *d_m2, uint32_t r2, void *d_work, const SummaryOut &out, hipStream_t st);
+int refset_fill_long_lists(kpop_refset *rs, const double *d_m2, uint32_t r2, const SummaryOut &out, hipStream_t st);  // (out: host buffers)
 int refset_query_norms(const kpop_refset *rs, const double *d_m2, uint32_t r2, double *n2, double *b_div, hipStream_t st);
 // refset.hip: the handle belongs to the calling thread's device slot
 int refset_check_handle(const kpop_refset *rs, const char *who);
-// distance_mfma.hip / summary_large.hip: kernels the set's lazily built pieces share with the unprepared call
-int launch_sample_gather(const double *a, uint32_t r1, uint32_t n_dims, uint32_t s, double *out, hipStream_t st);
-int launch_row_sumsq(const double *x, uint32_t rows, uint32_t n_dims, const double *metric, double *out, hipStream_t st);
-int launch_row_sumsq_max(const double *x, uint32_t rows, uint32_t n_dims, const double *metric, double *out, unsigned long long *smax, hipStream_t st);
-int launch_gather_sample_scalars(const double *sa, const double *ia, uint32_t r1, uint32_t s, double *sas, double *ias, hipStream_t st);
 }  // namespace kpop

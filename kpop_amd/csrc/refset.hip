@@ -19,7 +19,7 @@
 #include <new>
 
 #include "common.h"
-#include "refset.h"
+#include "distance_routes.h"
 #include "row_norms.h"
 
 namespace kpop {
@@ -351,7 +351,7 @@ extern "C" int kpop_dev_refset_distance_summary(kpop_refset *rs, const double *d
                                                 void *d_work, double *d_out_stats, uint32_t *d_out_n, uint32_t *d_out_idx, double *d_out_dist,
                                                 double *d_out_z, void *stream) {
   KPOP_TRY(check_handle(rs, "kpop_dev_refset_distance_summary"));
-  return refset_dev_summary(rs, d_m2, r2, keep_at_most, max_neighbours, d_work, d_out_stats, d_out_n, d_out_idx, d_out_dist, d_out_z, as_stream(stream));
+  return refset_dev_summary(rs, d_m2, r2, d_work, SummaryOut{d_out_stats, d_out_n, d_out_idx, d_out_dist, d_out_z, keep_at_most, max_neighbours}, as_stream(stream));
 }
 
 // ---------------------------------------------------------------------------
@@ -393,8 +393,8 @@ extern "C" int kpop_refset_distance_summary(kpop_refset *rs, const double *m2, u
   KPOP_TRY(dd.alloc(nn * 8));
   KPOP_TRY(dz.alloc(nn * 8));
   KPOP_HIP(hipMemcpyAsync(d2.p, m2, (uint64_t)r2 * D * 8, hipMemcpyHostToDevice, st));
-  KPOP_TRY(refset_dev_summary(rs, d2.as<double>(), r2, keep_at_most, max_neighbours, dw.p, ds.as<double>(), dn.as<uint32_t>(), di.as<uint32_t>(),
-                              dd.as<double>(), dz.as<double>(), st));
+  KPOP_TRY(refset_dev_summary(rs, d2.as<double>(), r2, dw.p,
+                              SummaryOut{ds.as<double>(), dn.as<uint32_t>(), di.as<uint32_t>(), dd.as<double>(), dz.as<double>(), keep_at_most, max_neighbours}, st));
   KPOP_HIP(hipMemcpyAsync(out_stats, ds.p, (uint64_t)r2 * 4 * 8, hipMemcpyDeviceToHost, st));
   KPOP_HIP(hipMemcpyAsync(out_n, dn.p, (uint64_t)r2 * 4, hipMemcpyDeviceToHost, st));
   if (nn) {
@@ -403,5 +403,5 @@ extern "C" int kpop_refset_distance_summary(kpop_refset *rs, const double *m2, u
     KPOP_HIP(hipMemcpyAsync(out_z, dz.p, nn * 8, hipMemcpyDeviceToHost, st));
   }
   KPOP_HIP(hipStreamSynchronize(st));
-  return refset_fill_long_lists(rs, d2.as<double>(), r2, max_neighbours, out_stats, out_n, out_idx, out_dist, out_z, st);
+  return refset_fill_long_lists(rs, d2.as<double>(), r2, SummaryOut{out_stats, out_n, out_idx, out_dist, out_z, keep_at_most, max_neighbours}, st);
 }

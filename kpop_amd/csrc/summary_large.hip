@@ -18,7 +18,7 @@
 #include "common.h"
 #include "summary_types.h"
 #include "space_ops.h"
-#include "refset.h"
+#include "distance_routes.h"
 
 namespace kpop {
 
@@ -1805,10 +1805,8 @@ int launch_sample_gather(const double *a, uint32_t r1, uint32_t n_dims, uint32_t
 // a, b: the prepared operands (b: the chunk's n_rows query rows); srow: [n_rows][s] distances to the sample; seg: [n_rows][r1]
 // (segments now, distance rows of the fallback later).  *gate: the device word that counts the rows left to the fallback.
 int launch_summary_fused(int kind, const double *a, uint32_t r1, const double *b, uint32_t n_rows, uint32_t n_dims, const double *metric, double p,
-                         const double *srow, uint32_t s, uint32_t row0, uint32_t keep_at_most, uint32_t max_neighbours, double *out_stats,
-                         uint32_t *out_n, uint32_t *out_idx, double *out_dist, double *out_z, double *seg, void *scratch, hipStream_t st,
-                         const uint32_t **gate) {
-  const uint32_t req_len = keep_at_most ? keep_at_most : r1;
+                         const double *srow, uint32_t s, uint32_t row0, const SummaryOut &out, double *seg, void *scratch, hipStream_t st, const uint32_t **gate) {
+  const uint32_t req_len = out.req_len(r1);
   const uint32_t n_stripes = (r1 + kStripe - 1) / kStripe;
   FusedScratch F;
   carve_fused(scratch, n_rows, r1, &F);
@@ -1823,9 +1821,8 @@ int launch_summary_fused(int kind, const double *a, uint32_t r1, const double *b
   else KPOP_FUSED(KPOP_MINKOWSKI);
 #undef KPOP_FUSED
   KPOP_LAUNCH_CHECK();
-  fused_finish_kernel<true><<<dim3(n_rows), dim3(kLT), 0, st>>>(seg, r1, row0, req_len, max_neighbours, F.info, F.thr, F.cnt, F.rec, F.part, n_stripes, F.pre,
-                                                          F.ccand, fused_cand_cap(r1), F.nb_idx, F.nb_d, F.n_failed, out_stats, out_n, out_idx, out_dist,
-                                                          out_z);
+  fused_finish_kernel<true><<<dim3(n_rows), dim3(kLT), 0, st>>>(seg, r1, row0, req_len, out.max_neighbours, F.info, F.thr, F.cnt, F.rec, F.part, n_stripes, F.pre,
+                                                          F.ccand, fused_cand_cap(r1), F.nb_idx, F.nb_d, F.n_failed, out.stats, out.n, out.idx, out.dist, out.z);
   KPOP_LAUNCH_CHECK();
   *gate = F.n_failed;
   return 0;
@@ -1835,13 +1832,10 @@ int launch_summary_fused(int kind, const double *a, uint32_t r1, const double *b
 // accumulators' registers, no distance row written): thresholds from the distances to the sample (`srow`, [n_rows][s], approximate as
 // well), the pass, the finish over the stripes' segments (values in `seg`, columns in `seg_i`, both [n_rows][r1]).  What it reports is
 // approximate: `lists` is what the exact refinement (summary_refine_kernel) reads.
-int launch_select_mfma(int kind, const double *a, uint32_t r1, uint32_t q, uint32_t n_dims, const void *mscratch, uint32_t q_room, const FusedThr *thr, double *seg,
-                       uint32_t *seg_i, StripeRec *rec, double *part, RowCounts *cnt, uint32_t *nb_idx, double *nb_d, uint32_t n_stripes, hipStream_t st, const RefScalars *ref);
 int launch_summary_fused_mfma(int kind, const double *a, uint32_t r1, uint32_t n_rows, uint32_t n_dims, const double *srow, uint32_t s, uint32_t row0,
-                              uint32_t keep_at_most, uint32_t max_neighbours, double *out_stats, uint32_t *out_n, uint32_t *out_idx, double *out_dist,
-                              double *out_z, double *seg, uint32_t *seg_i, void *scratch, const void *mscratch, uint32_t q_room, hipStream_t st,
+                              const SummaryOut &out, double *seg, uint32_t *seg_i, void *scratch, const void *mscratch, uint32_t q_room, hipStream_t st,
                               SummaryLists *lists, const RefScalars *ref) {
-  const uint32_t req_len = keep_at_most ? keep_at_most : r1;
+  const uint32_t req_len = out.req_len(r1);
   const uint32_t n_stripes = (r1 + kStripe - 1) / kStripe;  // blocks of the matrix-core kernel along the reference rows; it keeps FOUR records a stripe
   FusedScratch F;
   carve_fused(scratch, n_rows, r1, &F, kStripe / 4);
@@ -1851,9 +1845,9 @@ int launch_summary_fused_mfma(int kind, const double *a, uint32_t r1, uint32_t n
   fused_sample_kernel<false><<<dim3(n_rows), dim3(kLT), 0, st>>>(srow, s, r1, req_len, F.info, F.cnt, F.thr);
   KPOP_LAUNCH_CHECK();
   KPOP_TRY(launch_select_mfma(kind, a, r1, n_rows, n_dims, mscratch, q_room, F.thr, seg, seg_i, F.rec, F.part, F.cnt, F.nb_idx, F.nb_d, n_stripes, st, ref));
-  fused_finish_kernel<true><<<dim3(n_rows), dim3(kLT), 0, st>>>(seg, r1, row0, req_len, max_neighbours, F.info, F.thr, F.cnt, F.rec, F.part, 4 * n_stripes, F.pre,
-                                                          F.ccand, fused_cand_cap(r1), F.nb_idx, F.nb_d, F.n_failed, out_stats, out_n, out_idx, out_dist,
-                                                          out_z, seg_i, F.ccand_i, kStripe / 4, (uint64_t)n_stripes * kStripe);
+  fused_finish_kernel<true><<<dim3(n_rows), dim3(kLT), 0, st>>>(seg, r1, row0, req_len, out.max_neighbours, F.info, F.thr, F.cnt, F.rec, F.part, 4 * n_stripes, F.pre,
+                                                          F.ccand, fused_cand_cap(r1), F.nb_idx, F.nb_d, F.n_failed, out.stats, out.n, out.idx, out.dist, out.z, seg_i, F.ccand_i, kStripe / 4,
+                                                          (uint64_t)n_stripes * kStripe);
   KPOP_LAUNCH_CHECK();
   *lists = SummaryLists{F.info, F.thr, F.cnt, F.ccand, F.ccand_i, fused_cand_cap(r1), F.nb_idx, F.nb_d};
   return 0;
@@ -1864,22 +1858,18 @@ bool summary_select_mfma_applies(uint32_t r1, uint32_t keep_at_most) {
 }
 
 // the rows the fused path flagged, from distance rows computed meanwhile (gated the same way: nothing runs when none failed)
-int launch_summary_failed_rows(const double *rows, uint32_t n_rows, uint32_t r1, uint32_t row0, uint32_t keep_at_most, uint32_t max_neighbours,
-                               double *out_stats, uint32_t *out_n, uint32_t *out_idx, double *out_dist, double *out_z, void *scratch,
-                               hipStream_t st) {
+int launch_summary_failed_rows(const double *rows, uint32_t n_rows, uint32_t r1, uint32_t row0, const SummaryOut &out, void *scratch, hipStream_t st) {
   FusedScratch F;
   carve_fused(scratch, n_rows, r1, &F);
-  summary_large_kernel<<<dim3(n_rows), dim3(kLT), 0, st>>>(rows, r1, row0, keep_at_most ? keep_at_most : r1, max_neighbours, out_stats, out_n, out_idx,
-                                                           out_dist, out_z, F.cnt);
+  summary_large_kernel<<<dim3(n_rows), dim3(kLT), 0, st>>>(rows, r1, row0, out.req_len(r1), out.max_neighbours, out.stats, out.n, out.idx, out.dist, out.z, F.cnt);
   KPOP_LAUNCH_CHECK();
   return 0;
 }
 
 // the same over rows another path flagged (distance_mfma.hip: `flags` = its RowCounts, one a row of the chunk)
-int launch_summary_flagged_rows(const double *rows, uint32_t n_rows, uint32_t r1, uint32_t row0, uint32_t keep_at_most, uint32_t max_neighbours,
-                                double *out_stats, uint32_t *out_n, uint32_t *out_idx, double *out_dist, double *out_z, const void *flags, hipStream_t st) {
-  summary_large_kernel<<<dim3(n_rows), dim3(kLT), 0, st>>>(rows, r1, row0, keep_at_most ? keep_at_most : r1, max_neighbours, out_stats, out_n, out_idx,
-                                                           out_dist, out_z, reinterpret_cast<const RowCounts *>(flags));
+int launch_summary_flagged_rows(const double *rows, uint32_t n_rows, uint32_t r1, uint32_t row0, const SummaryOut &out, const void *flags, hipStream_t st) {
+  summary_large_kernel<<<dim3(n_rows), dim3(kLT), 0, st>>>(rows, r1, row0, out.req_len(r1), out.max_neighbours, out.stats, out.n, out.idx, out.dist, out.z,
+                                                           reinterpret_cast<const RowCounts *>(flags));
   KPOP_LAUNCH_CHECK();
   return 0;
 }
@@ -1895,19 +1885,17 @@ uint64_t summary_large_scratch_bytes(uint32_t n_rows, uint32_t r1) {
 
 // scratch = nullptr (or tune "summary2" 0): the one-block-per-row kernel alone.  "summary2" 1 (default): ONE pass over the
 // rows (brackets and bands from a sample, certificate for the MAD); 3: two passes (the first version of round 3).
-int launch_summary_large(const double *rows, uint32_t n_rows, uint32_t r1, uint32_t row0, uint32_t keep_at_most,
-                         uint32_t max_neighbours, double *out_stats, uint32_t *out_n, uint32_t *out_idx,
-                         double *out_dist, double *out_z, hipStream_t st, void *scratch, SummaryLists *lists, bool plain_rows, const double *srow, uint32_t srow_n) {
+int launch_summary_large(const double *rows, uint32_t n_rows, uint32_t r1, uint32_t row0, const SummaryOut &out, hipStream_t st, void *scratch,
+                         SummaryLists *lists, bool plain_rows, const double *srow, uint32_t srow_n) {
   // (srow: [n_rows][srow_n] distances of the query rows to a SAMPLE OF THE REFERENCE ROWS at even spacing -- the brackets and bands come from
   // them; nullptr: from runs of 1,024 consecutive elements of the distance rows themselves.  A database laid out lineage by lineage makes
   // neighbouring elements of a distance row near-copies of each other: 64 runs then speak for 640 of 10,000 clusters, the brackets
   // miss (126 + 176 of 512 rows on clusters of 100) and the rows go through the ten-pass kernel -- 8.1 ms where random rows take 2.3)
   if (lists) *lists = SummaryLists{};
-  const uint32_t req_len = keep_at_most ? keep_at_most : r1;
+  const uint32_t req_len = out.req_len(r1), max_neighbours = out.max_neighbours;
   const bool by_brackets = scratch && ctx().tune_summary2 && req_len <= kLargeMaxNb && r1 >= 2 * kSlice;
   if (!by_brackets) {
-    summary_large_kernel<<<dim3(n_rows), dim3(kLT), 0, st>>>(rows, r1, row0, req_len, max_neighbours, out_stats, out_n, out_idx, out_dist,
-                                                             out_z, nullptr);
+    summary_large_kernel<<<dim3(n_rows), dim3(kLT), 0, st>>>(rows, r1, row0, req_len, max_neighbours, out.stats, out.n, out.idx, out.dist, out.z, nullptr);
     KPOP_LAUNCH_CHECK();
     return 0;
   }
@@ -1946,7 +1934,7 @@ int launch_summary_large(const double *rows, uint32_t n_rows, uint32_t r1, uint3
       summary1_pass_kernel<<<dim3(n_slices, n_rows), dim3(256), 0, st>>>(rows, r1, info, thr, cnt, cand, cand_i, nb_idx, nb_d, part, n_slices, cap);
     KPOP_LAUNCH_CHECK();
     fused_finish_kernel<false><<<dim3(n_rows), dim3(kLT), 0, st>>>(rows, r1, row0, req_len, max_neighbours, info, thr, cnt, nullptr, part, n_slices, nullptr, cand,
-                                                                   cap, nb_idx, nb_d, n_failed, out_stats, out_n, out_idx, out_dist, out_z);
+                                                                   cap, nb_idx, nb_d, n_failed, out.stats, out.n, out.idx, out.dist, out.z);
     KPOP_LAUNCH_CHECK();
   } else {
     summary2_sample_kernel<<<dim3(n_rows), dim3(kLT), 0, st>>>(rows, r1, req_len, info, cnt);
@@ -1954,15 +1942,15 @@ int launch_summary_large(const double *rows, uint32_t n_rows, uint32_t r1, uint3
     summary2_pass_kernel<1><<<dim3(n_slices, n_rows), dim3(256), 0, st>>>(rows, r1, info, cnt, cand, nb_idx, nb_d, part, n_slices, cap);
     KPOP_LAUNCH_CHECK();
     summary2_finish_kernel<1><<<dim3(n_rows), dim3(kLT), 0, st>>>(rows, r1, row0, req_len, max_neighbours, info, cnt, cand, nb_idx, nb_d, part, n_slices,
-                                                                  cap, out_stats, out_n, out_idx, out_dist, out_z);
+                                                                  cap, out.stats, out.n, out.idx, out.dist, out.z);
     KPOP_LAUNCH_CHECK();
     summary2_pass_kernel<2><<<dim3(n_slices, n_rows), dim3(256), 0, st>>>(rows, r1, info, cnt, cand, nb_idx, nb_d, part, n_slices, cap);
     KPOP_LAUNCH_CHECK();
     summary2_finish_kernel<2><<<dim3(n_rows), dim3(kLT), 0, st>>>(rows, r1, row0, req_len, max_neighbours, info, cnt, cand, nb_idx, nb_d, part, n_slices,
-                                                                  cap, out_stats, out_n, out_idx, out_dist, out_z);
+                                                                  cap, out.stats, out.n, out.idx, out.dist, out.z);
     KPOP_LAUNCH_CHECK();
   }
-  summary_large_kernel<<<dim3(n_rows), dim3(kLT), 0, st>>>(rows, r1, row0, req_len, max_neighbours, out_stats, out_n, out_idx, out_dist, out_z, cnt);
+  summary_large_kernel<<<dim3(n_rows), dim3(kLT), 0, st>>>(rows, r1, row0, req_len, max_neighbours, out.stats, out.n, out.idx, out.dist, out.z, cnt);
   KPOP_LAUNCH_CHECK();
   return 0;
 }

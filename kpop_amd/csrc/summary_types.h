@@ -44,4 +44,17 @@ struct SummaryLists {
   const uint32_t *n_failed = nullptr;  // the device word that counts the rows whose brackets or bands missed (they went through the ten-pass kernel)
 };
 
+// where a summary's results go (device or host pointers): stats [rows][4], n [rows], the neighbours' idx / dist / z [rows][max_neighbours]
+struct SummaryOut {
+  double *stats;
+  uint32_t *n, *idx;
+  double *dist, *z;
+  uint32_t keep_at_most, max_neighbours;
+  // the same from query row q0 on (for the launchers that count their rows from 0; the ones that take `row0` shift inside)
+  SummaryOut from_row(uint64_t q0) const {
+    return SummaryOut{stats + q0 * 4, n + q0, idx + q0 * max_neighbours, dist + q0 * max_neighbours, z + q0 * max_neighbours, keep_at_most, max_neighbours};
+  }
+  uint32_t req_len(uint32_t r1) const { return keep_at_most ? keep_at_most : r1; }  // lib/Matrix.ml:723-726,774-777
+};
+
 }  // namespace kpop

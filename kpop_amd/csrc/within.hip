@@ -25,7 +25,7 @@
 #include <algorithm>
 
 #include "common.h"
-#include "refset.h"
+#include "distance_routes.h"
 #include "scan.h"
 #include "space_ops.h"
 

@@ -779,13 +779,16 @@ def test_distance_summary_on_the_matrix_cores_many_query_rows(kpop, oracle, kind
     api.tune("summary_audit", 1)
     api.summary_fallbacks()
     # (copy: the reference set divided by its norms into a copy first, as until late in round 6 -- the default takes it as it is; general_pass: the
-    # pass over the approximate rows written for any caller's rows)
-    for name, mfma, lanes, rawref, plain_pass in (("default", 1, 1, 1, 1), ("select", 2, 1, 1, 1), ("lanes", 1, 2, 1, 1), ("copy", 1, 1, 0, 1), ("general_pass", 1, 1, 1, 0),
-                                                  ("vector", 0, 1, 1, 1)):
+    # pass over the approximate rows written for any caller's rows; lanes_runs, lanes_copy: the two lanes share the one-lane form's loop over the
+    # batches, so they meet the brackets from runs of the distance rows and the divided copy there)
+    for name, mfma, lanes, rawref, plain_pass, sample in (("default", 1, 1, 1, 1, 1), ("select", 2, 1, 1, 1, 1), ("lanes", 1, 2, 1, 1, 1), ("copy", 1, 1, 0, 1, 1),
+                                                          ("general_pass", 1, 1, 1, 0, 1), ("lanes_runs", 1, 2, 1, 1, 0), ("lanes_copy", 1, 2, 0, 1, 1),
+                                                          ("vector", 0, 1, 1, 1, 1)):
         api.tune("summary_mfma", mfma)
         api.tune("summary_lanes", lanes)
         api.tune("summary_rawref", rawref)
         api.tune("summary_pass", plain_pass)
+        api.tune("summary_sample", sample)
         res[name] = kpop.distance_summary(m1, m2, metric, kind, 2.0, True, 20, max_neighbours=32)
         left = api.summary_fallbacks()
         assert left == 0, (name, left)
@@ -794,8 +797,9 @@ def test_distance_summary_on_the_matrix_cores_many_query_rows(kpop, oracle, kind
     api.tune("summary_lanes", 1)
     api.tune("summary_rawref", 1)
     api.tune("summary_pass", 1)
+    api.tune("summary_sample", 1)
     ref = res["vector"]
-    for name in ("default", "select", "lanes", "copy", "general_pass"):
+    for name in ("default", "select", "lanes", "copy", "general_pass", "lanes_runs", "lanes_copy"):
         got = res[name]
         assert np.array_equal(got[0][:, 2:], ref[0][:, 2:]), name
         np.testing.assert_allclose(got[0][:, :2], ref[0][:, :2], rtol=1e-10)
