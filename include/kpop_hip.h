@@ -658,6 +658,36 @@ int kpop_distance_within(const double *m1, uint32_t r1, const double *m2, uint32
                          const double *metric, int kind, double p, int normalize, double max_distance,
                          uint64_t capacity, uint64_t *out_offsets, uint32_t *out_idx, double *out_dist);
 
+/* ------------------------------------------------- clusters at a distance (connected components of a resident set)
+ * The graph on the set's r1 rows: i < j are joined iff d(j, i) <= max_distance, where d is the reference chain's distance
+ * (lib/Space.ml:182-205 with the adaptors of lib/Matrix.ml:243-250) -- the bits kpop_refset_distance_rowwise writes to
+ * out[j][i] under kpop_tune("distance_mfma", 0) when the set's own rows are the query -- whatever kpop_tune says.  The chain
+ * is symmetric bit for bit, so only i < j is examined, and i == j never.  A NaN distance joins nothing: a row with a NaN in
+ * it is a cluster of its own.  labels[i] is the SMALLEST row index of row i's connected component (labels[i] <= i,
+ * labels[labels[i]] == labels[i]), *n_clusters the number of i with labels[i] == i: the same bits on every run.
+ * max_distance negative: every row alone; +inf: every pair whose distance is a number; NaN: KPOP_ERR_INVALID.  r1 = 0:
+ * KPOP_OK and *n_clusters = 0.  Neither the r1 x r1 matrix nor any neighbour list is formed: the transitive closure of
+ * kpop_neighbours_within's lists of the set against itself, without them.
+ * known_rows <= r1 (0: none) says that labels[0 .. known_rows) hold, on entry, what this call returned for the first
+ * known_rows rows at the same max_distance: pairs of two such rows are not examined, and the result is that of
+ * known_rows = 0, bit for bit -- after kpop_refset_append a re-cluster costs new x all, not all x all.  known_rows = r1
+ * examines nothing.  The set's limits, slot and thread ownership hold as for every call on a set.                      */
+/* (lib/Space.ml:182-205; lib/Matrix.ml:243-250.)  labels: r1 entries, the first known_rows read, all written.  The incoming
+   labels are checked against the two invariants above (KPOP_ERR_INVALID).  Synchronises.                              */
+int kpop_clusters_within(kpop_refset *rs, double max_distance, uint32_t known_rows, uint32_t *labels,
+                         uint32_t *n_clusters);
+/* bytes of d_work for kpop_dev_clusters_within (lib/Space.ml:182-205 over the set against itself, see the block above): a
+   constant -- the union-find forest lives in d_labels, the divided copy in the set                                    */
+uint64_t kpop_dev_clusters_within_workspace_bytes(const kpop_refset *rs);
+/* (lib/Space.ml:182-205; lib/Matrix.ml:243-250.)  Enqueues only.  d_labels[r1] (the first known_rows TRUSTED to be an
+   earlier result), d_n_clusters[1].                                                                                   */
+int kpop_dev_clusters_within(kpop_refset *rs, double max_distance, uint32_t known_rows, void *d_work, uint32_t *d_labels,
+                             uint32_t *d_n_clusters, void *stream);
+/* unprepared convenience (lib/Matrix.ml:191-266 for the distances, m against itself): a temporary set over m, then
+   kpop_clusters_within with known_rows = 0                                                                            */
+int kpop_distance_clusters(const double *m, uint32_t rows, uint32_t n_dims, const double *metric, int kind, double p,
+                           int normalize, double max_distance, uint32_t *labels, uint32_t *n_clusters);
+
 /* ------------------------------------------------- k-mer database (KPopCountDB)
  * the operations of lib/KMerDB.ml that touch every count.  A database is the reference's
  * `storage: I32BAVector.t array` (lib/KMerDB.ml:54-63): n_cols spectra ("columns"), each a vector of n_rows int32

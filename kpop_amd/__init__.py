@@ -11,7 +11,8 @@ from .api import (check, COSINE, DNA_DS, DNA_SS, PROTEIN, EUCLIDEAN, METRIC_FLAT
                   COMBINE_MEDIAN, TRANSF_BINARY, TRANSF_POWER, TRANSF_CLR, TRANSF_PSEUDO, Pipeline, host_empty, init_devices, use_device,
                   device_slots, OUT_TWISTED, OUT_DISTANCES, OUT_SUMMARY, Sharded, shard_bounds, sharded_distance_rowwise,
                   sharded_distance_summary, RefSet, dev_refset_workspace_bytes, dev_refset_distance_rowwise, dev_refset_distance_summary,
-                  dev_neighbours_within_workspace_bytes, dev_neighbours_within, distance_within)
+                  dev_neighbours_within_workspace_bytes, dev_neighbours_within, distance_within, dev_clusters_within_workspace_bytes,
+                  dev_clusters_within, distance_clusters)
 
 __all__ = ["init", "device_count", "count_reads", "Twister", "ca", "metric_compute", "distance_rowwise",
            "distance_summary", "embeddings", "splits_gaps", "summarize_distances", "parse_distance", "KPopError", "DNA_DS", "DNA_SS", "PROTEIN", "EUCLIDEAN", "COSINE",
@@ -20,4 +21,5 @@ __all__ = ["init", "device_count", "count_reads", "Twister", "ca", "metric_compu
            "init_devices", "use_device", "device_slots", "OUT_TWISTED", "OUT_DISTANCES", "OUT_SUMMARY", "Sharded", "shard_bounds",
            "sharded_distance_rowwise", "sharded_distance_summary", "RefSet", "dev_refset_workspace_bytes",
            "dev_refset_distance_rowwise", "dev_refset_distance_summary", "dev_neighbours_within_workspace_bytes",
-           "dev_neighbours_within", "distance_within"]
+           "dev_neighbours_within", "distance_within", "dev_clusters_within_workspace_bytes", "dev_clusters_within",
+           "distance_clusters"]

@@ -826,6 +826,24 @@ class RefSet:
         total = int(offsets[r2])
         return offsets, idx[:total], dist[:total]
 
+    def clusters(self, max_distance, known=None):
+        """The connected components of the graph that joins rows i < j iff d(j, i) <= max_distance -> (labels u32 [r1], n_clusters):
+        labels[i] is the smallest row index of row i's component, the same bits on every run.  known: the labels an earlier call
+        returned at the same max_distance, for the first len(known) rows (the set has grown since: append); pairs of two such rows are
+        not examined, the result is the from-scratch one (kpop_clusters_within, include/kpop_hip.h)."""
+        r1 = self.info()["r1"]
+        labels = np.zeros(max(r1, 1), dtype=np.uint32)
+        known_rows = 0
+        if known is not None:
+            known = np.asarray(known)
+            if known.ndim != 1 or len(known) > r1:
+                raise ValueError("known: the labels of the first rows of the set, at most %d" % r1)
+            known_rows = len(known)
+            labels[:known_rows] = known
+        n = C.c_uint32()
+        check(_lib.load().kpop_clusters_within(self._h, float(max_distance), known_rows, _p(labels, C.c_uint32), C.byref(n)))
+        return labels[:r1], int(n.value)
+
     def free(self):
         if self._h is not None and self._h.value:
             check(_lib.load().kpop_refset_free(self._h))
@@ -998,3 +1016,26 @@ def distance_within(m1, m2, metric, max_distance, kind=EUCLIDEAN, p=2.0, normali
                                            capacity, _p(offsets, C.c_uint64), _p(idx, C.c_uint32), _p(dist, C.c_double)))
     total = int(offsets[r2])
     return offsets, idx[:total], dist[:total]
+
+
+def dev_clusters_within_workspace_bytes(rs):
+    """the size of d_work for dev_clusters_within: a constant, whatever the set's size"""
+    return int(_lib.load().kpop_dev_clusters_within_workspace_bytes(rs.handle))
+
+
+def dev_clusters_within(rs, max_distance, d_work, d_labels, d_n_clusters, known_rows=0, stream=0):
+    """enqueue only: d_labels[r1] (u32; the first known_rows an earlier result at the same max_distance, trusted), d_n_clusters[1] (u32)"""
+    check(_lib.load().kpop_dev_clusters_within(rs.handle, float(max_distance), int(known_rows), d_work, d_labels, d_n_clusters, stream))
+
+
+def distance_clusters(m, metric, kind=EUCLIDEAN, p=2.0, normalize=True, max_distance=0.0):
+    """RefSet(m, ...).clusters(max_distance) without keeping the set: one call of kpop_distance_clusters -> (labels u32 [rows], n_clusters)"""
+    m, metric = _c(m, np.float64), _c(metric, np.float64)
+    if m.ndim != 2 or m.shape[1] != len(metric):
+        raise ValueError("Incompatible_geometries")  # lib/Matrix.ml:193-194
+    rows = m.shape[0]
+    labels = np.zeros(max(rows, 1), dtype=np.uint32)
+    n = C.c_uint32()
+    check(_lib.load().kpop_distance_clusters(_p(_nz(m, np.float64), C.c_double), rows, len(metric), _p(_nz(metric, np.float64), C.c_double), int(kind),
+                                             float(p), 1 if normalize else 0, float(max_distance), _p(labels, C.c_uint32), C.byref(n)))
+    return labels[:rows], int(n.value)

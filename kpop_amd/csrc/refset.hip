@@ -117,7 +117,7 @@ static int check_handle(const kpop_refset *rs, const char *who) {
   return 0;
 }
 
-int refset_check_handle(const kpop_refset *rs, const char *who) { return check_handle(rs, who); }  // (within.hip)
+int refset_check_handle(const kpop_refset *rs, const char *who) { return check_handle(rs, who); }  // (within.hip, clusters.hip)
 
 // the common part of create and wrap: arguments, the handle, the per-row arrays (rows and metric are the caller's business)
 static int make_set(const char *who, uint32_t r1, uint32_t n_dims, int kind, double p, int normalize, uint32_t capacity, kpop_refset **out) {
