@@ -688,6 +688,43 @@ int kpop_dev_clusters_within(kpop_refset *rs, double max_distance, uint32_t know
 int kpop_distance_clusters(const double *m, uint32_t rows, uint32_t n_dims, const double *metric, int kind, double p,
                            int normalize, double max_distance, uint32_t *labels, uint32_t *n_clusters);
 
+/* ------------------------------------------------- single-linkage tree (minimum spanning forest of a resident set)
+ * The graph of the block above: nodes are the set's r1 rows, d(j, i) the reference chain's distance (lib/Space.ml:182-205
+ * with the adaptors of lib/Matrix.ml:243-250), symmetric bit for bit, so that an edge is an unordered pair written i < j;
+ * a NaN distance is no edge; no kpop_tune setting is read.  An edge exists iff d <= max_distance (+inf: every pair whose
+ * distance is a number, +inf distances included; negative: none; NaN: KPOP_ERR_INVALID).  Edges are ordered by
+ * (d with -0 taken as +0, i, j) ascending -- a strict total order, under which the minimum spanning forest is UNIQUE: the
+ * result is defined without reference to an algorithm and is the same bits on every run.  *n_edges = r1 - (the number of
+ * components at max_distance); edge_i[e] < edge_j[e] with edge_dist[e] (a zero as +0), e in [0, *n_edges), listed in
+ * that order; room is the caller's: r1 - 1 entries each (none for r1 <= 1).  labels[r1] (may be NULL) are what
+ * kpop_clusters_within(rs, max_distance, 0, ...) returns, bit for bit.  r1 = 0: KPOP_OK and *n_edges = 0.
+ * THE CUT: for any T <= max_distance, uniting the ends of the edges with edge_dist <= T (kpop_forest_cut) gives exactly
+ * the labels and the count of kpop_clusters_within at T -- one forest answers every threshold.  Neither the r1 x r1
+ * matrix nor a neighbour list is formed.  The set's limits, slot and thread ownership hold as for every call on a set. */
+/* (lib/Space.ml:182-205; lib/Matrix.ml:243-250.)  Host arrays.  Synchronises.                                           */
+int kpop_spanning_forest(kpop_refset *rs, double max_distance, uint32_t *n_edges, uint32_t *edge_i, uint32_t *edge_j,
+                         double *edge_dist, uint32_t *labels);
+/* bytes of d_work for kpop_dev_spanning_forest (lib/Space.ml:182-205 over the set against itself, see the block above),
+   for the set's r1 at the time of the call                                                                             */
+uint64_t kpop_dev_spanning_forest_workspace_bytes(const kpop_refset *rs);
+/* (lib/Space.ml:182-205; lib/Matrix.ml:243-250.)  Enqueues only: ceil(log2 r1) rounds, each of which returns at once
+   when the round before added no edge; nothing is read back.  d_n_edges[1], d_edge_i / d_edge_j / d_edge_dist[r1 - 1]
+   (the first *d_n_edges written), d_labels[r1] or NULL.                                                                 */
+int kpop_dev_spanning_forest(kpop_refset *rs, double max_distance, void *d_work, uint32_t *d_n_edges, uint32_t *d_edge_i,
+                             uint32_t *d_edge_j, double *d_edge_dist, uint32_t *d_labels, void *stream);
+/* unprepared convenience (lib/Matrix.ml:191-266 for the distances, m against itself): a temporary set over m, then
+   kpop_spanning_forest                                                                                                  */
+int kpop_distance_spanning_forest(const double *m, uint32_t rows, uint32_t n_dims, const double *metric, int kind,
+                                  double p, int normalize, double max_distance, uint32_t *n_edges, uint32_t *edge_i,
+                                  uint32_t *edge_j, double *edge_dist, uint32_t *labels);
+/* pure host arithmetic, no GPU and no kpop_init: the connected components of ANY list of edges i < j < r1 (a forest or
+   not) cut at T -- the edges with edge_dist <= T united (a NaN joins nothing), labels[i] the smallest row index of row i's
+   component, *n_clusters their number.  Over a forest of kpop_spanning_forest and T <= its max_distance: the labels of
+   the reference chain's distances (lib/Space.ml:182-205; lib/Matrix.ml:243-250) at T.  KPOP_ERR_INVALID for a NaN T and
+   for an edge that is not i < j < r1.                                                                                   */
+int kpop_forest_cut(uint32_t r1, uint32_t n_edges, const uint32_t *edge_i, const uint32_t *edge_j,
+                    const double *edge_dist, double T, uint32_t *labels, uint32_t *n_clusters);
+
 /* ------------------------------------------------- k-mer database (KPopCountDB)
  * the operations of lib/KMerDB.ml that touch every count.  A database is the reference's
  * `storage: I32BAVector.t array` (lib/KMerDB.ml:54-63): n_cols spectra ("columns"), each a vector of n_rows int32

@@ -172,6 +172,12 @@ SIGNATURES = {
     "kpop_dev_clusters_within_workspace_bytes": (C.c_uint64, [vp]),
     "kpop_dev_clusters_within": (C.c_int, [vp, C.c_double, C.c_uint32, vp, vp, vp, vp]),
     "kpop_distance_clusters": (C.c_int, [f64p, C.c_uint32, C.c_uint32, f64p, C.c_int, C.c_double, C.c_int, C.c_double, u32p, u32p]),
+    "kpop_spanning_forest": (C.c_int, [vp, C.c_double, u32p, u32p, u32p, f64p, u32p]),
+    "kpop_dev_spanning_forest_workspace_bytes": (C.c_uint64, [vp]),
+    "kpop_dev_spanning_forest": (C.c_int, [vp, C.c_double, vp, vp, vp, vp, vp, vp, vp]),
+    "kpop_distance_spanning_forest": (C.c_int, [f64p, C.c_uint32, C.c_uint32, f64p, C.c_int, C.c_double, C.c_int, C.c_double, u32p, u32p, u32p, f64p,
+                                                u32p]),
+    "kpop_forest_cut": (C.c_int, [C.c_uint32, C.c_uint32, u32p, u32p, f64p, C.c_double, u32p, u32p]),
 }
 
 

@@ -844,6 +844,22 @@ class RefSet:
         check(_lib.load().kpop_clusters_within(self._h, float(max_distance), known_rows, _p(labels, C.c_uint32), C.byref(n)))
         return labels[:r1], int(n.value)
 
+    def spanning_forest(self, max_distance=float("inf")):
+        """The single-linkage tree of the set: the minimum spanning forest of the graph that joins rows i < j iff d(j, i) <= max_distance,
+        under the order (d, i, j) -> (edge_i u32, edge_j u32, edge_dist f64, labels u32 [r1]).  The order is strict, so the forest is
+        unique: the same bits on every run, the edges listed ascending.  labels are clusters(max_distance)'s; forest_cut of the edges
+        at any T <= max_distance gives clusters(T) (kpop_spanning_forest, include/kpop_hip.h)."""
+        r1 = self.info()["r1"]
+        room = max(r1 - 1, 1)
+        ei, ej = np.zeros(room, dtype=np.uint32), np.zeros(room, dtype=np.uint32)
+        ed = np.zeros(room, dtype=np.float64)
+        labels = np.zeros(max(r1, 1), dtype=np.uint32)
+        n = C.c_uint32()
+        check(_lib.load().kpop_spanning_forest(self._h, float(max_distance), C.byref(n), _p(ei, C.c_uint32), _p(ej, C.c_uint32), _p(ed, C.c_double),
+                                               _p(labels, C.c_uint32)))
+        n = int(n.value)
+        return ei[:n], ej[:n], ed[:n], labels[:r1]
+
     def free(self):
         if self._h is not None and self._h.value:
             check(_lib.load().kpop_refset_free(self._h))
@@ -1039,3 +1055,50 @@ def distance_clusters(m, metric, kind=EUCLIDEAN, p=2.0, normalize=True, max_dist
     check(_lib.load().kpop_distance_clusters(_p(_nz(m, np.float64), C.c_double), rows, len(metric), _p(_nz(metric, np.float64), C.c_double), int(kind),
                                              float(p), 1 if normalize else 0, float(max_distance), _p(labels, C.c_uint32), C.byref(n)))
     return labels[:rows], int(n.value)
+
+
+def dev_spanning_forest_workspace_bytes(rs):
+    """the size of d_work for dev_spanning_forest, for the set's r1 at the time of the call"""
+    return int(_lib.load().kpop_dev_spanning_forest_workspace_bytes(rs.handle))
+
+
+def dev_spanning_forest(rs, max_distance, d_work, d_n_edges, d_edge_i, d_edge_j, d_edge_dist, d_labels=None, stream=0):
+    """enqueue only: d_n_edges[1] (u32), d_edge_i / d_edge_j (u32) and d_edge_dist (f64) of r1 - 1 entries each, the first
+    *d_n_edges written; d_labels[r1] (u32) or None"""
+    check(_lib.load().kpop_dev_spanning_forest(rs.handle, float(max_distance), d_work, d_n_edges, d_edge_i, d_edge_j, d_edge_dist, d_labels, stream))
+
+
+def distance_spanning_forest(m, metric, kind=EUCLIDEAN, p=2.0, normalize=True, max_distance=float("inf")):
+    """RefSet(m, ...).spanning_forest(max_distance) without keeping the set: one call of kpop_distance_spanning_forest
+    -> (edge_i, edge_j, edge_dist, labels)"""
+    m, metric = _c(m, np.float64), _c(metric, np.float64)
+    if m.ndim != 2 or m.shape[1] != len(metric):
+        raise ValueError("Incompatible_geometries")
+    rows = m.shape[0]
+    room = max(rows - 1, 1)
+    ei, ej = np.zeros(room, dtype=np.uint32), np.zeros(room, dtype=np.uint32)
+    ed = np.zeros(room, dtype=np.float64)
+    labels = np.zeros(max(rows, 1), dtype=np.uint32)
+    n = C.c_uint32()
+    check(_lib.load().kpop_distance_spanning_forest(_p(_nz(m, np.float64), C.c_double), rows, len(metric), _p(_nz(metric, np.float64), C.c_double),
+                                                    int(kind), float(p), 1 if normalize else 0, float(max_distance), C.byref(n), _p(ei, C.c_uint32),
+                                                    _p(ej, C.c_uint32), _p(ed, C.c_double), _p(labels, C.c_uint32)))
+    n = int(n.value)
+    return ei[:n], ej[:n], ed[:n], labels[:rows]
+
+
+def forest_cut(r1, edge_i, edge_j, edge_dist, T):
+    """The connected components of a list of edges cut at T (the edges with edge_dist <= T united) -> (labels u32 [r1], n_clusters),
+    labels[i] the smallest row index of row i's component.  Host arithmetic alone: no GPU, no init.  Over a spanning_forest and
+    T <= its max_distance: RefSet.clusters(T), exactly (kpop_forest_cut, include/kpop_hip.h)."""
+    ei = np.ascontiguousarray(edge_i, dtype=np.uint32)
+    ej = np.ascontiguousarray(edge_j, dtype=np.uint32)
+    ed = np.ascontiguousarray(edge_dist, dtype=np.float64)
+    if not (ei.ndim == ej.ndim == ed.ndim == 1 and len(ei) == len(ej) == len(ed)):
+        raise ValueError("edge_i, edge_j and edge_dist: three lists of one length")
+    r1, n_edges = int(r1), len(ei)
+    labels = np.zeros(max(r1, 1), dtype=np.uint32)
+    n = C.c_uint32()
+    check(_lib.load().kpop_forest_cut(r1, n_edges, _p(_nz(ei, np.uint32), C.c_uint32), _p(_nz(ej, np.uint32), C.c_uint32),
+                                      _p(_nz(ed, np.float64), C.c_double), float(T), _p(labels, C.c_uint32), C.byref(n)))
+    return labels[:r1], int(n.value)

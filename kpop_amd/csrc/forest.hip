@@ -1,0 +1,597 @@
+// forest.hip -- the single-linkage tree of a resident set: its minimum spanning forest.
+//
+//   The graph of clusters.hip: the set's r1 rows, i < j joined iff d(j, i) <= max_distance, d the reference chain's distance
+//   (lib/Space.ml:182-205 with the adaptors of lib/Matrix.ml:243-250), symmetric bit for bit, a NaN no edge; no kpop_tune setting is
+//   read.  Edges are ordered by (d with -0 taken as +0, i, j) ascending: a STRICT total order, under which the minimum spanning
+//   forest is unique -- the result is defined without reference to an algorithm and is the same bits on every run.
+//
+// Boruvka rounds over the implicit complete graph; neither a matrix nor a neighbour list is formed.  A round:
+//   forest_tile_labels_kernel  per tile of w rows: the label its rows share, or "mixed" -- a tile of the pass below whose rows and
+//                              columns all carry one label holds no foreign pair and is skipped (the late rounds are mostly that)
+//   forest_nearest_kernel      per row, the least allowed edge to a row of ANOTHER component.  The arithmetic of
+//                              clusters_tile_kernel (clusters.hip), operation for operation: a pair's bits are the chain's.  A
+//                              workgroup owns a strip of TJ rows and walks the column tiles of its segment of the set, columns
+//                              ascending; every thread keeps the best (key, column) of its TY rows in registers, the threads of a
+//                              row are neighbouring lanes and reduce with shuffles, one store a row and segment.  For a fixed row r
+//                              the order of the edges {r, c} is (d, c): whichever side of r the columns lie on, (min, max) ascends
+//                              with c.  Each pair is computed twice (once from either end); the key is 96 bits, which no atomic of
+//                              gfx950 holds, and this shape needs none
+//   forest_row_min_kernel      the least of a row's segments; atomicMin of its key onto the row's component (a distance's key: its
+//                              bits mapped so that doubles order as unsigned integers, negative ones included)
+//   forest_comp_edge_kernel    among the rows that hold their component's least key: atomicMin of (i << 32 | j), i < j
+//   forest_link_kernel         a component emits its edge unless the component at the other end chose the SAME edge and has the
+//                              smaller label (the edge is then emitted once, by that one), and unites with the other end: the
+//                              lock-free union of clusters.hip, the larger root hooked under the smaller with one compare-and-swap
+//   forest_flatten_kernel      labels[i] = the root of i, the smallest index of its component: section 6d's labels when the rounds end
+// No cycle can form: under a strict total order the least edge that leaves a component belongs to THE minimum spanning forest (the
+// cut property, without ties to break), so every edge emitted in any round is an edge of that one forest, and a subset of a forest
+// holds no cycle; the only edge two components can both choose is the same edge, which is emitted once.
+// Components that can still merge at least halve a round, so ceil(log2 r1) rounds always suffice.  The device form enqueues that
+// many; every kernel of a round returns at once when the word of the round before says that it added no edge -- nothing is read
+// back.  The host form reads the word and stops.  Edges arrive in any order; they are sorted on the device by (d, i, j): two stable
+// radix sorts (radix_sort.h), the pair first, the distance's key second.
+// The same copy of the staging-and-accumulate loop as clusters.hip's and within.hip's, kept here so that those kernels stay the
+// kernels they were.
+#include <algorithm>
+
+#include "common.h"
+#include "distance_routes.h"
+#include "radix_sort.h"
+#include "refset.h"
+#include "space_ops.h"
+
+namespace kpop {
+
+constexpr int kFDC = 16, kFMaxW = 64, kFMaxTJ = 256, kFMaxSeg = 8, kFMaxRounds = 32;
+constexpr uint32_t kFMixed = 0xFFFFFFFFu;  // (no label: labels are row indices, below r1 <= 2^32 - 1)
+constexpr uint64_t kFNone = ~0ull;         // (no key: dist_key maps only a NaN's bits there, and a NaN is never a key)
+
+// a distance that is a number -> a key that orders as the distance does; -0 is taken as +0
+__device__ __forceinline__ uint64_t dist_key(double d) {
+  if (d == 0.0) d = 0.0;
+  const uint64_t b = (uint64_t)__double_as_longlong(d);
+  return (b >> 63) ? ~b : (b | (1ull << 63));
+}
+__device__ __forceinline__ double key_dist(uint64_t k) { return __longlong_as_double((long long)((k >> 63) ? (k & ~(1ull << 63)) : ~k)); }
+
+// clusters.hip's union-find, on words that many workgroups read and write at once: relaxed atomics at the device's scope
+__device__ __forceinline__ uint32_t fuf_load(uint32_t *q) { return __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+__device__ __forceinline__ uint32_t fuf_find(uint32_t *parent, uint32_t x) {
+  for (;;) {
+    const uint32_t q = fuf_load(parent + x);
+    if (q == x) return x;
+    const uint32_t g = fuf_load(parent + q);
+    if (g == q) return q;
+    __hip_atomic_store(parent + x, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    x = g;
+  }
+}
+
+__device__ __forceinline__ uint32_t fuf_find_readonly(uint32_t *parent, uint32_t x) {
+  for (;;) {
+    const uint32_t q = fuf_load(parent + x);
+    if (q == x) return x;
+    x = q;
+  }
+}
+
+// only a root is ever hooked, and only under a smaller index: acyclic, and the last root of a component is its smallest index
+__device__ __forceinline__ void fuf_unite(uint32_t *parent, uint32_t a, uint32_t b) {
+  for (;;) {
+    a = fuf_find(parent, a);
+    b = fuf_find(parent, b);
+    if (a == b) return;
+    const uint32_t hi = max(a, b), lo = min(a, b);
+    uint32_t expected = hi;
+    if (__hip_atomic_compare_exchange_strong(parent + hi, &expected, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+    a = hi;  // somebody else hooked hi in the meantime: from there again
+    b = lo;
+  }
+}
+
+#define FOREST_GATE() \
+  if (gate && *gate == 0) return  // the round before added no edge: the forest is complete
+
+__global__ __launch_bounds__(256) void forest_init_kernel(uint32_t *__restrict__ lab, uint32_t *__restrict__ par, uint64_t *__restrict__ comp_k,
+                                                          uint64_t *__restrict__ comp_e, uint64_t *__restrict__ out_k, uint64_t *__restrict__ out_e, uint32_t r1,
+                                                          uint32_t m) {
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < r1; i += (uint64_t)gridDim.x * 256) {
+    lab[i] = (uint32_t)i;
+    par[i] = (uint32_t)i;
+    comp_k[i] = kFNone;
+    comp_e[i] = kFNone;
+    if (i < m) {
+      out_k[i] = kFNone;  // (a slot no edge takes sorts behind every edge)
+      out_e[i] = kFNone;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void forest_tile_labels_kernel(const uint32_t *__restrict__ lab, uint32_t r1, uint32_t w, uint32_t n_ct,
+                                                                 uint32_t *__restrict__ tile_lab, const uint32_t *gate) {
+  FOREST_GATE();
+  for (uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x; t < n_ct; t += (uint64_t)gridDim.x * 256) {
+    const uint64_t i0 = t * w, i1 = (i0 + w < r1) ? i0 + w : (uint64_t)r1;
+    uint32_t l = lab[i0];
+    for (uint64_t i = i0 + 1; i < i1; ++i)
+      if (lab[i] != l) {
+        l = kFMixed;
+        break;
+      }
+    tile_lab[t] = l;
+  }
+}
+
+// a: the set's rows as the chain reads them (divided by their norms when the set normalises), both operands.  Strip blockIdx.x:
+// rows j0 .. j0 + TJ, TJ = TY n_rg = kf w; segment blockIdx.y: the column tiles (w rows of the set each) t_begin .. t_end.  A thread
+// 4 columns x TY rows, the dimensions ascending in one thread, 16 at a time through LDS: clusters_tile_kernel's.  The next step's
+// operands -- the tile's next 16 dimensions, or the first of the next tile that is not skipped -- are loaded under the arithmetic.
+template <int KIND, int TY>
+__global__ __launch_bounds__(256, 1) void forest_nearest_kernel(const double *__restrict__ a, uint32_t w, uint32_t r1, uint32_t n_dims,
+                                                                const double *__restrict__ metric, double p, double max_distance, uint32_t n_cg,
+                                                                uint32_t n_rg, uint32_t kf, uint32_t n_ct, uint32_t tiles_per_seg,
+                                                                const uint32_t *__restrict__ lab, const uint32_t *__restrict__ tile_lab,
+                                                                uint64_t *__restrict__ part_k, uint32_t *__restrict__ part_c, const uint32_t *gate) {
+  FOREST_GATE();
+  __shared__ __attribute__((aligned(16))) double As[kFDC][kFMaxW + 2];
+  __shared__ __attribute__((aligned(16))) double Bs[kFDC][kFMaxTJ + 2];
+  __shared__ double s_metric[kFDC];
+  const uint32_t TJ = TY * n_rg;
+  const uint32_t strip = blockIdx.x, seg = blockIdx.y;
+  const uint32_t j0 = strip * TJ, j1 = min(r1, j0 + TJ);  // (the grid has div_up(r1, TJ) strips: j0 < r1)
+  const uint32_t t_begin = min(n_ct, seg * tiles_per_seg), t_end = min(n_ct, t_begin + tiles_per_seg);
+  // the label all rows of the strip share, if they do
+  uint32_t strip_lab = tile_lab[strip * kf];
+  for (uint32_t q = 1; q < kf; ++q)
+    if (strip * kf + q < n_ct && tile_lab[strip * kf + q] != strip_lab) strip_lab = kFMixed;
+  auto next_tile = [&](uint32_t t) {  // the first tile from t on that holds a foreign pair (the same for every thread)
+    while (t < t_end && strip_lab != kFMixed && tile_lab[t] == strip_lab) ++t;
+    return t;
+  };
+  const uint32_t cg = threadIdx.x % n_cg, rg = threadIdx.x / n_cg;
+  const bool worker = rg < n_rg;
+  const uint32_t ti = cg * 4, tj = (worker ? rg : 0) * TY;
+  uint32_t lj[TY], best_c[TY];
+  uint64_t best_k[TY];
+#pragma unroll
+  for (int yy = 0; yy < TY; ++yy) {
+    lj[yy] = (j0 + tj + yy < j1) ? lab[j0 + tj + yy] : 0u;
+    best_k[yy] = kFNone;
+    best_c[yy] = 0u;
+  }
+  constexpr int NA = kFMaxW * kFDC / 256, NB = kFMaxTJ * kFDC / 256;
+  double ra[NA], rb[NB];
+  const uint32_t sc = threadIdx.x % kFDC, rbase = threadIdx.x / kFDC;
+  auto prefetch = [&](uint32_t i0, uint32_t c0) {
+    const uint32_t i1 = min(r1, i0 + w);
+    const bool cok = c0 + sc < n_dims;
+#pragma unroll
+    for (int q = 0; q < NA; ++q) {
+      const uint32_t row = rbase + q * 16;
+      ra[q] = (cok && row < w && i0 + row < i1) ? a[(uint64_t)(i0 + row) * n_dims + c0 + sc] : 0.0;
+    }
+#pragma unroll
+    for (int q = 0; q < NB; ++q) {
+      const uint32_t row = rbase + q * 16;
+      rb[q] = (cok && row < TJ && j0 + row < j1) ? a[(uint64_t)(j0 + row) * n_dims + c0 + sc] : 0.0;
+    }
+  };
+  uint32_t t = next_tile(t_begin);
+  if (t < t_end) prefetch(t * w, 0);
+  while (t < t_end) {
+    const uint32_t t_next = next_tile(t + 1);
+    const uint32_t i0 = t * w, i1 = min(r1, i0 + w);
+    uint32_t li[4];
+#pragma unroll
+    for (int x = 0; x < 4; ++x) li[x] = (i0 + ti + x < i1) ? lab[i0 + ti + x] : 0u;
+    double acc[TY][4];
+#pragma unroll
+    for (int yy = 0; yy < TY; ++yy)
+#pragma unroll
+      for (int x = 0; x < 4; ++x) acc[yy][x] = 0.0;
+    for (uint32_t c0 = 0; c0 < n_dims; c0 += kFDC) {
+      __syncthreads();
+#pragma unroll
+      for (int q = 0; q < NA; ++q) As[sc][rbase + q * 16] = ra[q];
+#pragma unroll
+      for (int q = 0; q < NB; ++q) Bs[sc][rbase + q * 16] = rb[q];
+      if (threadIdx.x < kFDC) s_metric[threadIdx.x] = (c0 + threadIdx.x < n_dims) ? metric[c0 + threadIdx.x] : 0.0;
+      __syncthreads();
+      if (c0 + kFDC < n_dims) prefetch(i0, c0 + kFDC);
+      else if (t_next < t_end) prefetch(t_next * w, 0);
+      const uint32_t lim = min((uint32_t)kFDC, n_dims - c0);
+      if (worker) {
+        for (uint32_t cc = 0; cc < lim; ++cc) {
+          double av[4], bv[TY];
+#pragma unroll
+          for (int x = 0; x < 4; ++x) av[x] = As[cc][ti + x];
+#pragma unroll
+          for (int yy = 0; yy < TY; ++yy) bv[yy] = Bs[cc][tj + yy];
+          const double mc = s_metric[cc];
+#pragma unroll
+          for (int yy = 0; yy < TY; ++yy)
+#pragma unroll
+            for (int x = 0; x < 4; ++x) {
+              // lib/Space.ml:192-200: diff = a -. b ; acc +. (diff *. diff *. m)
+              double diff = __dsub_rn(av[x], bv[yy]);
+              acc[yy][x] = __dadd_rn(acc[yy][x], component<KIND>(diff, mc, p));
+            }
+        }
+      }
+    }
+    // the epilogue: compare where clusters_tile_kernel compares (a NaN compares false: no edge), a row of another component only
+    // (which the row itself never is); columns ascend within the tile and from tile to tile, so that `below` alone keeps, among
+    // equal keys, the least column
+    if (worker) {
+#pragma unroll
+      for (int yy = 0; yy < TY; ++yy)
+#pragma unroll
+        for (int x = 0; x < 4; ++x) {
+          const double d = scale_distance<KIND>(acc[yy][x], p);
+          const uint32_t i = i0 + ti + x, j = j0 + tj + yy;
+          if (j < j1 && i < i1 && li[x] != lj[yy] && d <= max_distance) {
+            const uint64_t key = dist_key(d);
+            if (key < best_k[yy]) {
+              best_k[yy] = key;
+              best_c[yy] = i;
+            }
+          }
+        }
+    }
+    t = t_next;
+  }
+  // the n_cg threads of a row are neighbouring lanes of one wavefront (n_cg divides 64, a row group starts at a multiple of it)
+  for (uint32_t o = n_cg >> 1; o > 0; o >>= 1) {
+#pragma unroll
+    for (int yy = 0; yy < TY; ++yy) {
+      const uint64_t ok = (uint64_t)__shfl_xor((unsigned long long)best_k[yy], (int)o, 64);
+      const uint32_t oc = (uint32_t)__shfl_xor((int)best_c[yy], (int)o, 64);
+      if (ok < best_k[yy] || (ok == best_k[yy] && oc < best_c[yy])) {
+        best_k[yy] = ok;
+        best_c[yy] = oc;
+      }
+    }
+  }
+  if (worker && cg == 0) {
+#pragma unroll
+    for (int yy = 0; yy < TY; ++yy) {
+      const uint32_t j = j0 + tj + yy;
+      if (j < j1) {
+        part_k[(uint64_t)seg * r1 + j] = best_k[yy];
+        part_c[(uint64_t)seg * r1 + j] = best_c[yy];
+      }
+    }
+  }
+}
+
+// the segments hold ascending columns: among equal keys the first segment's
+__global__ __launch_bounds__(256) void forest_row_min_kernel(uint64_t *__restrict__ part_k, uint32_t *__restrict__ part_c, uint32_t n_seg, uint32_t r1,
+                                                             const uint32_t *__restrict__ lab, uint64_t *comp_k, const uint32_t *gate) {
+  FOREST_GATE();
+  for (uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x; r < r1; r += (uint64_t)gridDim.x * 256) {
+    uint64_t k = part_k[r];
+    uint32_t c = part_c[r];
+    for (uint32_t s = 1; s < n_seg; ++s) {
+      const uint64_t kk = part_k[(uint64_t)s * r1 + r];
+      if (kk < k) {
+        k = kk;
+        c = part_c[(uint64_t)s * r1 + r];
+      }
+    }
+    part_k[r] = k;
+    part_c[r] = c;
+    if (k != kFNone) atomicMin((unsigned long long *)(comp_k + lab[r]), (unsigned long long)k);
+  }
+}
+
+__global__ __launch_bounds__(256) void forest_comp_edge_kernel(const uint64_t *__restrict__ part_k, const uint32_t *__restrict__ part_c, uint32_t r1,
+                                                               const uint32_t *__restrict__ lab, const uint64_t *__restrict__ comp_k, uint64_t *comp_e,
+                                                               const uint32_t *gate) {
+  FOREST_GATE();
+  for (uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x; r < r1; r += (uint64_t)gridDim.x * 256) {
+    const uint64_t k = part_k[r];
+    if (k == kFNone || k != comp_k[lab[r]]) continue;
+    const uint32_t c = part_c[r], lo = min((uint32_t)r, c), hi = max((uint32_t)r, c);
+    atomicMin((unsigned long long *)(comp_e + lab[r]), ((unsigned long long)lo << 32) | hi);
+  }
+}
+
+// lab, comp_k, comp_e: the round's, read only here; the unions go into par
+__global__ __launch_bounds__(256) void forest_link_kernel(const uint32_t *__restrict__ lab, const uint64_t *__restrict__ comp_k,
+                                                          const uint64_t *__restrict__ comp_e, uint32_t r1, uint32_t m, uint32_t *par, uint32_t *n_edges,
+                                                          uint64_t *__restrict__ out_k, uint64_t *__restrict__ out_e, uint32_t *added, const uint32_t *gate) {
+  FOREST_GATE();
+  for (uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x; r < r1; r += (uint64_t)gridDim.x * 256) {
+    const uint32_t R = (uint32_t)r;
+    if (lab[R] != R) continue;
+    const uint64_t k = comp_k[R];
+    if (k == kFNone) continue;  // nothing within max_distance leaves this component: it is final
+    const uint64_t e = comp_e[R];
+    const uint32_t i = (uint32_t)(e >> 32), j = (uint32_t)e;
+    const uint32_t li = lab[i], other = (li == R) ? lab[j] : li;
+    if (comp_k[other] == k && comp_e[other] == e && other < R) continue;  // the same edge from its other end: emitted and united there
+    const uint32_t pos = atomicAdd(n_edges, 1u);
+    if (pos < m) {  // (a forest on r1 rows has at most m = r1 - 1 edges)
+      out_k[pos] = k;
+      out_e[pos] = e;
+    }
+    atomicAdd(added, 1u);
+    fuf_unite(par, R, other);
+  }
+}
+
+// every row's root into par and lab, the components' words cleared for the next round.  A root is a row whose word is its own
+// index: no store here changes that, and a word on somebody's path is that row's ancestor before the store and after it
+__global__ __launch_bounds__(256) void forest_flatten_kernel(uint32_t *par, uint32_t *__restrict__ lab, uint64_t *__restrict__ comp_k,
+                                                             uint64_t *__restrict__ comp_e, uint32_t r1, const uint32_t *gate) {
+  FOREST_GATE();
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < r1; i += (uint64_t)gridDim.x * 256) {
+    const uint32_t root = fuf_find_readonly(par, (uint32_t)i);
+    if (root != (uint32_t)i) __hip_atomic_store(par + i, root, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    lab[i] = root;
+    comp_k[i] = kFNone;
+    comp_e[i] = kFNone;
+  }
+}
+
+// the first sort's key: the pair in 2 jb bits (i, j < 2^jb); the value that travels is the edge's slot
+__global__ __launch_bounds__(256) void forest_pair_keys_kernel(const uint64_t *__restrict__ out_e, uint32_t m, uint32_t jb, uint64_t *__restrict__ keys,
+                                                               uint32_t *__restrict__ vals) {
+  for (uint64_t q = (uint64_t)blockIdx.x * 256 + threadIdx.x; q < m; q += (uint64_t)gridDim.x * 256) {
+    const uint64_t e = out_e[q];
+    keys[q] = ((e >> 32) << jb) | (e & 0xFFFFFFFFull);  // (an empty slot: any key, its distance's key puts it last)
+    vals[q] = (uint32_t)q;
+  }
+}
+
+// the second sort's key: the distance's, in the order the first sort left
+__global__ __launch_bounds__(256) void forest_dist_keys_kernel(const uint64_t *__restrict__ out_k, const uint32_t *__restrict__ slot, uint32_t m,
+                                                               uint64_t *__restrict__ keys, uint32_t *__restrict__ vals) {
+  for (uint64_t q = (uint64_t)blockIdx.x * 256 + threadIdx.x; q < m; q += (uint64_t)gridDim.x * 256) {
+    keys[q] = out_k[slot[q]];
+    vals[q] = slot[q];
+  }
+}
+
+__global__ __launch_bounds__(256) void forest_write_kernel(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ slot,
+                                                           const uint64_t *__restrict__ out_e, const uint32_t *__restrict__ n_edges, uint32_t m,
+                                                           uint32_t *__restrict__ edge_i, uint32_t *__restrict__ edge_j, double *__restrict__ edge_dist) {
+  const uint32_t n = min(*n_edges, m);
+  for (uint64_t q = (uint64_t)blockIdx.x * 256 + threadIdx.x; q < n; q += (uint64_t)gridDim.x * 256) {
+    const uint64_t e = out_e[slot[q]];
+    edge_i[q] = (uint32_t)(e >> 32);
+    edge_j[q] = (uint32_t)e;
+    edge_dist[q] = key_dist(keys[q]);
+  }
+}
+
+// the workspace, carved: sized for the set's r1 alone
+struct ForestWork {
+  uint32_t *words, *lab, *par, *tile_lab, *part_c, *va, *vb, *v2a, *v2b;
+  uint64_t *comp_k, *comp_e, *part_k, *out_k, *out_e, *ka, *kb, *k2a, *k2b;
+  void *radix;
+  uint64_t bytes;
+};
+
+static ForestWork forest_carve(void *base, uint32_t r1) {
+  const uint64_t n = std::max(r1, 1u), m = std::max(r1, 2u) - 1;
+  char *c = reinterpret_cast<char *>(base);
+  uint64_t off = 0;
+  auto take = [&](uint64_t b) {
+    char *q = c + off;
+    off += (b + 255) & ~255ull;
+    return q;
+  };
+  ForestWork f;
+  f.words = reinterpret_cast<uint32_t *>(take(4 * (kFMaxRounds + 1)));  // what each round added
+  f.lab = reinterpret_cast<uint32_t *>(take(n * 4));
+  f.par = reinterpret_cast<uint32_t *>(take(n * 4));
+  f.tile_lab = reinterpret_cast<uint32_t *>(take(n * 4));
+  f.comp_k = reinterpret_cast<uint64_t *>(take(n * 8));
+  f.comp_e = reinterpret_cast<uint64_t *>(take(n * 8));
+  f.part_k = reinterpret_cast<uint64_t *>(take(n * 8 * kFMaxSeg));
+  f.part_c = reinterpret_cast<uint32_t *>(take(n * 4 * kFMaxSeg));
+  f.out_k = reinterpret_cast<uint64_t *>(take(m * 8));
+  f.out_e = reinterpret_cast<uint64_t *>(take(m * 8));
+  f.ka = reinterpret_cast<uint64_t *>(take(m * 8));
+  f.kb = reinterpret_cast<uint64_t *>(take(m * 8));
+  f.k2a = reinterpret_cast<uint64_t *>(take(m * 8));
+  f.k2b = reinterpret_cast<uint64_t *>(take(m * 8));
+  f.va = reinterpret_cast<uint32_t *>(take(m * 4));
+  f.vb = reinterpret_cast<uint32_t *>(take(m * 4));
+  f.v2a = reinterpret_cast<uint32_t *>(take(m * 4));
+  f.v2b = reinterpret_cast<uint32_t *>(take(m * 4));
+  f.radix = take(radix_scratch_bytes(m));
+  f.bytes = off;
+  return f;
+}
+
+template <int KIND>
+static int forest_nearest(const double *a, uint32_t r1, uint32_t n_dims, const double *metric, double p, double max_distance, const ForestWork &f,
+                          uint32_t *lab, uint32_t *n_seg_out, const uint32_t *gate, hipStream_t st) {
+  // clusters_tiles' two shapes (clusters.hip): 32 columns x 256 rows, a thread 4 x 8, for a long set; 64 x 64, a thread 4 x 4, below.
+  // (The choice moves no bit: a pair's chain is one thread's either way.)
+  const bool big = r1 >= 65536;
+  const uint32_t w = big ? 32 : 64, n_cg = w / 4, n_rg = 256 / n_cg, TJ = (big ? 8 : 4) * n_rg, kf = TJ / w;
+  const uint32_t n_ct = div_up(r1, w), strips = div_up(r1, TJ);
+  // the columns in a few segments when the strips alone do not fill the chip twice over
+  const uint32_t want = div_up(2 * (uint64_t)std::max(ctx().n_cus, 1), strips);
+  const uint32_t n_seg_max = std::max(1u, std::min({want, (uint32_t)kFMaxSeg, n_ct}));
+  const uint32_t tiles_per_seg = div_up(n_ct, n_seg_max), n_seg = div_up(n_ct, tiles_per_seg);  // (no segment is empty)
+  *n_seg_out = n_seg;
+  forest_tile_labels_kernel<<<dim3(std::min(div_up(n_ct, 256), 4096u)), dim3(256), 0, st>>>(lab, r1, w, n_ct, f.tile_lab, gate);
+  KPOP_LAUNCH_CHECK();
+  if (strips > 0x7FFFFFFFu) KPOP_FAIL(KPOP_ERR_UNSUPPORTED, "kpop_dev_spanning_forest: %u rows", r1);
+  const dim3 grid(strips, n_seg);
+  if (big)
+    forest_nearest_kernel<KIND, 8><<<grid, dim3(256), 0, st>>>(a, w, r1, n_dims, metric, p, max_distance, n_cg, n_rg, kf, n_ct, tiles_per_seg, lab, f.tile_lab,
+                                                               f.part_k, f.part_c, gate);
+  else
+    forest_nearest_kernel<KIND, 4><<<grid, dim3(256), 0, st>>>(a, w, r1, n_dims, metric, p, max_distance, n_cg, n_rg, kf, n_ct, tiles_per_seg, lab, f.tile_lab,
+                                                               f.part_k, f.part_c, gate);
+  KPOP_LAUNCH_CHECK();
+  return 0;
+}
+
+static uint32_t forest_rounds(uint32_t r1) {  // ceil(log2 r1)
+  uint32_t rounds = 0;
+  while (rounds < 32 && (1ull << rounds) < r1) ++rounds;
+  return rounds;
+}
+
+// the body of both entry points.  host_reads: after a round, wait for the word that says what it added and stop at zero;
+// otherwise enqueues only
+static int forest_dev(kpop_refset *rs, double max_distance, void *d_work, uint32_t *d_n_edges, uint32_t *d_edge_i, uint32_t *d_edge_j, double *d_edge_dist,
+                      uint32_t *d_labels, hipStream_t st, bool host_reads, const char *who) {
+  if (max_distance != max_distance) KPOP_FAIL(KPOP_ERR_INVALID, "%s: the distance is not a number", who);
+  if (!d_n_edges) KPOP_FAIL(KPOP_ERR_INVALID, "%s: null count", who);
+  KPOP_HIP(hipMemsetAsync(d_n_edges, 0, 4, st));
+  const uint32_t r1 = rs->r1;
+  if (r1 == 0) return KPOP_OK;
+  if (r1 > 1 && (!d_edge_i || !d_edge_j || !d_edge_dist)) KPOP_FAIL(KPOP_ERR_INVALID, "%s: null edge arrays", who);
+  const ForestWork f = forest_carve(d_work, r1);
+  uint32_t *lab = d_labels ? d_labels : f.lab;
+  const uint32_t m = std::max(r1, 2u) - 1, rows_grid = std::min(div_up(r1, 256), 4096u);
+  KPOP_HIP(hipMemsetAsync(f.words, 0, 4 * (kFMaxRounds + 1), st));
+  forest_init_kernel<<<dim3(rows_grid), dim3(256), 0, st>>>(lab, f.par, f.comp_k, f.comp_e, f.out_k, f.out_e, r1, r1 > 1 ? m : 0);
+  KPOP_LAUNCH_CHECK();
+  if (r1 == 1 || !(max_distance >= 0.0)) return KPOP_OK;  // (no distance is negative: below zero every row stays alone)
+  const double *a = rs->rows;
+  if (rs->normalize) {
+    KPOP_TRY(rs->prepared(st));
+    KPOP_TRY(rs->divided(st, &a));
+  }
+  const uint32_t rounds = forest_rounds(r1);
+  for (uint32_t k = 0; k < rounds; ++k) {
+    const uint32_t *gate = k ? f.words + (k - 1) : nullptr;
+    uint32_t n_seg = 1;
+    switch (rs->kind) {
+      case KPOP_EUCLIDEAN: KPOP_TRY(forest_nearest<KPOP_EUCLIDEAN>(a, r1, rs->n_dims, rs->metric, rs->p, max_distance, f, lab, &n_seg, gate, st)); break;
+      case KPOP_COSINE: KPOP_TRY(forest_nearest<KPOP_COSINE>(a, r1, rs->n_dims, rs->metric, rs->p, max_distance, f, lab, &n_seg, gate, st)); break;
+      default: KPOP_TRY(forest_nearest<KPOP_MINKOWSKI>(a, r1, rs->n_dims, rs->metric, rs->p, max_distance, f, lab, &n_seg, gate, st)); break;
+    }
+    forest_row_min_kernel<<<dim3(rows_grid), dim3(256), 0, st>>>(f.part_k, f.part_c, n_seg, r1, lab, f.comp_k, gate);
+    KPOP_LAUNCH_CHECK();
+    forest_comp_edge_kernel<<<dim3(rows_grid), dim3(256), 0, st>>>(f.part_k, f.part_c, r1, lab, f.comp_k, f.comp_e, gate);
+    KPOP_LAUNCH_CHECK();
+    forest_link_kernel<<<dim3(rows_grid), dim3(256), 0, st>>>(lab, f.comp_k, f.comp_e, r1, m, f.par, d_n_edges, f.out_k, f.out_e, f.words + k, gate);
+    KPOP_LAUNCH_CHECK();
+    forest_flatten_kernel<<<dim3(rows_grid), dim3(256), 0, st>>>(f.par, lab, f.comp_k, f.comp_e, r1, gate);
+    KPOP_LAUNCH_CHECK();
+    if (host_reads) {
+      uint32_t added = 0;
+      KPOP_HIP(hipMemcpyAsync(&added, f.words + k, 4, hipMemcpyDeviceToHost, st));
+      KPOP_HIP(hipStreamSynchronize(st));
+      if (added == 0) break;
+    }
+  }
+  // the order: by the pair, then -- stably -- by the distance's key
+  const uint32_t edges_grid = std::min(div_up(m, 256), 4096u);
+  uint32_t jb = 1;
+  while (jb < 32 && (1ull << jb) < r1) ++jb;
+  forest_pair_keys_kernel<<<dim3(edges_grid), dim3(256), 0, st>>>(f.out_e, m, jb, f.ka, f.va);
+  KPOP_LAUNCH_CHECK();
+  uint64_t *ks = nullptr, *k2s = nullptr;
+  uint32_t *vs = nullptr, *v2s = nullptr;
+  KPOP_TRY(radix_sort_pairs_u64(f.ka, f.kb, f.va, f.vb, m, (int)(2 * jb), f.radix, st, &ks, &vs));
+  forest_dist_keys_kernel<<<dim3(edges_grid), dim3(256), 0, st>>>(f.out_k, vs, m, f.k2a, f.v2a);
+  KPOP_LAUNCH_CHECK();
+  KPOP_TRY(radix_sort_pairs_u64(f.k2a, f.k2b, f.v2a, f.v2b, m, 64, f.radix, st, &k2s, &v2s));
+  forest_write_kernel<<<dim3(edges_grid), dim3(256), 0, st>>>(k2s, v2s, f.out_e, d_n_edges, m, d_edge_i, d_edge_j, d_edge_dist);
+  KPOP_LAUNCH_CHECK();
+  return KPOP_OK;
+}
+
+}  // namespace kpop
+
+using namespace kpop;
+
+extern "C" uint64_t kpop_dev_spanning_forest_workspace_bytes(const kpop_refset *rs) {
+  if (!rs) return 0;
+  return forest_carve(nullptr, rs->r1).bytes;
+}
+
+extern "C" int kpop_dev_spanning_forest(kpop_refset *rs, double max_distance, void *d_work, uint32_t *d_n_edges, uint32_t *d_edge_i, uint32_t *d_edge_j,
+                                        double *d_edge_dist, uint32_t *d_labels, void *stream) {
+  const char *who = "kpop_dev_spanning_forest";
+  KPOP_TRY(refset_check_handle(rs, who));
+  if (!d_work) KPOP_FAIL(KPOP_ERR_INVALID, "%s: null workspace", who);
+  return forest_dev(rs, max_distance, d_work, d_n_edges, d_edge_i, d_edge_j, d_edge_dist, d_labels, as_stream(stream), false, who);
+}
+
+extern "C" int kpop_spanning_forest(kpop_refset *rs, double max_distance, uint32_t *n_edges, uint32_t *edge_i, uint32_t *edge_j, double *edge_dist,
+                                    uint32_t *labels) {
+  const char *who = "kpop_spanning_forest";
+  KPOP_TRY(refset_check_handle(rs, who));
+  ArenaScope scratch;
+  if (max_distance != max_distance) KPOP_FAIL(KPOP_ERR_INVALID, "%s: the distance is not a number", who);
+  const uint32_t r1 = rs->r1;
+  if (!n_edges || (r1 > 1 && (!edge_i || !edge_j || !edge_dist))) KPOP_FAIL(KPOP_ERR_INVALID, "%s: null argument", who);
+  *n_edges = 0;
+  if (r1 == 0) return KPOP_OK;
+  hipStream_t st = nullptr;
+  const uint64_t m = std::max(r1, 2u) - 1;
+  DevBuf work, dn, di, dj, dd, dl;
+  KPOP_TRY(work.alloc(forest_carve(nullptr, r1).bytes));
+  KPOP_TRY(dn.alloc(256));
+  KPOP_TRY(di.alloc(m * 4));
+  KPOP_TRY(dj.alloc(m * 4));
+  KPOP_TRY(dd.alloc(m * 8));
+  KPOP_TRY(dl.alloc((uint64_t)r1 * 4));
+  KPOP_TRY(forest_dev(rs, max_distance, work.p, dn.as<uint32_t>(), di.as<uint32_t>(), dj.as<uint32_t>(), dd.as<double>(), dl.as<uint32_t>(), st, true, who));
+  uint32_t n = 0;
+  KPOP_HIP(hipMemcpyAsync(&n, dn.p, 4, hipMemcpyDeviceToHost, st));
+  KPOP_HIP(hipStreamSynchronize(st));
+  if (n > m) KPOP_FAIL(KPOP_ERR_HIP, "%s: %u edges on %u rows", who, n, r1);  // (cannot happen: a forest)
+  if (n) {
+    KPOP_HIP(hipMemcpyAsync(edge_i, di.p, (uint64_t)n * 4, hipMemcpyDeviceToHost, st));
+    KPOP_HIP(hipMemcpyAsync(edge_j, dj.p, (uint64_t)n * 4, hipMemcpyDeviceToHost, st));
+    KPOP_HIP(hipMemcpyAsync(edge_dist, dd.p, (uint64_t)n * 8, hipMemcpyDeviceToHost, st));
+  }
+  if (labels) KPOP_HIP(hipMemcpyAsync(labels, dl.p, (uint64_t)r1 * 4, hipMemcpyDeviceToHost, st));
+  KPOP_HIP(hipStreamSynchronize(st));
+  *n_edges = n;
+  return KPOP_OK;
+}
+
+extern "C" int kpop_distance_spanning_forest(const double *m, uint32_t rows, uint32_t n_dims, const double *metric, int kind, double p, int normalize,
+                                             double max_distance, uint32_t *n_edges, uint32_t *edge_i, uint32_t *edge_j, double *edge_dist,
+                                             uint32_t *labels) {
+  kpop_refset *rs = nullptr;
+  KPOP_TRY(kpop_refset_create(m, rows, n_dims, metric, kind, p, normalize, 0, &rs));
+  const int rc = kpop_spanning_forest(rs, max_distance, n_edges, edge_i, edge_j, edge_dist, labels);
+  const int rc_free = kpop_refset_free(rs);
+  return rc ? rc : rc_free;
+}
+
+// host arithmetic alone: the union-find of the labels, the larger root under the smaller, over the edges within T
+extern "C" int kpop_forest_cut(uint32_t r1, uint32_t n_edges, const uint32_t *edge_i, const uint32_t *edge_j, const double *edge_dist, double T,
+                               uint32_t *labels, uint32_t *n_clusters) {
+  const char *who = "kpop_forest_cut";
+  if (T != T) KPOP_FAIL(KPOP_ERR_INVALID, "%s: the distance is not a number", who);
+  if (!n_clusters || (r1 && !labels) || (n_edges && (!edge_i || !edge_j || !edge_dist))) KPOP_FAIL(KPOP_ERR_INVALID, "%s: null argument", who);
+  for (uint32_t e = 0; e < n_edges; ++e)
+    if (!(edge_i[e] < edge_j[e] && edge_j[e] < r1))
+      KPOP_FAIL(KPOP_ERR_INVALID, "%s: edge %u joins rows %u and %u of %u (i < j < r1)", who, e, edge_i[e], edge_j[e], r1);
+  for (uint32_t i = 0; i < r1; ++i) labels[i] = i;
+  auto find = [&](uint32_t x) {
+    while (labels[x] != x) {
+      labels[x] = labels[labels[x]];
+      x = labels[x];
+    }
+    return x;
+  };
+  for (uint32_t e = 0; e < n_edges; ++e) {
+    if (!(edge_dist[e] <= T)) continue;  // (a NaN joins nothing)
+    const uint32_t a = find(edge_i[e]), b = find(edge_j[e]);
+    if (a != b) labels[std::max(a, b)] = std::min(a, b);
+  }
+  uint32_t n = 0;
+  for (uint32_t i = 0; i < r1; ++i) {
+    labels[i] = find(i);
+    n += labels[i] == i;
+  }
+  *n_clusters = n;
+  return KPOP_OK;
+}
