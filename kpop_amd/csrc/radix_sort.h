@@ -137,6 +137,9 @@ struct StoreBases {
 
 // Sorts the low `bits` bits' worth of passes; keys ping-pong between a and b.
 // Returns (through *result) the buffer holding the sorted keys.
+// ceil(bits / 8) passes of a whole digit each: the result is the STABLE order on the low 8 * ceil(bits / 8) bits, and it is
+// in a after an even number of passes (none included: bits = 0 or n = 0 leave a untouched) and in b after an odd one; the
+// other buffer holds the pass before.  (Held case by case by tools/probes/src/device_primitives_check.hip.)
 static inline int radix_sort_u64(uint64_t *a, uint64_t *b, uint64_t n, int bits, void *scratch, hipStream_t st,
                                  uint64_t **result) {
   *result = a;

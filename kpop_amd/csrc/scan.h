@@ -1,9 +1,13 @@
 // scan.h -- device-wide exclusive prefix sum (three launches, no inter-workgroup
 // hand-off inside a launch, so no agent-scope protocol is needed).
-//   in(i)        : functor giving the u32 addend of element i
-//   out(i, pre)  : functor receiving the exclusive prefix of element i
+//   in(i)          : functor giving the u32 addend of element i
+//   out(i, pre, v) : functor receiving the exclusive prefix of element i and the addend in(i) gave
 // `d_block_sums` needs scan_blocks(n)+1 u64 entries; the grand total is left in
 // d_block_sums[scan_blocks(n)].
+// CONTRACT: the addends of one tile (kScanTile consecutive elements) total less than 2^32 -- prefixes inside a tile are
+// 32-bit offsets from the tile's 64-bit base.  The grand total may be anything a u64 holds.  Nothing checks the tile bound:
+// beyond it the prefixes of that tile wrap SILENTLY (the tile's sum and the total are still right).  Pinned at the bound,
+// tile totals of 2^32 - 4096 under a grand total beyond 2^32, by tools/probes/src/device_primitives_check.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -16,7 +16,8 @@ namespace kpop {
 // the ~R log^2(64R) compare-exchanges plus cross-lane shuffles of a full sort.
 // The values are compared as the doubles they are (f64 comparisons issue at the full rate, 64-bit integer ones on
 // order-preserving keys do not): there is no NaN among them -- the norms are positive and finite -- and +inf is the
-// padding of the empty slots, never a candidate (hi starts there).
+// padding of the empty slots, never a candidate (hi starts there).  So a REAL +inf among the values is not found either: a
+// target that falls on one comes back as the largest finite value (and as -inf if nothing is finite); the callers keep +inf out.
 template <int R>
 __device__ __forceinline__ double wave_select_rank(const double (&v)[R], uint32_t target) {
   double lo = -INFINITY, hi = INFINITY;
