@@ -725,6 +725,48 @@ int kpop_distance_spanning_forest(const double *m, uint32_t rows, uint32_t n_dim
 int kpop_forest_cut(uint32_t r1, uint32_t n_edges, const uint32_t *edge_i, const uint32_t *edge_j,
                     const double *edge_dist, double T, uint32_t *labels, uint32_t *n_clusters);
 
+/* ------------------------------------------------- k-NN vote (classify query rows against a labelled resident set)
+ * The classifier of the reference's README (README.md:758-775: `--keep-at-most k -s Test Train`, then a count of the
+ * classes among the listed neighbours), on the device.  class_of[r1] gives every row of the set a class in
+ * [0, n_classes); the labels travel with the call, the set stays what it is.  d(j, i) is the reference chain's distance
+ * (lib/Space.ml:182-205 with the adaptors of lib/Matrix.ml:243-250) -- the bits kpop_refset_distance_rowwise writes under
+ * kpop_tune("distance_mfma", 0) -- whatever kpop_tune says.  THE LIST of query row j: the set rows whose distance to j is
+ * a number, ordered by (d with -0 taken as +0, index) ascending; its first k, plus every further row whose distance
+ * equals the k-th one -- eff_len of summarize_distance_matrix_row (lib/Matrix.ml:641-650): whole tie groups; fewer than
+ * k numbers: all of them.  A NaN distance is never a neighbour (a summary line of a row that holds a NaN differs: there
+ * the NaN takes a place in the order); +inf is a number.  THE VOTE: out_n[j] the length of the list, out_class[j] the
+ * class with the most members in it -- among classes with equally many, the one whose nearest member comes first in the
+ * list's order (README.md:775) --, out_votes[j] its count, out_first_dist[j] (may be NULL) the distance of that nearest
+ * member, bits kept.  An empty list (r1 = 0, or every distance a NaN): KPOP_NO_CLASS, 0, 0, NaN.  The result is a function
+ * of the distances alone: the same bits on every run.  Neither the r2 x r1 matrix nor a neighbour list longer than k a
+ * row is formed; 12-20 bytes a query row cross the bus.  k in 1..128 (0: KPOP_ERR_INVALID, more: KPOP_ERR_UNSUPPORTED);
+ * n_classes in 1..65,535 (more: KPOP_ERR_UNSUPPORTED).  The set's limits, slot and thread ownership hold as for every
+ * call on a set.  The distances are the exact chain's on the vector pipe, one pass over the pairs (a second for the rows
+ * whose tie group at the k-th distance is longer than the k slots hold).  MEASURED (k = 5, profiles/knn_vote.md): SLOWER
+ * than kpop_dev_refset_distance_summary, which locates its neighbours on the matrix cores, at 256 x 1,000,000 x 64 (4.5
+ * against 2.0 ms) and at 256 x 650,000 x 1,635 (44 against 11 ms); faster at 4,096 x 100,000 x 64 (5.8 against 6.7 ms) and
+ * on a set of 600,000 identical rows (11.7 against 33.6 ms).                                                            */
+#define KPOP_NO_CLASS 0xFFFFFFFFu
+/* (lib/Matrix.ml:641-650 for the list; lib/Space.ml:182-205 for the distances.)  Host arrays; class_of[i] >= n_classes is
+   KPOP_ERR_INVALID.  The query rows go through in chunks that keep the workspace bounded.  Synchronises.               */
+int kpop_knn_vote(kpop_refset *rs, const uint32_t *class_of, uint32_t n_classes, const double *m2, uint32_t r2,
+                  uint32_t k, uint32_t *out_class, uint32_t *out_votes, uint32_t *out_n, double *out_first_dist);
+/* bytes of d_work for kpop_dev_knn_vote (the lists of lib/Matrix.ml:641-650, see the block above): the query side, 12 k
+   bytes of lists a query row and segment of the set's columns (at most 128 segments, fewer the more query rows: about
+   512 strips of rows x segments in all) and 8 n_classes bytes of tie tables a query row; does not grow with the set   */
+uint64_t kpop_dev_knn_vote_workspace_bytes(const kpop_refset *rs, uint32_t r2, uint32_t k, uint32_t n_classes);
+/* (lib/Matrix.ml:641-650; lib/Space.ml:182-205.)  Enqueues only: reads nothing back, allocates nothing.  d_class_of[r1] is
+   TRUSTED; every table access is guarded: a row whose class is >= n_classes counts in d_out_n and votes for nobody.    */
+int kpop_dev_knn_vote(kpop_refset *rs, const uint32_t *d_class_of, uint32_t n_classes, const double *d_m2, uint32_t r2,
+                      uint32_t k, void *d_work, uint32_t *d_out_class, uint32_t *d_out_votes, uint32_t *d_out_n,
+                      double *d_out_first_dist, void *stream);
+/* unprepared convenience (lib/Matrix.ml:191-266 for the distances, :641-650 for the list): a temporary set over m1, then
+   kpop_knn_vote                                                                                                        */
+int kpop_distance_knn_vote(const double *m1, uint32_t r1, const uint32_t *class_of, uint32_t n_classes, const double *m2,
+                           uint32_t r2, uint32_t n_dims, const double *metric, int kind, double p, int normalize,
+                           uint32_t k, uint32_t *out_class, uint32_t *out_votes, uint32_t *out_n,
+                           double *out_first_dist);
+
 /* ------------------------------------------------- k-mer database (KPopCountDB)
  * the operations of lib/KMerDB.ml that touch every count.  A database is the reference's
  * `storage: I32BAVector.t array` (lib/KMerDB.ml:54-63): n_cols spectra ("columns"), each a vector of n_rows int32

@@ -178,6 +178,12 @@ SIGNATURES = {
     "kpop_distance_spanning_forest": (C.c_int, [f64p, C.c_uint32, C.c_uint32, f64p, C.c_int, C.c_double, C.c_int, C.c_double, u32p, u32p, u32p, f64p,
                                                 u32p]),
     "kpop_forest_cut": (C.c_int, [C.c_uint32, C.c_uint32, u32p, u32p, f64p, C.c_double, u32p, u32p]),
+    # the k-NN vote (knn.hip)
+    "kpop_knn_vote": (C.c_int, [vp, u32p, C.c_uint32, f64p, C.c_uint32, C.c_uint32, u32p, u32p, u32p, f64p]),
+    "kpop_dev_knn_vote_workspace_bytes": (C.c_uint64, [vp, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "kpop_dev_knn_vote": (C.c_int, [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp]),
+    "kpop_distance_knn_vote": (C.c_int, [f64p, C.c_uint32, u32p, C.c_uint32, f64p, C.c_uint32, C.c_uint32, f64p, C.c_int, C.c_double, C.c_int, C.c_uint32,
+                                         u32p, u32p, u32p, f64p]),
 }
 
 

@@ -860,6 +860,25 @@ class RefSet:
         n = int(n.value)
         return ei[:n], ej[:n], ed[:n], labels[:r1]
 
+    def knn_vote(self, m2, class_of, k=5, n_classes=None):
+        """The k-NN classifier of the reference's README on the device -> (cls u32, votes u32, n u32, first f64), one entry a row of m2.
+        class_of: a class in [0, n_classes) for every row of the set (n_classes=None: the largest class + 1).  A row's list is its k
+        nearest rows of the set by (distance, index) plus every further row at the k-th distance (lib/Matrix.ml:641-650); n its length,
+        cls the class with the most members in it -- among equals the one whose nearest member comes first --, votes its count, first that
+        member's distance.  An empty list gives NO_CLASS, 0, 0, NaN (kpop_knn_vote, include/kpop_hip.h)."""
+        m2 = _c(m2, np.float64)
+        i = self.info()
+        if m2.ndim != 2 or m2.shape[1] != i["n_dims"]:
+            raise ValueError("Incompatible_geometries")
+        class_of, n_classes = _classes(class_of, i["r1"], n_classes)
+        r2 = m2.shape[0]
+        cls, votes, n = (np.zeros(r2, dtype=np.uint32) for _ in range(3))
+        first = np.zeros(r2, dtype=np.float64)
+        check(_lib.load().kpop_knn_vote(self._h, _p(_nz(class_of, np.uint32), C.c_uint32), n_classes, _p(_nz(m2, np.float64), C.c_double), r2, int(k),
+                                        _p(_nz(cls, np.uint32), C.c_uint32), _p(_nz(votes, np.uint32), C.c_uint32), _p(_nz(n, np.uint32), C.c_uint32),
+                                        _p(_nz(first, np.float64), C.c_double)))
+        return cls, votes, n, first
+
     def free(self):
         if self._h is not None and self._h.value:
             check(_lib.load().kpop_refset_free(self._h))
@@ -999,6 +1018,49 @@ def dev_refset_distance_rowwise(rs, d_m2, r2, d_work, d_out, stream=0):
 def dev_refset_distance_summary(rs, d_m2, r2, d_work, d_stats, d_n, d_idx, d_dist, d_z, keep_at_most=2, max_neighbours=8, stream=0):
     check(_lib.load().kpop_dev_refset_distance_summary(rs.handle, d_m2, int(r2), int(keep_at_most or 0), int(max_neighbours), d_work, d_stats, d_n,
                                                        d_idx, d_dist, d_z, stream))
+
+
+NO_CLASS = 0xFFFFFFFF  # KPOP_NO_CLASS: the class of a query row with an empty list
+
+
+def _classes(class_of, r1, n_classes):
+    """the labels of a set's rows as the C ABI takes them"""
+    class_of = np.asarray(class_of)
+    if class_of.ndim != 1 or len(class_of) != r1:
+        raise ValueError("class_of: one class for each of the set's %d rows" % r1)
+    if len(class_of) and (class_of.min() < 0 or class_of.max() > 0xFFFFFFFF):
+        raise ValueError("class_of: classes are uint32")
+    class_of = _c(class_of, np.uint32)
+    if n_classes is None:
+        n_classes = int(class_of.max()) + 1 if len(class_of) else 1
+    return class_of, int(n_classes)
+
+
+def dev_knn_vote_workspace_bytes(rs, r2, k, n_classes):
+    """the size of d_work for dev_knn_vote: by r2, k and n_classes; it does not grow with the set"""
+    return int(_lib.load().kpop_dev_knn_vote_workspace_bytes(rs.handle, int(r2), int(k), int(n_classes)))
+
+
+def dev_knn_vote(rs, d_class_of, n_classes, d_m2, r2, k, d_work, d_cls, d_votes, d_n, d_first=None, stream=0):
+    """enqueue only: d_cls / d_votes / d_n (u32 [r2]) and d_first (f64 [r2], or None) as RefSet.knn_vote returns them; d_class_of
+    (u32, one a row of the set) is trusted"""
+    check(_lib.load().kpop_dev_knn_vote(rs.handle, d_class_of, int(n_classes), d_m2, int(r2), int(k), d_work, d_cls, d_votes, d_n, d_first, stream))
+
+
+def distance_knn_vote(m1, class_of, m2, metric, k=5, kind=EUCLIDEAN, p=2.0, normalize=True, n_classes=None):
+    """RefSet(m1, ...).knn_vote(m2, class_of, k) without keeping the set: one call of kpop_distance_knn_vote"""
+    m1, m2, metric = _c(m1, np.float64), _c(m2, np.float64), _c(metric, np.float64)
+    if m1.ndim != 2 or m2.ndim != 2 or m1.shape[1] != len(metric) or m2.shape[1] != len(metric):
+        raise ValueError("Incompatible_geometries")  # lib/Matrix.ml:193-194
+    class_of, n_classes = _classes(class_of, m1.shape[0], n_classes)
+    r2 = m2.shape[0]
+    cls, votes, n = (np.zeros(r2, dtype=np.uint32) for _ in range(3))
+    first = np.zeros(r2, dtype=np.float64)
+    check(_lib.load().kpop_distance_knn_vote(_p(_nz(m1, np.float64), C.c_double), m1.shape[0], _p(_nz(class_of, np.uint32), C.c_uint32), n_classes,
+                                             _p(_nz(m2, np.float64), C.c_double), r2, len(metric), _p(_nz(metric, np.float64), C.c_double), int(kind),
+                                             float(p), 1 if normalize else 0, int(k), _p(_nz(cls, np.uint32), C.c_uint32),
+                                             _p(_nz(votes, np.uint32), C.c_uint32), _p(_nz(n, np.uint32), C.c_uint32), _p(_nz(first, np.float64), C.c_double)))
+    return cls, votes, n, first
 
 
 def dev_neighbours_within_workspace_bytes(rs, r2, capacity):

@@ -1,0 +1,711 @@
+// knn.hip -- the k-NN vote: classify query rows against a labelled resident set.
+//
+//   The list of query row j: the set rows whose distance to j is a number, ordered by (d with -0 taken as +0, index) ascending; its
+//   first k, plus every further row whose distance equals the k-th one -- eff_len of summarize_distance_matrix_row
+//   (lib/Matrix.ml:641-650): whole tie groups.  The vote (the reference's README.md:773-775): the class with the most members in the
+//   list; among classes with equally many, the one whose nearest member comes first in the list's order.  d(j, i) is the reference
+//   chain's distance (lib/Space.ml:182-205 with the adaptors of lib/Matrix.ml:243-250): the bits of distance_rowwise_kernel
+//   (distance.hip), whatever kpop_tune says -- no setting is read here.  Neither the r2 x r1 matrix nor a list longer than k a row
+//   is formed; every step is a function of the distances alone: the same bits on every run.
+//
+// Four launches, always the same four (the device form reads nothing back):
+//   knn_nearest_kernel   the arithmetic of distance_rowwise_kernel, operation for operation (the copy of within.hip's and forest.hip's
+//                        staging-and-accumulate loop, kept here so that those kernels stay the kernels they were).  A workgroup owns a
+//                        strip of TJ query rows and walks the column tiles of its segment of the set, columns ascending.  Every row
+//                        has in LDS the sorted list of its k smallest (key, index) so far and the list's bound, its k-th key.  A
+//                        thread compares its 4 x TY finished distances with the bound; after the first tiles almost nothing passes.
+//                        What passes is inserted by the row's wavefront, one candidate at a time, the lanes side by side over the
+//                        list's slots (a row belongs to ONE wavefront: no other touches its list).  The k smallest of a set under a
+//                        strict order do not depend on the order of arrival.  Beside each list a count of DROPPED TIES: the entries
+//                        refused or evicted whose key equals the list's current k-th key, reset whenever that key changes.  The rows
+//                        of a strip by k, so that the lists fit the LDS (KnnShape, knn_strip_rows); the columns in as many segments
+//                        as make about kKBlocks workgroups with the strips, so that a few query rows still fill the chip.
+//   knn_merge_kernel     per row: the segments' lists merged, tau = the k-th key (the largest, if there are fewer than k).  A
+//                        segment's k-th key never lies below tau, so an entry equal to tau can only have been dropped while that
+//                        segment's bound was tau -- and the bound stays there afterwards.  Hence: the tie group of tau is held whole
+//                        by the segments' lists unless a segment whose final k-th key is tau reports dropped ties: the row is FLAGGED
+//                        (also when the lists hold more entries at tau than knn_vote_kernel has room for: kKMaxTies).
+//   knn_ties_kernel      the same tile loop; a workgroup returns at once unless one of its rows is flagged (the common case: no tie
+//                        group longer than k slots hold).  For a flagged row every column with key == tau adds 1 to
+//                        tie_count[row][class] and takes atomicMin of its index into tie_first[row][class]: sums and minima do not
+//                        depend on the order, and all entries of a tie group share one distance, so their order is their index.
+//   knn_vote_kernel      per row: the classes of the entries below tau are tallied; the tie group comes from the segments' lists
+//                        (unflagged) or from the tables (flagged); the winner by (count descending, first (key, index) ascending).
+// The chain makes no -0 (a sum of terms added to +0, its square root, half or power): a key gives back the distance's bits.
+#include <algorithm>
+
+#include "common.h"
+#include "distance_routes.h"
+#include "refset.h"
+#include "space_ops.h"
+
+namespace kpop {
+
+constexpr int kKDC = 16, kKMaxK = 128;
+// a workgroup's shape: W columns (rows of the set) x TJ query rows, a thread 4 columns x TY rows
+template <int TY, int W>
+struct KnnShape {
+  static constexpr uint32_t NCG = W / 4, NRG = 256 / NCG, TJ = TY * NRG;
+  static constexpr uint32_t SLOTS = 2048;  // list slots of the workgroup: TJ k <= SLOTS, the whole within 64 KiB of LDS
+};
+constexpr int kKMaxSeg = 128, kKBlocks = 512;                // segments a strip at most; workgroups a launch aims at (two a CU)
+constexpr int kKMaxTies = 1024;                              // listed ties of a row that knn_vote_kernel takes from the lists; more: the tables
+constexpr int kKVoteList = kKMaxK + kKMaxTies;               // knn_vote_kernel: < k entries below tau, then the listed ties
+constexpr uint64_t kKNone = ~0ull;                           // (no key: knn_key maps only a NaN's bits there, and a NaN is never a key)
+constexpr uint32_t kKMaxClasses = 65535;
+
+// a distance that is a number -> a key that orders as the distance does; -0 is taken as +0 (forest.hip's dist_key)
+__device__ __forceinline__ uint64_t knn_key(double d) {
+  if (d == 0.0) d = 0.0;
+  const uint64_t b = (uint64_t)__double_as_longlong(d);
+  return (b >> 63) ? ~b : (b | (1ull << 63));
+}
+__device__ __forceinline__ double knn_key_dist(uint64_t k) { return __longlong_as_double((long long)((k >> 63) ? (k & ~(1ull << 63)) : ~k)); }
+__device__ __forceinline__ bool knn_less(uint64_t ka, uint32_t ia, uint64_t kb, uint32_t ib) { return ka < kb || (ka == kb && ia < ib); }
+
+// One candidate into a row's sorted list, by the whole wavefront that owns the row (every argument is the same in all 64 lanes).
+// lk, li: the row's k slots; *np its length; *bp, *bip its bound (kKNone until the list is full, then its k-th key and index); *dp its
+// dropped ties.
+// A lane holds slots lane and lane + 64 (k <= 128).  The slots are read into registers before any is written, and the LDS serves a
+// wavefront's accesses in the order it issued them: volatile keeps the compiler from moving them.
+__device__ __forceinline__ void knn_insert(volatile uint64_t *lk, volatile uint32_t *li, volatile uint32_t *np, volatile uint64_t *bp, volatile uint32_t *bip,
+                                           volatile uint32_t *dp, uint32_t k, uint64_t ck, uint32_t ci, uint32_t lane) {
+  const uint32_t n = *np;
+  uint64_t bk = 0;
+  if (n == k) {
+    bk = lk[k - 1];
+    const uint32_t bi = li[k - 1];
+    if (ck > bk) return;
+    if (ck == bk && ci > bi) {  // refused, a tie of the k-th key
+      if (lane == 0) *dp = *dp + 1;
+      return;
+    }
+  }
+  const uint32_t q0 = lane, q1 = lane + 64;
+  const uint64_t e0k = q0 < n ? lk[q0] : 0, e1k = q1 < n ? lk[q1] : 0;
+  const uint32_t e0i = q0 < n ? li[q0] : 0, e1i = q1 < n ? li[q1] : 0;
+  const uint32_t pos = (uint32_t)__popcll(__ballot(q0 < n && knn_less(e0k, e0i, ck, ci))) + (uint32_t)__popcll(__ballot(q1 < n && knn_less(e1k, e1i, ck, ci)));
+  // (pos <= n, and pos < k: a full list was entered only below its last entry)
+  if (q0 < n && q0 >= pos && q0 + 1 < k) {
+    lk[q0 + 1] = e0k;
+    li[q0 + 1] = e0i;
+  }
+  if (q1 < n && q1 >= pos && q1 + 1 < k) {
+    lk[q1 + 1] = e1k;
+    li[q1 + 1] = e1i;
+  }
+  if (lane == 0) {
+    lk[pos] = ck;
+    li[pos] = ci;
+  }
+  if (n < k) {
+    if (lane == 0) *np = n + 1;
+    if (n + 1 == k) {
+      const uint64_t nk = lk[k - 1];
+      const uint32_t ni = li[k - 1];
+      if (lane == 0) {
+        *bp = nk;
+        *bip = ni;
+      }
+    }
+  } else {  // the old last entry, of key bk, was evicted
+    const uint64_t nk = lk[k - 1];
+    const uint32_t ni = li[k - 1];
+    if (lane == 0) {
+      *dp = (nk == bk) ? *dp + 1 : 0u;
+      *bp = nk;
+      *bip = ni;
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+}
+
+// The tile loop.  a: the set's rows, b: the query rows, both as the chain reads them (divided by their rows' norms when the set
+// normalises).  The workgroup's rows j0 .. j1 (at most TJ), its column tiles t_begin .. t_end of W rows of the set each.
+// A thread 4 columns x TY rows, the dimensions ascending in one thread, 16 at a time through LDS: within_tile_kernel's; the next step's
+// operands -- the tile's next 16 dimensions, or the first of the next tile -- are loaded under the arithmetic: forest_nearest_kernel's.
+// epi(i0, i1, acc): what to do with a tile's finished sums.
+template <int KIND, int TY, int W, class Epi>
+__device__ __forceinline__ void knn_tiles(const double *__restrict__ a, uint32_t r1, const double *__restrict__ b, uint32_t j0, uint32_t j1, uint32_t n_dims,
+                                          const double *__restrict__ metric, double p, uint32_t t_begin, uint32_t t_end, double (*As)[W + 2],
+                                          double (*Bs)[KnnShape<TY, W>::TJ + 2], double *s_metric, Epi &&epi) {
+  using S = KnnShape<TY, W>;
+  constexpr uint32_t TJ = S::TJ;
+  const uint32_t cg = threadIdx.x % S::NCG, rg = threadIdx.x / S::NCG;
+  const uint32_t ti = cg * 4, tj = rg * TY;
+  constexpr int NA = W * kKDC / 256, NB = TJ * kKDC / 256;
+  double ra[NA], rb[NB];
+  const uint32_t sc = threadIdx.x % kKDC, rbase = threadIdx.x / kKDC;
+  auto prefetch = [&](uint32_t i0, uint32_t c0) {
+    const uint32_t i1 = min(r1, i0 + W);
+    const bool cok = c0 + sc < n_dims;
+#pragma unroll
+    for (int q = 0; q < NA; ++q) {
+      const uint32_t row = rbase + q * 16;
+      ra[q] = (cok && i0 + row < i1) ? a[(uint64_t)(i0 + row) * n_dims + c0 + sc] : 0.0;
+    }
+#pragma unroll
+    for (int q = 0; q < NB; ++q) {
+      const uint32_t row = rbase + q * 16;
+      rb[q] = (cok && j0 + row < j1) ? b[(uint64_t)(j0 + row) * n_dims + c0 + sc] : 0.0;
+    }
+  };
+  if (t_begin < t_end) prefetch(t_begin * W, 0);
+  for (uint32_t t = t_begin; t < t_end; ++t) {
+    const uint32_t i0 = t * W, i1 = min(r1, i0 + W);
+    double acc[TY][4];
+#pragma unroll
+    for (int yy = 0; yy < TY; ++yy)
+#pragma unroll
+      for (int x = 0; x < 4; ++x) acc[yy][x] = 0.0;
+    for (uint32_t c0 = 0; c0 < n_dims; c0 += kKDC) {
+      __syncthreads();
+#pragma unroll
+      for (int q = 0; q < NA; ++q) As[sc][rbase + q * 16] = ra[q];
+#pragma unroll
+      for (int q = 0; q < NB; ++q) Bs[sc][rbase + q * 16] = rb[q];
+      if (threadIdx.x < kKDC) s_metric[threadIdx.x] = (c0 + threadIdx.x < n_dims) ? metric[c0 + threadIdx.x] : 0.0;
+      __syncthreads();
+      if (c0 + kKDC < n_dims) prefetch(i0, c0 + kKDC);
+      else if (t + 1 < t_end) prefetch((t + 1) * W, 0);
+      const uint32_t lim = min((uint32_t)kKDC, n_dims - c0);
+      for (uint32_t cc = 0; cc < lim; ++cc) {
+        double av[4], bv[TY];
+#pragma unroll
+        for (int x = 0; x < 4; ++x) av[x] = As[cc][ti + x];
+#pragma unroll
+        for (int yy = 0; yy < TY; ++yy) bv[yy] = Bs[cc][tj + yy];
+        const double mc = s_metric[cc];
+#pragma unroll
+        for (int yy = 0; yy < TY; ++yy)
+#pragma unroll
+          for (int x = 0; x < 4; ++x) {
+            // lib/Space.ml:192-200: diff = a -. b ; acc +. (diff *. diff *. m)
+            double diff = __dsub_rn(av[x], bv[yy]);
+            acc[yy][x] = __dadd_rn(acc[yy][x], component<KIND>(diff, mc, p));
+          }
+      }
+    }
+    epi(i0, i1, acc);
+  }
+}
+
+// the column tiles of a segment
+__device__ __forceinline__ void knn_segment(uint32_t n_ct, uint32_t tiles_per_seg, uint32_t *t_begin, uint32_t *t_end) {
+  *t_begin = min(n_ct, blockIdx.y * tiles_per_seg);
+  *t_end = min(n_ct, *t_begin + tiles_per_seg);
+}
+
+// Strip blockIdx.x: query rows j0 .. j0 + TJ; segment blockIdx.y.  seg_key, seg_idx: [segment][r2][k], the list's first seg_n
+// entries ascending; seg_drop: the dropped ties of the list's last key.  TJ k <= SLOTS (the launch sees to it).
+template <int KIND, int TY, int W>
+__global__ __launch_bounds__(256, 1) void knn_nearest_kernel(const double *__restrict__ a, uint32_t r1, const double *__restrict__ b, uint32_t r2, uint32_t n_dims,
+                                                             const double *__restrict__ metric, double p, uint32_t k, uint32_t n_ct, uint32_t tiles_per_seg,
+                                                             uint64_t *__restrict__ seg_key, uint32_t *__restrict__ seg_idx, uint32_t *__restrict__ seg_n,
+                                                             uint32_t *__restrict__ seg_drop) {
+  using S = KnnShape<TY, W>;
+  constexpr uint32_t TJ = S::TJ;
+  __shared__ __attribute__((aligned(16))) double As[kKDC][W + 2];
+  __shared__ __attribute__((aligned(16))) double Bs[kKDC][TJ + 2];
+  __shared__ double s_metric[kKDC];
+  __shared__ uint64_t s_key[S::SLOTS];
+  __shared__ uint32_t s_idx[S::SLOTS];
+  __shared__ uint64_t s_bound[TJ];
+  __shared__ uint32_t s_n[TJ], s_drop[TJ], s_bidx[TJ];
+  const uint32_t j0 = blockIdx.x * TJ, j1 = min(r2, j0 + TJ);  // (the grid has div_up(r2, TJ) strips: j0 < r2)
+  uint32_t t_begin, t_end;
+  knn_segment(n_ct, tiles_per_seg, &t_begin, &t_end);
+  if (threadIdx.x < TJ) {
+    s_bound[threadIdx.x] = kKNone;
+    s_bidx[threadIdx.x] = 0;
+    s_n[threadIdx.x] = 0;
+    s_drop[threadIdx.x] = 0;
+  }
+  __syncthreads();
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t ti = (threadIdx.x % S::NCG) * 4, tj = (threadIdx.x / S::NCG) * TY;  // (the rows of a wavefront: TJ / 4 in a row, nobody else's)
+  knn_tiles<KIND, TY, W>(a, r1, b, j0, j1, n_dims, metric, p, t_begin, t_end, As, Bs, s_metric, [&](uint32_t i0, uint32_t i1, double(&acc)[TY][4]) {
+    // the rows' bounds as the step before left them (a row is this wavefront's alone): read again after every step that inserted
+    uint64_t bound[TY];
+    uint32_t bidx[TY];
+    auto bounds = [&]() {
+#pragma unroll
+      for (int yy = 0; yy < TY; ++yy) {
+        bound[yy] = *(volatile uint64_t *)&s_bound[tj + yy];
+        bidx[yy] = *(volatile uint32_t *)&s_bidx[tj + yy];
+      }
+    };
+    bounds();
+#pragma unroll
+    for (int yy = 0; yy < TY; ++yy) {
+      const uint32_t row = tj + yy;
+#pragma unroll
+      for (int x = 0; x < 4; ++x) {
+        const double d = scale_distance<KIND>(acc[yy][x], p);
+        const uint32_t i = i0 + ti + x;
+        const uint64_t key = knn_key(d);
+        const bool number = j0 + row < j1 && i < i1 && d == d;  // a NaN is never a neighbour
+        // a tie of the k-th key behind the k-th entry is dropped and counted where it stands: a sum, whatever the order.  These
+        // come first, the entries that go into the list after them: one of the orders of arrival, all of which give the same
+        if (number && key == bound[yy] && i > bidx[yy]) atomicAdd(&s_drop[row], 1u);
+        __builtin_amdgcn_wave_barrier();
+        const bool c = number && (key < bound[yy] || (key == bound[yy] && i < bidx[yy]));
+        uint64_t m = __ballot(c);
+        const bool inserted = m != 0;
+        while (m) {  // (the same in every lane)
+          const int src = __ffsll((unsigned long long)m) - 1;
+          m &= m - 1;
+          const uint64_t ck = (uint64_t)__shfl((unsigned long long)key, src, 64);
+          const uint32_t ci = (uint32_t)__shfl((int)i, src, 64);
+          const uint32_t cr = (uint32_t)__shfl((int)row, src, 64);
+          knn_insert(s_key + cr * k, s_idx + cr * k, s_n + cr, s_bound + cr, s_bidx + cr, s_drop + cr, k, ck, ci, lane);
+        }
+        if (inserted) bounds();
+      }
+    }
+  });
+  __syncthreads();
+  const uint32_t seg = blockIdx.y;
+  for (uint32_t e = threadIdx.x; e < TJ * k; e += 256) {
+    const uint32_t row = e / k, q = e % k;
+    if (j0 + row < j1) {
+      const uint64_t o = ((uint64_t)seg * r2 + j0 + row) * k + q;
+      const bool in = q < s_n[row];
+      seg_key[o] = in ? s_key[e] : kKNone;
+      seg_idx[o] = in ? s_idx[e] : 0u;
+    }
+  }
+  if (threadIdx.x < TJ && j0 + threadIdx.x < j1) {
+    seg_n[(uint64_t)seg * r2 + j0 + threadIdx.x] = s_n[threadIdx.x];
+    seg_drop[(uint64_t)seg * r2 + j0 + threadIdx.x] = s_drop[threadIdx.x];
+  }
+}
+
+// a block of 64 a row: every entry's place in the merged list is its place in its own segment's list plus its lower bounds in the
+// others (the pairs of a row are all distinct: they differ in the index) -- within_merge_kernel's.  m_key, m_idx: [r2][k], the first
+// m_n entries; m_tau: the last of them; m_flag: the tie group of tau is not whole in the segments' lists
+__global__ __launch_bounds__(64) void knn_merge_kernel(const uint64_t *__restrict__ seg_key, const uint32_t *__restrict__ seg_idx, const uint32_t *__restrict__ seg_n,
+                                                       const uint32_t *__restrict__ seg_drop, uint32_t n_seg, uint32_t r2, uint32_t k, uint64_t *__restrict__ m_key,
+                                                       uint32_t *__restrict__ m_idx, uint32_t *__restrict__ m_n, uint64_t *__restrict__ m_tau, uint32_t *__restrict__ m_flag) {
+  __shared__ uint64_t s_k[kKMaxK];
+  __shared__ uint32_t s_i[kKMaxK];
+  __shared__ uint32_t s_ties, s_total;
+  __shared__ unsigned long long s_least;
+  for (uint32_t row = blockIdx.x; row < r2; row += gridDim.x) {
+    __syncthreads();  // (the row before has read s_k and the three words)
+    if (threadIdx.x == 0) {
+      s_ties = 0;
+      s_total = 0;
+      s_least = kKNone;
+    }
+    __syncthreads();
+    // the lists' lengths in all, and the least k-th key of a full list: k entries lie at or below it, so nothing above it is among the
+    // k smallest -- most of what the segments hold, and it is not looked at again
+    for (uint32_t s = threadIdx.x; s < n_seg; s += 64) {
+      const uint64_t o = (uint64_t)s * r2 + row;
+      const uint32_t ns = seg_n[o];
+      if (ns) atomicAdd(&s_total, ns);
+      if (ns == k) atomicMin(&s_least, (unsigned long long)seg_key[o * k + k - 1]);
+    }
+    __syncthreads();
+    const uint32_t nm = min(s_total, k);
+    const uint64_t least = s_least;
+    for (uint32_t e = threadIdx.x; e < n_seg * k; e += 64) {
+      const uint32_t s = e / k, q = e % k;
+      if (q >= seg_n[(uint64_t)s * r2 + row]) continue;
+      const uint64_t base = ((uint64_t)s * r2 + row) * k;
+      const uint64_t key = seg_key[base + q];
+      if (key > least) continue;
+      const uint32_t idx = seg_idx[base + q];
+      uint32_t rank = q;
+      for (uint32_t s2 = 0; s2 < n_seg && rank < k; ++s2) {
+        if (s2 == s) continue;
+        const uint64_t b2 = ((uint64_t)s2 * r2 + row) * k;
+        uint32_t lo = 0, hi = seg_n[(uint64_t)s2 * r2 + row];
+        while (lo < hi) {  // the first entry of the list that is not below (key, idx)
+          const uint32_t mid = (lo + hi) >> 1;
+          if (knn_less(seg_key[b2 + mid], seg_idx[b2 + mid], key, idx)) lo = mid + 1;
+          else hi = mid;
+        }
+        rank += lo;
+      }
+      if (rank < k) {
+        s_k[rank] = key;
+        s_i[rank] = idx;
+      }
+    }
+    __syncthreads();
+    for (uint32_t q = threadIdx.x; q < nm; q += 64) {
+      m_key[(uint64_t)row * k + q] = s_k[q];
+      m_idx[(uint64_t)row * k + q] = s_i[q];
+    }
+    const uint64_t tau = nm ? s_k[nm - 1] : kKNone;
+    // the ties of tau that the lists hold: more than knn_vote_kernel has room for, and the tables take over
+    uint32_t ties = 0;
+    for (uint32_t e = threadIdx.x; e < n_seg * k; e += 64) {
+      const uint64_t o = (uint64_t)(e / k) * r2 + row;
+      ties += (e % k < seg_n[o] && seg_key[o * k + e % k] == tau) ? 1u : 0u;
+    }
+    if (ties) atomicAdd(&s_ties, ties);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      uint32_t flag = (nm && s_ties > (uint32_t)kKMaxTies) ? 1u : 0u;
+      if (nm == k)
+        for (uint32_t s = 0; s < n_seg; ++s) {
+          const uint64_t o = (uint64_t)s * r2 + row;
+          if (seg_n[o] == k && seg_key[o * k + k - 1] == tau && seg_drop[o] > 0) flag = 1;
+        }
+      m_n[row] = nm;
+      m_tau[row] = tau;
+      m_flag[row] = flag;
+    }
+  }
+}
+
+// the grid of knn_nearest_kernel.  tie_total: [r2], every column of a flagged row at tau; tie_count, tie_first: [r2][n_classes], those
+// of a class and the least index among them (0xFFFFFFFF: none).  class_of is trusted, every table access guarded
+template <int KIND, int TY, int W>
+__global__ __launch_bounds__(256, 1) void knn_ties_kernel(const double *__restrict__ a, uint32_t r1, const double *__restrict__ b, uint32_t r2, uint32_t n_dims,
+                                                          const double *__restrict__ metric, double p, uint32_t n_ct, uint32_t tiles_per_seg,
+                                                          const uint32_t *__restrict__ class_of, uint32_t n_classes, const uint64_t *__restrict__ m_tau,
+                                                          const uint32_t *__restrict__ m_flag, uint32_t *tie_total, uint32_t *tie_count, uint32_t *tie_first) {
+  using S = KnnShape<TY, W>;
+  constexpr uint32_t TJ = S::TJ;
+  __shared__ __attribute__((aligned(16))) double As[kKDC][W + 2];
+  __shared__ __attribute__((aligned(16))) double Bs[kKDC][TJ + 2];
+  __shared__ double s_metric[kKDC];
+  const uint32_t j0 = blockIdx.x * TJ, j1 = min(r2, j0 + TJ);
+  if (!__syncthreads_or(threadIdx.x < TJ && j0 + threadIdx.x < j1 && m_flag[j0 + threadIdx.x] != 0)) return;  // (nearly every workgroup)
+  uint32_t t_begin, t_end;
+  knn_segment(n_ct, tiles_per_seg, &t_begin, &t_end);
+  const uint32_t ti = (threadIdx.x % S::NCG) * 4, tj = (threadIdx.x / S::NCG) * TY;
+  uint64_t tau[TY];
+  bool fl[TY];
+#pragma unroll
+  for (int yy = 0; yy < TY; ++yy) {
+    const uint32_t j = j0 + tj + yy;
+    fl[yy] = j < j1 && m_flag[j] != 0;
+    tau[yy] = fl[yy] ? m_tau[j] : kKNone;
+  }
+  knn_tiles<KIND, TY, W>(a, r1, b, j0, j1, n_dims, metric, p, t_begin, t_end, As, Bs, s_metric, [&](uint32_t i0, uint32_t i1, double(&acc)[TY][4]) {
+#pragma unroll
+    for (int yy = 0; yy < TY; ++yy) {
+      if (!fl[yy]) continue;
+      const uint32_t j = j0 + tj + yy;
+#pragma unroll
+      for (int x = 0; x < 4; ++x) {
+        const double d = scale_distance<KIND>(acc[yy][x], p);
+        const uint32_t i = i0 + ti + x;
+        if (i < i1 && d == d && knn_key(d) == tau[yy]) {
+          atomicAdd(tie_total + j, 1u);
+          const uint32_t c = class_of[i];
+          if (c < n_classes) {
+            atomicAdd(tie_count + (uint64_t)j * n_classes + c, 1u);
+            atomicMin(tie_first + (uint64_t)j * n_classes + c, i);
+          }
+        }
+      }
+    }
+  });
+}
+
+struct KnnBest {
+  uint32_t cnt, idx, cls;
+  uint64_t key;
+};
+__device__ __forceinline__ bool knn_better(const KnnBest &x, const KnnBest &y) {  // more members; among equally many, the nearer first member
+  return x.cnt > y.cnt || (x.cnt == y.cnt && x.cnt > 0 && knn_less(x.key, x.idx, y.key, y.idx));
+}
+
+// a block of 64 (one wavefront) a row
+__global__ __launch_bounds__(64) void knn_vote_kernel(const uint64_t *__restrict__ seg_key, const uint32_t *__restrict__ seg_idx, const uint32_t *__restrict__ seg_n,
+                                                      uint32_t n_seg, uint32_t r2, uint32_t k, const uint64_t *__restrict__ m_key, const uint32_t *__restrict__ m_idx,
+                                                      const uint32_t *__restrict__ m_n, const uint64_t *__restrict__ m_tau, const uint32_t *__restrict__ m_flag,
+                                                      const uint32_t *__restrict__ class_of, uint32_t n_classes, const uint32_t *__restrict__ tie_total,
+                                                      const uint32_t *__restrict__ tie_count, const uint32_t *__restrict__ tie_first, uint32_t *__restrict__ out_class,
+                                                      uint32_t *__restrict__ out_votes, uint32_t *__restrict__ out_n, double *__restrict__ out_first_dist) {
+  __shared__ uint64_t s_k[kKVoteList];
+  __shared__ uint32_t s_i[kKVoteList], s_c[kKVoteList];
+  __shared__ uint32_t s_nb, s_nt;
+  for (uint32_t row = blockIdx.x; row < r2; row += gridDim.x) {
+    const uint32_t nm = m_n[row];
+    if (nm == 0) {  // no distance of the row is a number (or the set is empty)
+      if (threadIdx.x == 0) {
+        out_class[row] = KPOP_NO_CLASS;
+        out_votes[row] = 0;
+        out_n[row] = 0;
+        if (out_first_dist) out_first_dist[row] = __longlong_as_double(0x7FF8000000000000ll);
+      }
+      continue;
+    }
+    const uint64_t tau = m_tau[row];
+    const bool flagged = m_flag[row] != 0;
+    __syncthreads();  // (the row before is done with the lists)
+    if (threadIdx.x == 0) {
+      s_nb = 0;
+      s_nt = 0;
+    }
+    __syncthreads();
+    // the entries below tau: a prefix of the merged list, fewer than k
+    for (uint32_t q = threadIdx.x; q < nm; q += 64) {
+      const uint64_t key = m_key[(uint64_t)row * k + q];
+      if (key < tau) {
+        const uint32_t idx = m_idx[(uint64_t)row * k + q];
+        s_k[q] = key;
+        s_i[q] = idx;
+        s_c[q] = class_of[idx];
+        atomicAdd(&s_nb, 1u);
+      }
+    }
+    // the tie group, when the segments' lists hold it whole: behind slot kKMaxK, in any order (its order is the index)
+    if (!flagged)
+      for (uint32_t e = threadIdx.x; e < n_seg * k; e += 64) {
+        const uint32_t s = e / k, q = e % k;
+        const uint64_t o = (uint64_t)s * r2 + row;
+        if (q < seg_n[o] && seg_key[o * k + q] == tau) {
+          const uint32_t slot = kKMaxK + atomicAdd(&s_nt, 1u);  // (at most kKMaxTies of them: knn_merge_kernel flags the row otherwise)
+          const uint32_t idx = seg_idx[o * k + q];
+          s_k[slot] = tau;
+          s_i[slot] = idx;
+          s_c[slot] = class_of[idx];
+        }
+      }
+    __syncthreads();
+    const uint32_t nb = s_nb, nt = s_nt, L = nb + nt;
+    auto phys = [&](uint32_t e) { return e < nb ? e : kKMaxK + (e - nb); };
+    KnnBest best = {0u, 0u, KPOP_NO_CLASS, kKNone};
+    // an entry that is the first of its class stands for the class
+    for (uint32_t e = threadIdx.x; e < L; e += 64) {
+      const uint32_t pe = phys(e), c = s_c[pe];
+      if (c >= n_classes) continue;  // counts in out_n, votes for nobody
+      uint32_t cnt = 0;
+      bool first = true;
+      for (uint32_t f = 0; f < L; ++f) {
+        const uint32_t pf = phys(f);
+        if (s_c[pf] != c) continue;
+        ++cnt;
+        if (knn_less(s_k[pf], s_i[pf], s_k[pe], s_i[pe])) first = false;
+      }
+      if (!first) continue;
+      if (flagged) cnt += tie_count[(uint64_t)row * n_classes + c];
+      const KnnBest cand = {cnt, s_i[pe], c, s_k[pe]};
+      if (knn_better(cand, best)) best = cand;
+    }
+    uint32_t n_list = L;
+    if (flagged) {  // the classes that only the tie group holds
+      n_list = nb + tie_total[row];
+      for (uint32_t c = threadIdx.x; c < n_classes; c += 64) {
+        const uint32_t tc = tie_count[(uint64_t)row * n_classes + c];
+        if (tc == 0) continue;
+        bool below = false;
+        for (uint32_t f = 0; f < nb; ++f) below = below || s_c[f] == c;
+        if (below) continue;
+        const KnnBest cand = {tc, tie_first[(uint64_t)row * n_classes + c], c, tau};
+        if (knn_better(cand, best)) best = cand;
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      KnnBest other;
+      other.cnt = (uint32_t)__shfl_xor((int)best.cnt, o, 64);
+      other.idx = (uint32_t)__shfl_xor((int)best.idx, o, 64);
+      other.cls = (uint32_t)__shfl_xor((int)best.cls, o, 64);
+      other.key = (uint64_t)__shfl_xor((unsigned long long)best.key, o, 64);
+      if (knn_better(other, best)) best = other;
+    }
+    if (threadIdx.x == 0) {
+      out_class[row] = best.cnt ? best.cls : KPOP_NO_CLASS;
+      out_votes[row] = best.cnt;
+      out_n[row] = n_list;
+      if (out_first_dist) out_first_dist[row] = best.cnt ? knn_key_dist(best.key) : __longlong_as_double(0x7FF8000000000000ll);
+    }
+  }
+}
+
+// the workspace, carved: the query rows' norms and divided copy, the segments' lists, the merged lists, the tie tables.  It depends on
+// r2, k, n_classes, the set's n_dims and the constants above; not on r1
+struct KnnWork {
+  double *n2, *b;
+  uint64_t *seg_key, *m_key, *m_tau;
+  uint32_t *seg_idx, *seg_n, *seg_drop, *m_idx, *m_n, *m_flag, *tie_total, *tie_count, *tie_first;
+  uint64_t tables_off, tables_bytes, bytes;
+};
+
+// the rows of a strip by k, so that their lists fit the workgroup's slots: 64 columns x 64, 32 or 16 rows, a thread 4 x 4, 2 or 1.
+// (The choice moves no bit: a pair's chain is one thread's either way.  rowwise_block's 32 columns x 256 rows, a thread 4 x 8, was
+// tried for k <= 6 against long sets and measured slower here -- profiles/knn_vote.md -- and is not built.)
+static uint32_t knn_strip_rows(uint32_t k) { return k <= 2048 / 64 ? 64u : k <= 2048 / 32 ? 32u : 16u; }
+// the segments the columns are cut into at most: as many as make kKBlocks workgroups with the strips of r2 query rows (forest.hip's
+// reason: a few query rows still fill the chip).  By r2 and k alone, so that the workspace does not depend on the set
+static uint32_t knn_max_segments(uint32_t r2, uint32_t strip_rows) {
+  return std::max(1u, std::min<uint32_t>(kKMaxSeg, div_up(kKBlocks, std::max(1u, div_up(r2, strip_rows)))));
+}
+
+static KnnWork knn_carve(void *work, uint32_t r2, uint32_t k, uint32_t n_classes, uint32_t n_dims, bool normalize) {
+  char *base = reinterpret_cast<char *>(work);
+  uint64_t off = 0;
+  auto take = [&](uint64_t bytes) {
+    char *q = base + off;
+    off += (bytes + 255) & ~255ull;
+    return q;
+  };
+  const uint64_t n = r2, lists = n * k, segs = knn_max_segments(r2, knn_strip_rows(k));
+  KnnWork w;
+  w.n2 = reinterpret_cast<double *>(take(normalize ? n * 8 : 0));
+  w.b = reinterpret_cast<double *>(take(normalize ? n * n_dims * 8 : 0));
+  w.seg_key = reinterpret_cast<uint64_t *>(take(lists * 8 * segs));
+  w.seg_idx = reinterpret_cast<uint32_t *>(take(lists * 4 * segs));
+  w.seg_n = reinterpret_cast<uint32_t *>(take(n * 4 * segs));
+  w.seg_drop = reinterpret_cast<uint32_t *>(take(n * 4 * segs));
+  w.m_key = reinterpret_cast<uint64_t *>(take(lists * 8));
+  w.m_idx = reinterpret_cast<uint32_t *>(take(lists * 4));
+  w.m_tau = reinterpret_cast<uint64_t *>(take(n * 8));
+  w.m_n = reinterpret_cast<uint32_t *>(take(n * 4));
+  w.m_flag = reinterpret_cast<uint32_t *>(take(n * 4));
+  w.tables_off = off;
+  w.tie_total = reinterpret_cast<uint32_t *>(take(n * 4));
+  w.tie_count = reinterpret_cast<uint32_t *>(take(n * n_classes * 4));
+  w.tables_bytes = off - w.tables_off;  // (zeroes)
+  w.tie_first = reinterpret_cast<uint32_t *>(take(n * n_classes * 4));  // (ones)
+  w.bytes = off + 256;
+  return w;
+}
+
+template <int KIND, int TY, int W>
+static int knn_passes(const double *a, uint32_t r1, const double *b, uint32_t r2, uint32_t n_dims, const double *metric, double p, uint32_t k,
+                      const uint32_t *class_of, uint32_t n_classes, const KnnWork &w, uint32_t *n_seg_out, hipStream_t st) {
+  constexpr uint32_t TJ = KnnShape<TY, W>::TJ;
+  const uint32_t n_ct = div_up(r1, W), strips = div_up(r2, TJ);
+  const uint32_t n_seg_max = std::max(1u, std::min(knn_max_segments(r2, TJ), n_ct));
+  const uint32_t tiles_per_seg = div_up(n_ct, n_seg_max), n_seg = div_up(n_ct, tiles_per_seg);  // (no segment is empty)
+  *n_seg_out = n_seg;
+  const dim3 grid(strips, n_seg);
+  knn_nearest_kernel<KIND, TY, W><<<grid, dim3(256), 0, st>>>(a, r1, b, r2, n_dims, metric, p, k, n_ct, tiles_per_seg, w.seg_key, w.seg_idx, w.seg_n, w.seg_drop);
+  KPOP_LAUNCH_CHECK();
+  const uint32_t rows_grid = std::min(r2, 1u << 20);
+  knn_merge_kernel<<<dim3(rows_grid), dim3(64), 0, st>>>(w.seg_key, w.seg_idx, w.seg_n, w.seg_drop, n_seg, r2, k, w.m_key, w.m_idx, w.m_n, w.m_tau, w.m_flag);
+  KPOP_LAUNCH_CHECK();
+  knn_ties_kernel<KIND, TY, W><<<grid, dim3(256), 0, st>>>(a, r1, b, r2, n_dims, metric, p, n_ct, tiles_per_seg, class_of, n_classes, w.m_tau, w.m_flag, w.tie_total,
+                                                        w.tie_count, w.tie_first);
+  KPOP_LAUNCH_CHECK();
+  return 0;
+}
+
+template <int KIND>
+static int knn_passes_of(const double *a, uint32_t r1, const double *b, uint32_t r2, uint32_t n_dims, const double *metric, double p, uint32_t k,
+                         const uint32_t *class_of, uint32_t n_classes, const KnnWork &w, uint32_t *n_seg, hipStream_t st) {
+  const uint32_t TJ = knn_strip_rows(k);
+  if (TJ == 64) return knn_passes<KIND, 4, 64>(a, r1, b, r2, n_dims, metric, p, k, class_of, n_classes, w, n_seg, st);
+  if (TJ == 32) return knn_passes<KIND, 2, 64>(a, r1, b, r2, n_dims, metric, p, k, class_of, n_classes, w, n_seg, st);
+  return knn_passes<KIND, 1, 64>(a, r1, b, r2, n_dims, metric, p, k, class_of, n_classes, w, n_seg, st);
+}
+
+static int knn_check_sizes(uint32_t k, uint32_t n_classes, const char *who) {
+  if (k == 0) KPOP_FAIL(KPOP_ERR_INVALID, "%s: k = 0", who);
+  if (k > (uint32_t)kKMaxK) KPOP_FAIL(KPOP_ERR_UNSUPPORTED, "%s: k = %u (at most %d)", who, k, kKMaxK);
+  if (n_classes == 0) KPOP_FAIL(KPOP_ERR_INVALID, "%s: no classes", who);
+  if (n_classes > kKMaxClasses) KPOP_FAIL(KPOP_ERR_UNSUPPORTED, "%s: %u classes (at most %u)", who, n_classes, kKMaxClasses);
+  return 0;
+}
+
+// the body of both entry points: enqueues only
+static int knn_dev(kpop_refset *rs, const uint32_t *d_class_of, uint32_t n_classes, const double *d_m2, uint32_t r2, uint32_t k, void *d_work,
+                   uint32_t *d_out_class, uint32_t *d_out_votes, uint32_t *d_out_n, double *d_out_first_dist, hipStream_t st, const char *who) {
+  KPOP_TRY(knn_check_sizes(k, n_classes, who));
+  if (r2 == 0) return KPOP_OK;
+  if (!d_out_class || !d_out_votes || !d_out_n || !d_work) KPOP_FAIL(KPOP_ERR_INVALID, "%s: null argument", who);
+  const uint32_t r1 = rs->r1, D = rs->n_dims;
+  if (r1 && (!d_class_of || !d_m2)) KPOP_FAIL(KPOP_ERR_INVALID, "%s: null argument", who);
+  if (div_up(r2, 16) > 0x7FFFFFFFull) KPOP_FAIL(KPOP_ERR_UNSUPPORTED, "%s: %u query rows", who, r2);
+  const KnnWork w = knn_carve(d_work, r2, k, n_classes, D, rs->normalize != 0);
+  const uint32_t rows_grid = std::min(r2, 1u << 20);
+  uint32_t n_seg = 0;
+  if (r1 == 0) {
+    KPOP_HIP(hipMemsetAsync(w.m_n, 0, (uint64_t)r2 * 4, st));  // every list is empty
+  } else {
+    KPOP_HIP(hipMemsetAsync(reinterpret_cast<char *>(d_work) + w.tables_off, 0, w.tables_bytes, st));
+    KPOP_HIP(hipMemsetAsync(w.tie_first, 0xFF, (uint64_t)r2 * n_classes * 4, st));
+    const double *a = rs->rows, *b = d_m2;
+    if (rs->normalize) {  // the set's quotients from its copy, the query rows' from the norms' pass: prepare_operands' (distance.hip)
+      KPOP_TRY(rs->prepared(st));
+      KPOP_TRY(rs->divided(st, &a));
+      KPOP_TRY(refset_query_norms(rs, d_m2, r2, w.n2, w.b, st));
+      b = w.b;
+    }
+    switch (rs->kind) {
+      case KPOP_EUCLIDEAN: KPOP_TRY(knn_passes_of<KPOP_EUCLIDEAN>(a, r1, b, r2, D, rs->metric, rs->p, k, d_class_of, n_classes, w, &n_seg, st)); break;
+      case KPOP_COSINE: KPOP_TRY(knn_passes_of<KPOP_COSINE>(a, r1, b, r2, D, rs->metric, rs->p, k, d_class_of, n_classes, w, &n_seg, st)); break;
+      default: KPOP_TRY(knn_passes_of<KPOP_MINKOWSKI>(a, r1, b, r2, D, rs->metric, rs->p, k, d_class_of, n_classes, w, &n_seg, st)); break;
+    }
+  }
+  knn_vote_kernel<<<dim3(rows_grid), dim3(64), 0, st>>>(w.seg_key, w.seg_idx, w.seg_n, n_seg, r2, k, w.m_key, w.m_idx, w.m_n, w.m_tau, w.m_flag, d_class_of, n_classes,
+                                                        w.tie_total, w.tie_count, w.tie_first, d_out_class, d_out_votes, d_out_n, d_out_first_dist);
+  KPOP_LAUNCH_CHECK();
+  return KPOP_OK;
+}
+
+}  // namespace kpop
+
+using namespace kpop;
+
+extern "C" uint64_t kpop_dev_knn_vote_workspace_bytes(const kpop_refset *rs, uint32_t r2, uint32_t k, uint32_t n_classes) {
+  if (!rs) return 0;
+  return knn_carve(nullptr, r2, k, n_classes, rs->n_dims, rs->normalize != 0).bytes;
+}
+
+extern "C" int kpop_dev_knn_vote(kpop_refset *rs, const uint32_t *d_class_of, uint32_t n_classes, const double *d_m2, uint32_t r2, uint32_t k, void *d_work,
+                                 uint32_t *d_out_class, uint32_t *d_out_votes, uint32_t *d_out_n, double *d_out_first_dist, void *stream) {
+  const char *who = "kpop_dev_knn_vote";
+  KPOP_TRY(refset_check_handle(rs, who));
+  return knn_dev(rs, d_class_of, n_classes, d_m2, r2, k, d_work, d_out_class, d_out_votes, d_out_n, d_out_first_dist, as_stream(stream), who);
+}
+
+extern "C" int kpop_knn_vote(kpop_refset *rs, const uint32_t *class_of, uint32_t n_classes, const double *m2, uint32_t r2, uint32_t k, uint32_t *out_class,
+                             uint32_t *out_votes, uint32_t *out_n, double *out_first_dist) {
+  const char *who = "kpop_knn_vote";
+  KPOP_TRY(refset_check_handle(rs, who));
+  ArenaScope scratch;
+  KPOP_TRY(knn_check_sizes(k, n_classes, who));
+  const uint32_t r1 = rs->r1, D = rs->n_dims;
+  if ((r1 && !class_of) || (r2 && (!out_class || !out_votes || !out_n)) || (r1 && r2 && !m2)) KPOP_FAIL(KPOP_ERR_INVALID, "%s: null argument", who);
+  for (uint32_t i = 0; i < r1; ++i)
+    if (class_of[i] >= n_classes) KPOP_FAIL(KPOP_ERR_INVALID, "%s: row %u has class %u of %u", who, i, class_of[i], n_classes);
+  if (r2 == 0) return KPOP_OK;
+  hipStream_t st = nullptr;
+  // the query rows in chunks that keep the workspace bounded (a quarter of a GiB, or what 64 rows take)
+  const uint64_t per_row = knn_carve(nullptr, 1024, k, n_classes, D, rs->normalize != 0).bytes / 1024 + (uint64_t)D * 8 + 32;
+  const uint32_t chunk = (uint32_t)std::min<uint64_t>(r2, std::max<uint64_t>(64, (256ull << 20) / per_row));
+  DevBuf dc, d2, dw, ocl, ovo, on, ofd;
+  KPOP_TRY(dc.alloc((uint64_t)r1 * 4));
+  KPOP_TRY(d2.alloc((uint64_t)chunk * D * 8));
+  // (the last chunk may be cut into more segments than a whole one: the larger of the two workspaces)
+  KPOP_TRY(dw.alloc(std::max(kpop_dev_knn_vote_workspace_bytes(rs, chunk, k, n_classes),
+                             kpop_dev_knn_vote_workspace_bytes(rs, r2 % chunk ? r2 % chunk : chunk, k, n_classes))));
+  KPOP_TRY(ocl.alloc((uint64_t)chunk * 4));
+  KPOP_TRY(ovo.alloc((uint64_t)chunk * 4));
+  KPOP_TRY(on.alloc((uint64_t)chunk * 4));
+  KPOP_TRY(ofd.alloc((uint64_t)chunk * 8));
+  if (r1) KPOP_HIP(hipMemcpyAsync(dc.p, class_of, (uint64_t)r1 * 4, hipMemcpyHostToDevice, st));
+  for (uint32_t j0 = 0; j0 < r2; j0 += chunk) {
+    const uint32_t nr = std::min(chunk, r2 - j0);
+    if (r1) KPOP_HIP(hipMemcpyAsync(d2.p, m2 + (uint64_t)j0 * D, (uint64_t)nr * D * 8, hipMemcpyHostToDevice, st));
+    KPOP_TRY(knn_dev(rs, dc.as<uint32_t>(), n_classes, d2.as<double>(), nr, k, dw.p, ocl.as<uint32_t>(), ovo.as<uint32_t>(), on.as<uint32_t>(), ofd.as<double>(), st,
+                     who));
+    KPOP_HIP(hipMemcpyAsync(out_class + j0, ocl.p, (uint64_t)nr * 4, hipMemcpyDeviceToHost, st));
+    KPOP_HIP(hipMemcpyAsync(out_votes + j0, ovo.p, (uint64_t)nr * 4, hipMemcpyDeviceToHost, st));
+    KPOP_HIP(hipMemcpyAsync(out_n + j0, on.p, (uint64_t)nr * 4, hipMemcpyDeviceToHost, st));
+    if (out_first_dist) KPOP_HIP(hipMemcpyAsync(out_first_dist + j0, ofd.p, (uint64_t)nr * 8, hipMemcpyDeviceToHost, st));
+    KPOP_HIP(hipStreamSynchronize(st));
+  }
+  return KPOP_OK;
+}
+
+extern "C" int kpop_distance_knn_vote(const double *m1, uint32_t r1, const uint32_t *class_of, uint32_t n_classes, const double *m2, uint32_t r2, uint32_t n_dims,
+                                      const double *metric, int kind, double p, int normalize, uint32_t k, uint32_t *out_class, uint32_t *out_votes,
+                                      uint32_t *out_n, double *out_first_dist) {
+  kpop_refset *rs = nullptr;
+  KPOP_TRY(kpop_refset_create(m1, r1, n_dims, metric, kind, p, normalize, 0, &rs));
+  const int rc = kpop_knn_vote(rs, class_of, n_classes, m2, r2, k, out_class, out_votes, out_n, out_first_dist);
+  const int rc_free = kpop_refset_free(rs);
+  return rc ? rc : rc_free;
+}
