@@ -767,6 +767,69 @@ int kpop_distance_knn_vote(const double *m1, uint32_t r1, const uint32_t *class_
                            uint32_t k, uint32_t *out_class, uint32_t *out_votes, uint32_t *out_n,
                            double *out_first_dist);
 
+/* ------------------------------------------------- k-NN validation (leave-out votes of a labelled set, many k in one pass)
+ * How good is a labelled set as a classifier, which k (the README leaves it open: "of course the number of neighbours
+ * could be chosen to be different", README.md:770), and which rows disagree with their own neighbours (its classes are
+ * "heterogeneous collections", README.md:1087)?  The reference answers by a hold-out run and awk (README.md:1077-1085).
+ * Everything not said here is the block above's: the distance (lib/Space.ml:182-205 with the adaptors of
+ * lib/Matrix.ml:243-250), the key order (d with -0 as +0, index), whole tie groups (lib/Matrix.ml:641-650), a NaN never a
+ * neighbour, +inf a number, the vote's tie-break (README.md:773-775).
+ * VOTES FOR MANY k (*_knn_ks_vote; RefSet.knn_vote_ks in Python): ks[n_ks] strictly ascending, each in 1..128, n_ks in 1..32; the outputs are
+ * [n_ks][r2] row-major, and slice t is bit for bit what kpop_knn_vote returns for k = ks[t].  One pass over the pairs at
+ * K = ks[n_ks-1] (and one for the rows whose tie group at the K-th distance is longer than the slots hold) serves every
+ * t: the launches that do distance arithmetic do not depend on n_ks.
+ * LEAVE-OUT VOTES (*_knn_validate): the query rows are the set's own rows.  Left out of row j's list: row j itself when
+ * group_of == NULL (leave-one-out); otherwise every row i with group_of[i] == group_of[j], j among them (k-fold
+ * cross-validation: group_of = the fold; "sequences of one outbreak do not vote for each other": group_of = the
+ * outbreak).  By index or group, never by distance: a duplicate of j in another group stays, at distance 0.  d(j, i) is
+ * the bits kpop_refset_distance_rowwise writes to out[j][i] under kpop_tune("distance_mfma", 0) with the set's rows as
+ * the query: kpop_clusters_within's definition.  Per ks[t], [n_ks][rows] row-major: out_class, out_votes, out_n,
+ * out_first_dist (may be NULL), and out_correct[t], the rows with out_class == class_of[row] (KPOP_NO_CLASS is never
+ * correct).  A row with no list -- r1 = 1, every other distance a NaN, the whole set in its group -- gives
+ * KPOP_NO_CLASS, 0, 0, NaN.  A function of the distances, classes and groups alone: the same bits on every run; no
+ * kpop_tune setting is read.
+ * ERRORS: ks empty, not strictly ascending or holding a 0: KPOP_ERR_INVALID; a k above 128 or n_ks > 32:
+ * KPOP_ERR_UNSUPPORTED; n_classes as above.  MEASURED (profiles/knn_validate.md; 100,000 x 64, six k up to 31): the
+ * validation takes 123.8 ms, one kpop_dev_knn_vote over the same rows at k = 31 takes 122.6 ms, six of them 692.8 ms.   */
+/* (lib/Matrix.ml:641-650 for the list; lib/Space.ml:182-205 for the distances.)  Host arrays; class_of[i] >= n_classes is
+   KPOP_ERR_INVALID.  The query rows go through in chunks that keep the workspace bounded.  Synchronises.               */
+int kpop_knn_ks_vote(kpop_refset *rs, const uint32_t *class_of, uint32_t n_classes, const double *m2, uint32_t r2,
+                     const uint32_t *ks, uint32_t n_ks, uint32_t *out_class, uint32_t *out_votes, uint32_t *out_n,
+                     double *out_first_dist);
+/* bytes of d_work for kpop_dev_knn_ks_vote (the lists of lib/Matrix.ml:641-650): kpop_dev_knn_vote_workspace_bytes at
+   k = k_max, the largest k; does not grow with the set or with n_ks                                                    */
+uint64_t kpop_dev_knn_ks_vote_workspace_bytes(const kpop_refset *rs, uint32_t r2, uint32_t k_max, uint32_t n_classes);
+/* (lib/Matrix.ml:641-650; lib/Space.ml:182-205.)  Enqueues only: reads nothing back, allocates nothing.  ks is in HOST
+   memory and is handed to the kernels by value; everything else is device memory.  d_class_of[r1] is TRUSTED, every table
+   access guarded, as in kpop_dev_knn_vote.  d_out_*: [n_ks][r2]                                                        */
+int kpop_dev_knn_ks_vote(kpop_refset *rs, const uint32_t *d_class_of, uint32_t n_classes, const double *d_m2, uint32_t r2,
+                         const uint32_t *ks, uint32_t n_ks, void *d_work, uint32_t *d_out_class, uint32_t *d_out_votes,
+                         uint32_t *d_out_n, double *d_out_first_dist, void *stream);
+/* (lib/Matrix.ml:641-650 for the list; lib/Space.ml:182-205 for the distances; README.md:1077-1085 for the accuracy.)
+   Host arrays, [n_ks][r1] and out_correct[n_ks]; class_of[i] >= n_classes is KPOP_ERR_INVALID; group_of NULL:
+   leave-one-out.  The set's rows go through in ranges that keep the workspace bounded, out_correct summed over them;
+   the query side of a range is the set's own divided copy: no second copy of the rows.  Synchronises.                  */
+int kpop_knn_validate(kpop_refset *rs, const uint32_t *class_of, uint32_t n_classes, const uint32_t *group_of,
+                      const uint32_t *ks, uint32_t n_ks, uint32_t *out_class, uint32_t *out_votes, uint32_t *out_n,
+                      double *out_first_dist, uint64_t *out_correct);
+/* bytes of d_work for kpop_dev_knn_validate over n_rows rows (the lists of lib/Matrix.ml:641-650): the vote's without a
+   query side; does not grow with the set or with n_ks                                                                  */
+uint64_t kpop_dev_knn_validate_workspace_bytes(const kpop_refset *rs, uint32_t n_rows, uint32_t k_max, uint32_t n_classes);
+/* (lib/Matrix.ml:641-650; lib/Space.ml:182-205.)  Rows first_row .. first_row + n_rows of the set against the whole set
+   (beyond r1: KPOP_ERR_INVALID).  Enqueues only: reads nothing back, allocates nothing.  ks in HOST memory, by value to
+   the kernels.  d_class_of[r1] TRUSTED, every table access guarded; d_group_of[r1] or NULL.  d_out_*: [n_ks][n_rows];
+   d_out_correct[n_ks] is WRITTEN for this range, not accumulated                                                       */
+int kpop_dev_knn_validate(kpop_refset *rs, const uint32_t *d_class_of, uint32_t n_classes, const uint32_t *d_group_of,
+                          uint32_t first_row, uint32_t n_rows, const uint32_t *ks, uint32_t n_ks, void *d_work,
+                          uint32_t *d_out_class, uint32_t *d_out_votes, uint32_t *d_out_n, double *d_out_first_dist,
+                          uint64_t *d_out_correct, void *stream);
+/* unprepared convenience (lib/Matrix.ml:191-266 for the distances, m against itself; :641-650 for the list): a temporary
+   set over m, then kpop_knn_validate                                                                                   */
+int kpop_distance_knn_validate(const double *m, uint32_t rows, uint32_t n_dims, const double *metric, int kind, double p,
+                               int normalize, const uint32_t *class_of, uint32_t n_classes, const uint32_t *group_of,
+                               const uint32_t *ks, uint32_t n_ks, uint32_t *out_class, uint32_t *out_votes,
+                               uint32_t *out_n, double *out_first_dist, uint64_t *out_correct);
+
 /* ------------------------------------------------- k-mer database (KPopCountDB)
  * the operations of lib/KMerDB.ml that touch every count.  A database is the reference's
  * `storage: I32BAVector.t array` (lib/KMerDB.ml:54-63): n_cols spectra ("columns"), each a vector of n_rows int32

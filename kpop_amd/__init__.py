@@ -13,7 +13,8 @@ from .api import (check, COSINE, DNA_DS, DNA_SS, PROTEIN, EUCLIDEAN, METRIC_FLAT
                   sharded_distance_summary, RefSet, dev_refset_workspace_bytes, dev_refset_distance_rowwise, dev_refset_distance_summary,
                   dev_neighbours_within_workspace_bytes, dev_neighbours_within, distance_within, dev_clusters_within_workspace_bytes,
                   dev_clusters_within, distance_clusters, dev_spanning_forest_workspace_bytes, dev_spanning_forest, distance_spanning_forest,
-                  forest_cut, NO_CLASS, dev_knn_vote_workspace_bytes, dev_knn_vote, distance_knn_vote)
+                  forest_cut, NO_CLASS, dev_knn_vote_workspace_bytes, dev_knn_vote, distance_knn_vote, dev_knn_vote_ks_workspace_bytes,
+                  dev_knn_vote_ks, dev_knn_validate_workspace_bytes, dev_knn_validate, distance_knn_validate, confusion_matrix)
 
 __all__ = ["init", "device_count", "count_reads", "Twister", "ca", "metric_compute", "distance_rowwise",
            "distance_summary", "embeddings", "splits_gaps", "summarize_distances", "parse_distance", "KPopError", "DNA_DS", "DNA_SS", "PROTEIN", "EUCLIDEAN", "COSINE",
@@ -24,4 +25,5 @@ __all__ = ["init", "device_count", "count_reads", "Twister", "ca", "metric_compu
            "dev_refset_distance_rowwise", "dev_refset_distance_summary", "dev_neighbours_within_workspace_bytes",
            "dev_neighbours_within", "distance_within", "dev_clusters_within_workspace_bytes", "dev_clusters_within",
            "distance_clusters", "dev_spanning_forest_workspace_bytes", "dev_spanning_forest", "distance_spanning_forest", "forest_cut",
-           "NO_CLASS", "dev_knn_vote_workspace_bytes", "dev_knn_vote", "distance_knn_vote"]
+           "NO_CLASS", "dev_knn_vote_workspace_bytes", "dev_knn_vote", "distance_knn_vote", "dev_knn_vote_ks_workspace_bytes", "dev_knn_vote_ks",
+           "dev_knn_validate_workspace_bytes", "dev_knn_validate", "distance_knn_validate", "confusion_matrix"]

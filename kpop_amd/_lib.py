@@ -184,6 +184,15 @@ SIGNATURES = {
     "kpop_dev_knn_vote": (C.c_int, [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp]),
     "kpop_distance_knn_vote": (C.c_int, [f64p, C.c_uint32, u32p, C.c_uint32, f64p, C.c_uint32, C.c_uint32, f64p, C.c_int, C.c_double, C.c_int, C.c_uint32,
                                          u32p, u32p, u32p, f64p]),
+    # k-NN validation: many k in one pass, leave-out votes (knn_validate.hip)
+    "kpop_knn_ks_vote": (C.c_int, [vp, u32p, C.c_uint32, f64p, C.c_uint32, u32p, C.c_uint32, u32p, u32p, u32p, f64p]),
+    "kpop_dev_knn_ks_vote_workspace_bytes": (C.c_uint64, [vp, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "kpop_dev_knn_ks_vote": (C.c_int, [vp, vp, C.c_uint32, vp, C.c_uint32, u32p, C.c_uint32, vp, vp, vp, vp, vp, vp]),
+    "kpop_knn_validate": (C.c_int, [vp, u32p, C.c_uint32, u32p, u32p, C.c_uint32, u32p, u32p, u32p, f64p, u64p]),
+    "kpop_dev_knn_validate_workspace_bytes": (C.c_uint64, [vp, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "kpop_dev_knn_validate": (C.c_int, [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, u32p, C.c_uint32, vp, vp, vp, vp, vp, vp, vp]),
+    "kpop_distance_knn_validate": (C.c_int, [f64p, C.c_uint32, C.c_uint32, f64p, C.c_int, C.c_double, C.c_int, u32p, C.c_uint32, u32p, u32p, C.c_uint32,
+                                             u32p, u32p, u32p, f64p, u64p]),
 }
 
 

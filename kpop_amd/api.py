@@ -879,6 +879,42 @@ class RefSet:
                                         _p(_nz(first, np.float64), C.c_double)))
         return cls, votes, n, first
 
+    def knn_vote_ks(self, m2, class_of, ks, n_classes=None):
+        """knn_vote at every k of ks (strictly ascending, each in 1..128, at most 32 of them) from ONE pass over the pairs ->
+        (cls, votes, n, first), each [len(ks)][rows of m2]; slice t is knn_vote(m2, class_of, k=ks[t]) bit for bit (kpop_knn_ks_vote,
+        include/kpop_hip.h)."""
+        m2 = _c(m2, np.float64)
+        i = self.info()
+        if m2.ndim != 2 or m2.shape[1] != i["n_dims"]:
+            raise ValueError("Incompatible_geometries")
+        class_of, n_classes = _classes(class_of, i["r1"], n_classes)
+        ks = _ks(ks)
+        r2 = m2.shape[0]
+        cls, votes, n, first = _ks_outputs(len(ks), r2)
+        check(_lib.load().kpop_knn_ks_vote(self._h, _p(_nz(class_of, np.uint32), C.c_uint32), n_classes, _p(_nz(m2, np.float64), C.c_double), r2,
+                                           _p(_nz(ks, np.uint32), C.c_uint32), len(ks), _p(_nz(cls, np.uint32), C.c_uint32),
+                                           _p(_nz(votes, np.uint32), C.c_uint32), _p(_nz(n, np.uint32), C.c_uint32), _p(_nz(first, np.float64), C.c_double)))
+        return cls, votes, n, first
+
+    def knn_validate(self, class_of, ks=(1, 3, 5), group_of=None, n_classes=None):
+        """The set as its own test: every row classified by its neighbours among the OTHER rows, at every k of ks, from one pass over the
+        pairs -> (cls, votes, n, first, correct): the first four [len(ks)][r1] as knn_vote_ks gives them, correct[t] (u64) the rows whose
+        class at ks[t] is their own.  group_of=None leaves out the row itself (leave-one-out); otherwise every row of the row's group is
+        left out of its list (the fold of a cross-validation, an outbreak) -- by index or group, never by distance: a duplicate in another
+        group stays.  A row with no list gives NO_CLASS, 0, 0, NaN and is never correct (kpop_knn_validate, include/kpop_hip.h)."""
+        i = self.info()
+        r1 = i["r1"]
+        class_of, n_classes = _classes(class_of, r1, n_classes)
+        group_of = _groups(group_of, r1)
+        ks = _ks(ks)
+        cls, votes, n, first = _ks_outputs(len(ks), r1)
+        correct = np.zeros(max(len(ks), 1), dtype=np.uint64)
+        check(_lib.load().kpop_knn_validate(self._h, _p(_nz(class_of, np.uint32), C.c_uint32), n_classes,
+                                            None if group_of is None else _p(_nz(group_of, np.uint32), C.c_uint32), _p(_nz(ks, np.uint32), C.c_uint32), len(ks),
+                                            _p(_nz(cls, np.uint32), C.c_uint32), _p(_nz(votes, np.uint32), C.c_uint32), _p(_nz(n, np.uint32), C.c_uint32),
+                                            _p(_nz(first, np.float64), C.c_double), _p(correct, C.c_uint64)))
+        return cls, votes, n, first, correct[:len(ks)]
+
     def free(self):
         if self._h is not None and self._h.value:
             check(_lib.load().kpop_refset_free(self._h))
@@ -1061,6 +1097,94 @@ def distance_knn_vote(m1, class_of, m2, metric, k=5, kind=EUCLIDEAN, p=2.0, norm
                                              float(p), 1 if normalize else 0, int(k), _p(_nz(cls, np.uint32), C.c_uint32),
                                              _p(_nz(votes, np.uint32), C.c_uint32), _p(_nz(n, np.uint32), C.c_uint32), _p(_nz(first, np.float64), C.c_double)))
     return cls, votes, n, first
+
+
+def _ks(ks):
+    """a ladder of k as the C ABI takes it (the library checks it: strictly ascending, 1..128, at most 32)"""
+    ks = np.asarray(ks)
+    if ks.ndim != 1 or (len(ks) and (ks.min() < 0 or ks.max() > 0xFFFFFFFF)):
+        raise ValueError("ks: a list of k, each a uint32")
+    return _c(ks, np.uint32)
+
+
+def _groups(group_of, r1):
+    if group_of is None:
+        return None
+    group_of = np.asarray(group_of)
+    if group_of.ndim != 1 or len(group_of) != r1:
+        raise ValueError("group_of: one group for each of the set's %d rows" % r1)
+    if len(group_of) and (group_of.min() < 0 or group_of.max() > 0xFFFFFFFF):
+        raise ValueError("group_of: groups are uint32")
+    return _c(group_of, np.uint32)
+
+
+def _ks_outputs(n_ks, rows):
+    cls, votes, n = (np.zeros((n_ks, rows), dtype=np.uint32) for _ in range(3))
+    return cls, votes, n, np.zeros((n_ks, rows), dtype=np.float64)
+
+
+def dev_knn_vote_ks_workspace_bytes(rs, r2, k_max, n_classes):
+    """the size of d_work for dev_knn_vote_ks: dev_knn_vote's at the largest k; it grows neither with the set nor with len(ks)"""
+    return int(_lib.load().kpop_dev_knn_ks_vote_workspace_bytes(rs.handle, int(r2), int(k_max), int(n_classes)))
+
+
+def dev_knn_vote_ks(rs, d_class_of, n_classes, d_m2, r2, ks, d_work, d_cls, d_votes, d_n, d_first=None, stream=0):
+    """enqueue only: d_cls / d_votes / d_n (u32 [len(ks)][r2]) and d_first (f64, or None) as RefSet.knn_vote_ks returns them; ks is a
+    host sequence (it goes to the kernels by value), d_class_of (u32, one a row of the set) is trusted"""
+    ks = _ks(ks)
+    check(_lib.load().kpop_dev_knn_ks_vote(rs.handle, d_class_of, int(n_classes), d_m2, int(r2), _p(_nz(ks, np.uint32), C.c_uint32), len(ks), d_work, d_cls,
+                                           d_votes, d_n, d_first, stream))
+
+
+def dev_knn_validate_workspace_bytes(rs, n_rows, k_max, n_classes):
+    """the size of d_work for dev_knn_validate over n_rows rows: it grows neither with the set nor with len(ks)"""
+    return int(_lib.load().kpop_dev_knn_validate_workspace_bytes(rs.handle, int(n_rows), int(k_max), int(n_classes)))
+
+
+def dev_knn_validate(rs, d_class_of, n_classes, d_group_of, first_row, n_rows, ks, d_work, d_cls, d_votes, d_n, d_first, d_correct, stream=0):
+    """enqueue only: rows first_row .. first_row + n_rows of the set against the whole set; d_cls / d_votes / d_n (u32 [len(ks)][n_rows]),
+    d_first (f64, or None) and d_correct (u64 [len(ks)], written for this range, not accumulated) as RefSet.knn_validate returns them;
+    d_group_of (u32, one a row of the set) or None: leave-one-out; ks is a host sequence"""
+    ks = _ks(ks)
+    check(_lib.load().kpop_dev_knn_validate(rs.handle, d_class_of, int(n_classes), d_group_of, int(first_row), int(n_rows), _p(_nz(ks, np.uint32), C.c_uint32),
+                                            len(ks), d_work, d_cls, d_votes, d_n, d_first, d_correct, stream))
+
+
+def distance_knn_validate(m, class_of, metric, ks=(1, 3, 5), group_of=None, kind=EUCLIDEAN, p=2.0, normalize=True, n_classes=None):
+    """RefSet(m, ...).knn_validate(class_of, ks, group_of) without keeping the set: one call of kpop_distance_knn_validate"""
+    m, metric = _c(m, np.float64), _c(metric, np.float64)
+    if m.ndim != 2 or m.shape[1] != len(metric):
+        raise ValueError("Incompatible_geometries")  # lib/Matrix.ml:193-194
+    r1 = m.shape[0]
+    class_of, n_classes = _classes(class_of, r1, n_classes)
+    group_of = _groups(group_of, r1)
+    ks = _ks(ks)
+    cls, votes, n, first = _ks_outputs(len(ks), r1)
+    correct = np.zeros(max(len(ks), 1), dtype=np.uint64)
+    check(_lib.load().kpop_distance_knn_validate(_p(_nz(m, np.float64), C.c_double), r1, len(metric), _p(_nz(metric, np.float64), C.c_double), int(kind),
+                                                 float(p), 1 if normalize else 0, _p(_nz(class_of, np.uint32), C.c_uint32), n_classes,
+                                                 None if group_of is None else _p(_nz(group_of, np.uint32), C.c_uint32),
+                                                 _p(_nz(ks, np.uint32), C.c_uint32), len(ks), _p(_nz(cls, np.uint32), C.c_uint32),
+                                                 _p(_nz(votes, np.uint32), C.c_uint32), _p(_nz(n, np.uint32), C.c_uint32), _p(_nz(first, np.float64), C.c_double),
+                                                 _p(correct, C.c_uint64)))
+    return cls, votes, n, first, correct[:len(ks)]
+
+
+def confusion_matrix(class_of, predicted, n_classes):
+    """host bookkeeping (numpy): M[c][q] = the rows of class c that were given class q, with one more column, M[c][n_classes], for
+    NO_CLASS; the diagonal's sum is knn_validate's `correct` of that slice"""
+    class_of, predicted = np.asarray(class_of, dtype=np.int64), np.asarray(predicted, dtype=np.int64)
+    n_classes = int(n_classes)
+    if class_of.shape != predicted.shape or class_of.ndim != 1:
+        raise ValueError("confusion_matrix: one prediction for each row")
+    if len(class_of) and (class_of.min() < 0 or class_of.max() >= n_classes):
+        raise ValueError("confusion_matrix: a class is not below n_classes")
+    col = np.where(predicted == NO_CLASS, n_classes, predicted)
+    if len(col) and (col.min() < 0 or col.max() > n_classes):
+        raise ValueError("confusion_matrix: a prediction is neither a class nor NO_CLASS")
+    out = np.zeros((n_classes, n_classes + 1), dtype=np.int64)
+    np.add.at(out, (class_of, col), 1)
+    return out
 
 
 def dev_neighbours_within_workspace_bytes(rs, r2, capacity):

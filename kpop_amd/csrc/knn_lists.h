@@ -1,0 +1,169 @@
+// knn_lists.h -- what the k-NN vote (knn.hip) and the k-NN validation (knn_validate.hip) share: the keys and their order, a row's sorted
+// list in LDS and the insertion into it, the workgroup shapes, the workspace's layout and the limits.  The kernels stay in their files,
+// each with its own copy of the tile loop; knn.hip launches its own for knn_validate.hip's many-k vote (knn_run_passes) and its merge
+// for both (knn_run_merge).
+#pragma once
+#include <algorithm>
+
+#include "common.h"
+
+namespace kpop {
+
+constexpr int kKDC = 16, kKMaxK = 128;
+// a workgroup's shape: W columns (rows of the set) x TJ query rows, a thread 4 columns x TY rows
+template <int TY, int W>
+struct KnnShape {
+  static constexpr uint32_t NCG = W / 4, NRG = 256 / NCG, TJ = TY * NRG;
+  static constexpr uint32_t SLOTS = 2048;  // list slots of the workgroup: TJ k <= SLOTS, the whole within 64 KiB of LDS
+};
+constexpr int kKMaxSeg = 128, kKBlocks = 512;                // segments a strip at most; workgroups a launch aims at (two a CU)
+constexpr int kKMaxTies = 1024;                              // listed ties of a row that knn_vote_kernel takes from the lists; more: the tables
+constexpr int kKVoteList = kKMaxK + kKMaxTies;               // knn_vote_kernel: < k entries below tau, then the listed ties
+constexpr uint64_t kKNone = ~0ull;                           // (no key: knn_key maps only a NaN's bits there, and a NaN is never a key)
+constexpr uint32_t kKMaxClasses = 65535;
+constexpr uint32_t kKMaxKs = 32;                             // the cut points of one list (knn_validate.hip)
+
+// a distance that is a number -> a key that orders as the distance does; -0 is taken as +0 (forest.hip's dist_key)
+__device__ __forceinline__ uint64_t knn_key(double d) {
+  if (d == 0.0) d = 0.0;
+  const uint64_t b = (uint64_t)__double_as_longlong(d);
+  return (b >> 63) ? ~b : (b | (1ull << 63));
+}
+__device__ __forceinline__ double knn_key_dist(uint64_t k) { return __longlong_as_double((long long)((k >> 63) ? (k & ~(1ull << 63)) : ~k)); }
+__device__ __forceinline__ bool knn_less(uint64_t ka, uint32_t ia, uint64_t kb, uint32_t ib) { return ka < kb || (ka == kb && ia < ib); }
+
+// One candidate into a row's sorted list, by the whole wavefront that owns the row (every argument is the same in all 64 lanes).
+// lk, li: the row's k slots; *np its length; *bp, *bip its bound (kKNone until the list is full, then its k-th key and index); *dp its
+// dropped ties.
+// A lane holds slots lane and lane + 64 (k <= 128).  The slots are read into registers before any is written, and the LDS serves a
+// wavefront's accesses in the order it issued them: volatile keeps the compiler from moving them.
+__device__ __forceinline__ void knn_insert(volatile uint64_t *lk, volatile uint32_t *li, volatile uint32_t *np, volatile uint64_t *bp, volatile uint32_t *bip,
+                                           volatile uint32_t *dp, uint32_t k, uint64_t ck, uint32_t ci, uint32_t lane) {
+  const uint32_t n = *np;
+  uint64_t bk = 0;
+  if (n == k) {
+    bk = lk[k - 1];
+    const uint32_t bi = li[k - 1];
+    if (ck > bk) return;
+    if (ck == bk && ci > bi) {  // refused, a tie of the k-th key
+      if (lane == 0) *dp = *dp + 1;
+      return;
+    }
+  }
+  const uint32_t q0 = lane, q1 = lane + 64;
+  const uint64_t e0k = q0 < n ? lk[q0] : 0, e1k = q1 < n ? lk[q1] : 0;
+  const uint32_t e0i = q0 < n ? li[q0] : 0, e1i = q1 < n ? li[q1] : 0;
+  const uint32_t pos = (uint32_t)__popcll(__ballot(q0 < n && knn_less(e0k, e0i, ck, ci))) + (uint32_t)__popcll(__ballot(q1 < n && knn_less(e1k, e1i, ck, ci)));
+  // (pos <= n, and pos < k: a full list was entered only below its last entry)
+  if (q0 < n && q0 >= pos && q0 + 1 < k) {
+    lk[q0 + 1] = e0k;
+    li[q0 + 1] = e0i;
+  }
+  if (q1 < n && q1 >= pos && q1 + 1 < k) {
+    lk[q1 + 1] = e1k;
+    li[q1 + 1] = e1i;
+  }
+  if (lane == 0) {
+    lk[pos] = ck;
+    li[pos] = ci;
+  }
+  if (n < k) {
+    if (lane == 0) *np = n + 1;
+    if (n + 1 == k) {
+      const uint64_t nk = lk[k - 1];
+      const uint32_t ni = li[k - 1];
+      if (lane == 0) {
+        *bp = nk;
+        *bip = ni;
+      }
+    }
+  } else {  // the old last entry, of key bk, was evicted
+    const uint64_t nk = lk[k - 1];
+    const uint32_t ni = li[k - 1];
+    if (lane == 0) {
+      *dp = (nk == bk) ? *dp + 1 : 0u;
+      *bp = nk;
+      *bip = ni;
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+}
+
+// the column tiles of a segment
+__device__ __forceinline__ void knn_segment(uint32_t n_ct, uint32_t tiles_per_seg, uint32_t *t_begin, uint32_t *t_end) {
+  *t_begin = min(n_ct, blockIdx.y * tiles_per_seg);
+  *t_end = min(n_ct, *t_begin + tiles_per_seg);
+}
+
+struct KnnBest {
+  uint32_t cnt, idx, cls;
+  uint64_t key;
+};
+__device__ __forceinline__ bool knn_better(const KnnBest &x, const KnnBest &y) {  // more members; among equally many, the nearer first member
+  return x.cnt > y.cnt || (x.cnt == y.cnt && x.cnt > 0 && knn_less(x.key, x.idx, y.key, y.idx));
+}
+
+// the workspace, carved: the query rows' norms and divided copy, the segments' lists, the merged lists, the tie tables.  It depends on
+// r2, k, n_classes, the set's n_dims and the constants above; not on r1
+struct KnnWork {
+  double *n2, *b;
+  uint64_t *seg_key, *m_key, *m_tau;
+  uint32_t *seg_idx, *seg_n, *seg_drop, *m_idx, *m_n, *m_flag, *tie_total, *tie_count, *tie_first;
+  uint64_t tables_off, tables_bytes, bytes;
+};
+
+// the rows of a strip by k, so that their lists fit the workgroup's slots: 64 columns x 64, 32 or 16 rows, a thread 4 x 4, 2 or 1.
+// (The choice moves no bit: a pair's chain is one thread's either way.  rowwise_block's 32 columns x 256 rows, a thread 4 x 8, was
+// tried for k <= 6 against long sets and measured slower here -- profiles/knn_vote.md -- and is not built.)
+static uint32_t knn_strip_rows(uint32_t k) { return k <= 2048 / 64 ? 64u : k <= 2048 / 32 ? 32u : 16u; }
+// the segments the columns are cut into at most: as many as make kKBlocks workgroups with the strips of r2 query rows (forest.hip's
+// reason: a few query rows still fill the chip).  By r2 and k alone, so that the workspace does not depend on the set
+static uint32_t knn_max_segments(uint32_t r2, uint32_t strip_rows) {
+  return std::max(1u, std::min<uint32_t>(kKMaxSeg, div_up(kKBlocks, std::max(1u, div_up(r2, strip_rows)))));
+}
+
+static KnnWork knn_carve(void *work, uint32_t r2, uint32_t k, uint32_t n_classes, uint32_t n_dims, bool normalize) {
+  char *base = reinterpret_cast<char *>(work);
+  uint64_t off = 0;
+  auto take = [&](uint64_t bytes) {
+    char *q = base + off;
+    off += (bytes + 255) & ~255ull;
+    return q;
+  };
+  const uint64_t n = r2, lists = n * k, segs = knn_max_segments(r2, knn_strip_rows(k));
+  KnnWork w;
+  w.n2 = reinterpret_cast<double *>(take(normalize ? n * 8 : 0));
+  w.b = reinterpret_cast<double *>(take(normalize ? n * n_dims * 8 : 0));
+  w.seg_key = reinterpret_cast<uint64_t *>(take(lists * 8 * segs));
+  w.seg_idx = reinterpret_cast<uint32_t *>(take(lists * 4 * segs));
+  w.seg_n = reinterpret_cast<uint32_t *>(take(n * 4 * segs));
+  w.seg_drop = reinterpret_cast<uint32_t *>(take(n * 4 * segs));
+  w.m_key = reinterpret_cast<uint64_t *>(take(lists * 8));
+  w.m_idx = reinterpret_cast<uint32_t *>(take(lists * 4));
+  w.m_tau = reinterpret_cast<uint64_t *>(take(n * 8));
+  w.m_n = reinterpret_cast<uint32_t *>(take(n * 4));
+  w.m_flag = reinterpret_cast<uint32_t *>(take(n * 4));
+  w.tables_off = off;
+  w.tie_total = reinterpret_cast<uint32_t *>(take(n * 4));
+  w.tie_count = reinterpret_cast<uint32_t *>(take(n * n_classes * 4));
+  w.tables_bytes = off - w.tables_off;  // (zeroes)
+  w.tie_first = reinterpret_cast<uint32_t *>(take(n * n_classes * 4));  // (ones)
+  w.bytes = off + 256;
+  return w;
+}
+
+static int knn_check_sizes(uint32_t k, uint32_t n_classes, const char *who) {
+  if (k == 0) KPOP_FAIL(KPOP_ERR_INVALID, "%s: k = 0", who);
+  if (k > (uint32_t)kKMaxK) KPOP_FAIL(KPOP_ERR_UNSUPPORTED, "%s: k = %u (at most %d)", who, k, kKMaxK);
+  if (n_classes == 0) KPOP_FAIL(KPOP_ERR_INVALID, "%s: no classes", who);
+  if (n_classes > kKMaxClasses) KPOP_FAIL(KPOP_ERR_UNSUPPORTED, "%s: %u classes (at most %u)", who, n_classes, kKMaxClasses);
+  return 0;
+}
+
+// knn.hip: its own three passes over the pairs -- knn_nearest_kernel, knn_merge_kernel, knn_ties_kernel -- for the set's kind, and the
+// merge alone over segments' lists that another nearest pass wrote (knn_validate.hip).  Both enqueue only
+int knn_run_passes(int kind, const double *a, uint32_t r1, const double *b, uint32_t r2, uint32_t n_dims, const double *metric, double p, uint32_t k,
+                   const uint32_t *class_of, uint32_t n_classes, const KnnWork &w, uint32_t *n_seg, hipStream_t st);
+int knn_run_merge(const KnnWork &w, uint32_t n_seg, uint32_t r2, uint32_t k, hipStream_t st);
+
+}  // namespace kpop
