@@ -9,72 +9,27 @@
 // Neither a pair nor a list is ever written: the self-join's hits go straight into a union-find forest that lives in the labels.
 //   clusters_init_kernel     parent[i] = i for the rows that are new (i >= known_rows); the rows below carry the labels of an earlier
 //                            call at the same distance, which are a forest of depth one already
-//   clusters_tile_kernel     the arithmetic of within_tile_kernel (within.hip), operation for operation, both operands the set (its
+//   clusters_tile_kernel     the arithmetic of within_tile_kernel (within.hip), the same loop (pair_tile.h), both operands the set (its
 //                            divided copy when it normalises); tiles of the upper triangle only, none that lies below known_rows on
 //                            both sides.  The epilogue compares where that kernel compares, unites the tile's hits in LDS (a forest
 //                            over the tile's columns and rows: thousands of hits inside a dense lineage cost LDS traffic alone), and
 //                            then every node of the tile that is not its local root is united with that root in `parent`: at most
 //                            one global union per column and row of the tile, whatever the number of hits
-//   the union                lock-free, hooks the LARGER root under the smaller with one compare-and-swap; finds halve the paths.
-//                            Only a root is ever hooked, and only under a smaller index: the forest stays acyclic, a row that has
-//                            stopped being a root never becomes one again, and the last root of a component is its smallest index
-//                            whoever arrives first.  A failed compare-and-swap means somebody else hooked that root: progress, and
-//                            nothing waits on another workgroup
+//   the union                lock-free (union_find.h): the LARGER root hooked under the smaller, so that the last root of a
+//                            component is its smallest index whoever arrives first, and nothing waits on another workgroup
 //   clusters_flatten_kernel  a launch of its own after the tiles: labels[i] = the root of i (finds that store nothing but that), and
 //                            the count of the roots, an integer sum
-// The same copy of the staging-and-accumulate loop as within.hip's, kept here so that within_tile_kernel stays the kernel it was.
 #include <algorithm>
 
 #include "common.h"
 #include "distance_routes.h"
+#include "pair_tile.h"
 #include "space_ops.h"
+#include "union_find.h"
 
 namespace kpop {
 
-constexpr int kCDC = 16, kCMaxW = 64, kCMaxTJ = 256;
-
-// parent words are read and written by many workgroups at once: relaxed atomics at SCOPE (the device's for `parent` in HBM, the
-// workgroup's for a tile's forest in LDS), so that no read is served from a stale line of a compute unit's own cache
-template <int SCOPE>
-__device__ __forceinline__ uint32_t uf_load(uint32_t *q) { return __hip_atomic_load(q, __ATOMIC_RELAXED, SCOPE); }
-
-// the root of x, halving the path on the way.  A plain store of a grandparent into a node that is not a root: whoever hooks a root
-// compares against the root's own index, which a node that has a parent no longer holds
-template <int SCOPE>
-__device__ __forceinline__ uint32_t uf_find(uint32_t *parent, uint32_t x) {
-  for (;;) {
-    const uint32_t q = uf_load<SCOPE>(parent + x);
-    if (q == x) return x;
-    const uint32_t g = uf_load<SCOPE>(parent + q);
-    if (g == q) return q;
-    __hip_atomic_store(parent + x, g, __ATOMIC_RELAXED, SCOPE);
-    x = g;
-  }
-}
-
-template <int SCOPE>
-__device__ __forceinline__ uint32_t uf_find_readonly(uint32_t *parent, uint32_t x) {
-  for (;;) {
-    const uint32_t q = uf_load<SCOPE>(parent + x);
-    if (q == x) return x;
-    x = q;
-  }
-}
-
-template <int SCOPE>
-__device__ __forceinline__ void uf_unite(uint32_t *parent, uint32_t a, uint32_t b) {
-  if (uf_load<SCOPE>(parent + a) == uf_load<SCOPE>(parent + b)) return;  // the same parent: the same component (most hits of a dense lineage)
-  for (;;) {
-    a = uf_find<SCOPE>(parent, a);
-    b = uf_find<SCOPE>(parent, b);
-    if (a == b) return;
-    const uint32_t hi = max(a, b), lo = min(a, b);
-    uint32_t expected = hi;
-    if (__hip_atomic_compare_exchange_strong(parent + hi, &expected, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED, SCOPE)) return;
-    a = hi;  // somebody else hooked hi in the meantime: from there again
-    b = lo;
-  }
-}
+constexpr int kCMaxW = 64, kCMaxTJ = 256;
 
 __global__ __launch_bounds__(256) void clusters_init_kernel(uint32_t *__restrict__ parent, uint32_t known_rows, uint32_t r1) {
   for (uint64_t i = (uint64_t)known_rows + (uint64_t)blockIdx.x * 256 + threadIdx.x; i < r1; i += (uint64_t)gridDim.x * 256) parent[i] = (uint32_t)i;
@@ -90,9 +45,9 @@ __global__ __launch_bounds__(256, 1) void clusters_tile_kernel(const double *__r
                                                                const double *__restrict__ metric, double p, double max_distance, uint32_t n_cg,
                                                                uint32_t n_rg, uint32_t kf, uint32_t by_first, uint32_t n_act, uint32_t ybase,
                                                                uint32_t known_rows, uint32_t *parent) {
-  __shared__ __attribute__((aligned(16))) double As[kCDC][kCMaxW + 2];
-  __shared__ __attribute__((aligned(16))) double Bs[kCDC][kCMaxTJ + 2];
-  __shared__ double s_metric[kCDC];
+  __shared__ __attribute__((aligned(16))) double As[kPairDC][kCMaxW + 2];
+  __shared__ __attribute__((aligned(16))) double Bs[kPairDC][kCMaxTJ + 2];
+  __shared__ double s_metric[kPairDC];
   __shared__ uint32_t s_par[kCMaxW + kCMaxTJ];  // the tile's forest: the columns first, then the rows
   const uint32_t TJ = TY * n_rg;
   // which tile
@@ -114,55 +69,15 @@ __global__ __launch_bounds__(256, 1) void clusters_tile_kernel(const double *__r
   const uint32_t ti = cg * 4, tj = (worker ? rg : 0) * TY;
   for (uint32_t n = threadIdx.x; n < w + TJ; n += 256) s_par[n] = n;  // (the loop's barriers come before anybody unites)
   double acc[TY][4];
-#pragma unroll
-  for (int yy = 0; yy < TY; ++yy)
-#pragma unroll
-    for (int x = 0; x < 4; ++x) acc[yy][x] = 0.0;
-  constexpr int NA = kCMaxW * kCDC / 256, NB = kCMaxTJ * kCDC / 256;
-  double ra[NA], rb[NB];
-  const uint32_t sc = threadIdx.x % kCDC, rbase = threadIdx.x / kCDC;
-  auto prefetch = [&](uint32_t c0) {
-    const bool cok = c0 + sc < n_dims;
-#pragma unroll
-    for (int q = 0; q < NA; ++q) {
-      const uint32_t row = rbase + q * 16;
-      ra[q] = (cok && row < w && i0 + row < i1) ? a[(uint64_t)(i0 + row) * n_dims + c0 + sc] : 0.0;
-    }
-#pragma unroll
-    for (int q = 0; q < NB; ++q) {
-      const uint32_t row = rbase + q * 16;
-      rb[q] = (cok && row < TJ && j0 + row < j1) ? a[(uint64_t)(j0 + row) * n_dims + c0 + sc] : 0.0;
-    }
-  };
-  prefetch(0);
-  for (uint32_t c0 = 0; c0 < n_dims; c0 += kCDC) {
+  pair_zero(acc);
+  PairStage<kCMaxW, kCMaxTJ> stage;
+  stage.load(a, i0, i1, a, j0, j1, n_dims, 0, n_dims);
+  for (uint32_t c0 = 0; c0 < n_dims; c0 += kPairDC) {
     __syncthreads();
-#pragma unroll
-    for (int q = 0; q < NA; ++q) As[sc][rbase + q * 16] = ra[q];
-#pragma unroll
-    for (int q = 0; q < NB; ++q) Bs[sc][rbase + q * 16] = rb[q];
-    if (threadIdx.x < kCDC) s_metric[threadIdx.x] = (c0 + threadIdx.x < n_dims) ? metric[c0 + threadIdx.x] : 0.0;
+    stage.store(As, Bs, s_metric, metric, c0, n_dims);
     __syncthreads();
-    if (c0 + kCDC < n_dims) prefetch(c0 + kCDC);
-    const uint32_t lim = min((uint32_t)kCDC, n_dims - c0);
-    if (worker) {
-      for (uint32_t cc = 0; cc < lim; ++cc) {
-        double av[4], bv[TY];
-#pragma unroll
-        for (int x = 0; x < 4; ++x) av[x] = As[cc][ti + x];
-#pragma unroll
-        for (int yy = 0; yy < TY; ++yy) bv[yy] = Bs[cc][tj + yy];
-        const double mc = s_metric[cc];
-#pragma unroll
-        for (int yy = 0; yy < TY; ++yy)
-#pragma unroll
-          for (int x = 0; x < 4; ++x) {
-            // lib/Space.ml:192-200: diff = a -. b ; acc +. (diff *. diff *. m)
-            double diff = __dsub_rn(av[x], bv[yy]);
-            acc[yy][x] = __dadd_rn(acc[yy][x], component<KIND>(diff, mc, p));
-          }
-      }
-    }
+    if (c0 + kPairDC < n_dims) stage.load(a, i0, i1, a, j0, j1, n_dims, c0 + kPairDC, n_dims);
+    if (worker) pair_accumulate<KIND>(acc, As, Bs, s_metric, ti, tj, min((uint32_t)kPairDC, n_dims - c0), p);
   }
   // the epilogue: compare where within_tile_kernel compares (a NaN compares false: it joins nothing); only i < j, and no pair of
   // two known rows (i < j: the pair is one iff j is known)

@@ -81,9 +81,10 @@ constexpr int kDC = 16, kMaxW = 128, kMaxTJ = 256;
 // applies the scale.  SLAB = false is the hot path: one block walks all the dimensions, the sum is the reference's.
 // MAXTJ: the most second-operand rows a block stages (TJ <= MAXTJ).  With 128 (one column tile of 61..127 columns: distances to a
 // set of classes) and the rows' norms in LDS instead of 48 registers the kernel fits 168 VGPRs: three wavefronts a SIMD, not two.
-// TWIN: within_tile_kernel (within.hip) repeats this kernel's staging, prefetch and inner loop (the SLAB = false, undivided form) with an
-// epilogue that compares instead of storing, and within_tiles repeats rowwise_block's choice of tiles.  Its results must be this kernel's
-// bits (tests/test_gpu_within.py): a change to the order of operations here goes there as well.
+// TWIN: pair_tile.h holds this kernel's staging, prefetch and inner loop (the SLAB = false, undivided form) for every kernel that must
+// give this kernel's bits -- within.hip, clusters.hip, forest.hip, knn.hip (tests/test_gpu_within.py and its neighbours).  This kernel
+// keeps its own text: built on that header its instantiations need more registers (profiles/pair_tile_refactor.md).  A change to the
+// order of operations here goes into pair_accumulate as well, and the other way round.
 template <int KIND, bool SLAB = false, int TY = 4, int MAXTJ = 256>
 __global__ __launch_bounds__(256, MAXTJ == 128 ? 3 : 1) void distance_rowwise_kernel(const double *__restrict__ a, uint32_t w, uint32_t r1,
                                                                const double *__restrict__ b, uint32_t r2,
@@ -361,15 +362,6 @@ __global__ __launch_bounds__(1024) void distance_summary_kernel(
 constexpr size_t kWaveSummaryHalf = 78u << 10, kWaveSummaryWhole = 159u << 10;
 constexpr int kSummaryWaves = 16;  // per block: they share the LDS copy of the first operand, and 2 blocks fill a CU's 32 wave slots
 
-__device__ __forceinline__ uint64_t dist_key(double x) {  // order-preserving map of an f64 to u64
-  const uint64_t b = (uint64_t)__double_as_longlong(x);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double key_dist(uint64_t k) {
-  const uint64_t b = (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
-  return __longlong_as_double((long long)b);
-}
-
 constexpr int kWaveTail = 8;  // columns beyond 64 R that the TAIL variant takes in by rank instead of doubling the network
 
 __device__ __forceinline__ double wave_readlane_f64(double v, int l) {  // l uniform
@@ -470,20 +462,20 @@ __global__ __launch_bounds__(64 * kSummaryWaves) void distance_summary_wave_kern
 #pragma unroll
     for (int q = 0; q < R; ++q) {
       const uint32_t i = (uint32_t)lane + 64u * q;
-      key[q] = i < r1 ? dist_key(dv[q]) : ~0ull;  // padding sorts last (a NaN distance would too; none arises from finite rows)
+      key[q] = i < r1 ? f64_key(dv[q]) : ~0ull;  // padding sorts last (a NaN distance would too; none arises from finite rows)
       val[q] = i < r1 ? i : 0xFFFFFFFFu;
     }
     if (!(dbg & 1)) wave_bitonic_sort_pairs<R, uint64_t>(key, val, lane);
     if (!TAIL) {
 #pragma unroll
       for (int q = 0; q < R; ++q) {  // sorted position of (lane, q) is lane * R + q
-        kd[lane * R + q] = key_dist(key[q]);
+        kd[lane * R + q] = key_f64(key[q]);
         ki[lane * R + q] = val[q];
       }
     } else {
       // the tail's columns come after every sorted one (larger index): a tail element goes behind the sorted elements <= it
       // and the tail elements before it in (distance, column) order; a sorted element moves up by the tail elements < it
-      const uint64_t tkey = (uint32_t)lane < n_tail ? dist_key(dt) : ~0ull;
+      const uint64_t tkey = (uint32_t)lane < n_tail ? f64_key(dt) : ~0ull;
       uint32_t shift[R], my_pos = 0;
 #pragma unroll
       for (int q = 0; q < R; ++q) shift[q] = 0;
@@ -501,7 +493,7 @@ __global__ __launch_bounds__(64 * kSummaryWaves) void distance_summary_wave_kern
       }
 #pragma unroll
       for (int q = 0; q < R; ++q) {
-        kd[lane * R + q + shift[q]] = key_dist(key[q]);
+        kd[lane * R + q + shift[q]] = key_f64(key[q]);
         ki[lane * R + q + shift[q]] = val[q];
       }
       if ((uint32_t)lane < n_tail) {
@@ -588,13 +580,13 @@ __global__ __launch_bounds__(64 * kSummaryWaves) void distance_summary_wave_kern
     for (int q = 0; q < RP; ++q) mk[q] = ~0ull;
 #pragma unroll
     for (int q = 0; q < RS; ++q)
-      if (((uint32_t)q * 64u + lane) < r1) mk[q] = dist_key(fabs(__dsub_rn(sv[q], median)));
+      if (((uint32_t)q * 64u + lane) < r1) mk[q] = f64_key(fabs(__dsub_rn(sv[q], median)));
     if (!(dbg & 4)) wave_bitonic_merge_striped<RP, uint64_t>(mk, lane);
     const uint32_t mpos = r1 / 2;  // sorted position q * 64 + lane
     double mad = 0.0;
 #pragma unroll
     for (int q = 0; q < RS; ++q)
-      if (r1 > 0 && (mpos >> 6) == (uint32_t)q) mad = wave_readlane_f64(key_dist(mk[q]), (int)(mpos & 63u));
+      if (r1 > 0 && (mpos >> 6) == (uint32_t)q) mad = wave_readlane_f64(key_f64(mk[q]), (int)(mpos & 63u));
     if (lane == 0) {
       out_stats[(uint64_t)j * 4 + 0] = mean;
       out_stats[(uint64_t)j * 4 + 1] = sd;
@@ -792,7 +784,7 @@ __global__ __launch_bounds__(64 * kSummaryWaves) void distance_summary_batch_ker
 #pragma unroll
       for (int q = 0; q < R; ++q) {
         const uint32_t i = (uint32_t)lane + 64u * q;
-        key[q] = i < r1 ? dist_key(dv[r][q]) : ~0ull;  // padding sorts last
+        key[q] = i < r1 ? f64_key(dv[r][q]) : ~0ull;  // padding sorts last
         val[q] = i < r1 ? i : 0xFFFFFFFFu;
       }
       if (!(dbg & 1)) wave_bitonic_sort_pairs<R, uint64_t>(key, val, lane);
@@ -801,14 +793,14 @@ __global__ __launch_bounds__(64 * kSummaryWaves) void distance_summary_batch_ker
         for (int q = 0; q < R; ++q) {  // sorted position of (lane, q) is lane * R + q; padding lies beyond r1
           const uint32_t pos = (uint32_t)lane * R + q;
           if (pos < r1) {
-            kd_r[pos] = key_dist(key[q]);
+            kd_r[pos] = key_f64(key[q]);
             ki_r[pos] = val[q];
           }
         }
       } else {
         // (as in distance_summary_wave_kernel) a tail element goes behind the sorted elements <= it and the tail elements before it
         // in (distance, column) order; a sorted element moves up by the tail elements < it
-        const uint64_t tkey = (uint32_t)lane < n_tail ? dist_key(dt[r]) : ~0ull;
+        const uint64_t tkey = (uint32_t)lane < n_tail ? f64_key(dt[r]) : ~0ull;
         uint32_t shift[R], my_pos = 0;
 #pragma unroll
         for (int q = 0; q < R; ++q) shift[q] = 0;
@@ -826,7 +818,7 @@ __global__ __launch_bounds__(64 * kSummaryWaves) void distance_summary_batch_ker
         }
 #pragma unroll
         for (int q = 0; q < R; ++q) {
-          kd_r[lane * R + q + shift[q]] = key_dist(key[q]);
+          kd_r[lane * R + q + shift[q]] = key_f64(key[q]);
           ki_r[lane * R + q + shift[q]] = val[q];
         }
         if ((uint32_t)lane < n_tail) {
@@ -1576,7 +1568,7 @@ __global__ void long_list_keys_kernel(const double *__restrict__ d, uint32_t r1,
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < r1) {
     const double x = d[i];
-    key[i] = dist_key(x == 0.0 ? 0.0 : x);  // the kernels' own order (-0 as +0): a caller's matrix may hold negative entries or NaNs
+    key[i] = f64_key(x == 0.0 ? 0.0 : x);  // the kernels' own order (-0 as +0): a caller's matrix may hold negative entries or NaNs
     val[i] = i;
   }
 }
@@ -1628,7 +1620,7 @@ static int fill_long_lists(const LongListSource &src, uint32_t r1, uint32_t r2, 
     KPOP_HIP(hipStreamSynchronize(st));
     const double mean = out.stats[(uint64_t)j * 4 + 0], sd = out.stats[(uint64_t)j * 4 + 1];
     for (uint32_t q = 0; q < m; ++q) {
-      const uint64_t kq = hk[q], bq = (kq >> 63) ? (kq & 0x7FFFFFFFFFFFFFFFull) : ~kq;  // key_dist on the host
+      const uint64_t kq = hk[q], bq = (kq >> 63) ? (kq & 0x7FFFFFFFFFFFFFFFull) : ~kq;  // key_f64 on the host
       double dq;
       memcpy(&dq, &bq, 8);
       out.dist[(uint64_t)j * max_neighbours + q] = dq;

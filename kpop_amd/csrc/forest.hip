@@ -9,7 +9,7 @@
 //   forest_tile_labels_kernel  per tile of w rows: the label its rows share, or "mixed" -- a tile of the pass below whose rows and
 //                              columns all carry one label holds no foreign pair and is skipped (the late rounds are mostly that)
 //   forest_nearest_kernel      per row, the least allowed edge to a row of ANOTHER component.  The arithmetic of
-//                              clusters_tile_kernel (clusters.hip), operation for operation: a pair's bits are the chain's.  A
+//                              clusters_tile_kernel (clusters.hip), the same loop (pair_tile.h): a pair's bits are the chain's.  A
 //                              workgroup owns a strip of TJ rows and walks the column tiles of its segment of the set, columns
 //                              ascending; every thread keeps the best (key, column) of its TY rows in registers, the threads of a
 //                              row are neighbouring lanes and reduce with shuffles, one store a row and segment.  For a fixed row r
@@ -21,7 +21,7 @@
 //   forest_comp_edge_kernel    among the rows that hold their component's least key: atomicMin of (i << 32 | j), i < j
 //   forest_link_kernel         a component emits its edge unless the component at the other end chose the SAME edge and has the
 //                              smaller label (the edge is then emitted once, by that one), and unites with the other end: the
-//                              lock-free union of clusters.hip, the larger root hooked under the smaller with one compare-and-swap
+//                              lock-free union of union_find.h, the larger root hooked under the smaller with one compare-and-swap
 //   forest_flatten_kernel      labels[i] = the root of i, the smallest index of its component: section 6d's labels when the rounds end
 // No cycle can form: under a strict total order the least edge that leaves a component belongs to THE minimum spanning forest (the
 // cut property, without ties to break), so every edge emitted in any round is an edge of that one forest, and a subset of a forest
@@ -30,65 +30,22 @@
 // many; every kernel of a round returns at once when the word of the round before says that it added no edge -- nothing is read
 // back.  The host form reads the word and stops.  Edges arrive in any order; they are sorted on the device by (d, i, j): two stable
 // radix sorts (radix_sort.h), the pair first, the distance's key second.
-// The same copy of the staging-and-accumulate loop as clusters.hip's and within.hip's, kept here so that those kernels stay the
-// kernels they were.
+// The tile loop is pair_tile.h's, the union union_find.h's, the distance's key space_ops.h's.
 #include <algorithm>
 
 #include "common.h"
 #include "distance_routes.h"
+#include "pair_tile.h"
 #include "radix_sort.h"
 #include "refset.h"
 #include "space_ops.h"
+#include "union_find.h"
 
 namespace kpop {
 
-constexpr int kFDC = 16, kFMaxW = 64, kFMaxTJ = 256, kFMaxSeg = 8, kFMaxRounds = 32;
+constexpr int kFMaxW = 64, kFMaxTJ = 256, kFMaxSeg = 8, kFMaxRounds = 32;
 constexpr uint32_t kFMixed = 0xFFFFFFFFu;  // (no label: labels are row indices, below r1 <= 2^32 - 1)
-constexpr uint64_t kFNone = ~0ull;         // (no key: dist_key maps only a NaN's bits there, and a NaN is never a key)
-
-// a distance that is a number -> a key that orders as the distance does; -0 is taken as +0
-__device__ __forceinline__ uint64_t dist_key(double d) {
-  if (d == 0.0) d = 0.0;
-  const uint64_t b = (uint64_t)__double_as_longlong(d);
-  return (b >> 63) ? ~b : (b | (1ull << 63));
-}
-__device__ __forceinline__ double key_dist(uint64_t k) { return __longlong_as_double((long long)((k >> 63) ? (k & ~(1ull << 63)) : ~k)); }
-
-// clusters.hip's union-find, on words that many workgroups read and write at once: relaxed atomics at the device's scope
-__device__ __forceinline__ uint32_t fuf_load(uint32_t *q) { return __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ __forceinline__ uint32_t fuf_find(uint32_t *parent, uint32_t x) {
-  for (;;) {
-    const uint32_t q = fuf_load(parent + x);
-    if (q == x) return x;
-    const uint32_t g = fuf_load(parent + q);
-    if (g == q) return q;
-    __hip_atomic_store(parent + x, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    x = g;
-  }
-}
-
-__device__ __forceinline__ uint32_t fuf_find_readonly(uint32_t *parent, uint32_t x) {
-  for (;;) {
-    const uint32_t q = fuf_load(parent + x);
-    if (q == x) return x;
-    x = q;
-  }
-}
-
-// only a root is ever hooked, and only under a smaller index: acyclic, and the last root of a component is its smallest index
-__device__ __forceinline__ void fuf_unite(uint32_t *parent, uint32_t a, uint32_t b) {
-  for (;;) {
-    a = fuf_find(parent, a);
-    b = fuf_find(parent, b);
-    if (a == b) return;
-    const uint32_t hi = max(a, b), lo = min(a, b);
-    uint32_t expected = hi;
-    if (__hip_atomic_compare_exchange_strong(parent + hi, &expected, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
-    a = hi;  // somebody else hooked hi in the meantime: from there again
-    b = lo;
-  }
-}
+constexpr uint64_t kFNone = ~0ull;         // (no key: distance_key maps only a NaN's bits there, and a NaN is never a key)
 
 #define FOREST_GATE() \
   if (gate && *gate == 0) return  // the round before added no edge: the forest is complete
@@ -134,9 +91,9 @@ __global__ __launch_bounds__(256, 1) void forest_nearest_kernel(const double *__
                                                                 const uint32_t *__restrict__ lab, const uint32_t *__restrict__ tile_lab,
                                                                 uint64_t *__restrict__ part_k, uint32_t *__restrict__ part_c, const uint32_t *gate) {
   FOREST_GATE();
-  __shared__ __attribute__((aligned(16))) double As[kFDC][kFMaxW + 2];
-  __shared__ __attribute__((aligned(16))) double Bs[kFDC][kFMaxTJ + 2];
-  __shared__ double s_metric[kFDC];
+  __shared__ __attribute__((aligned(16))) double As[kPairDC][kFMaxW + 2];
+  __shared__ __attribute__((aligned(16))) double Bs[kPairDC][kFMaxTJ + 2];
+  __shared__ double s_metric[kPairDC];
   const uint32_t TJ = TY * n_rg;
   const uint32_t strip = blockIdx.x, seg = blockIdx.y;
   const uint32_t j0 = strip * TJ, j1 = min(r1, j0 + TJ);  // (the grid has div_up(r1, TJ) strips: j0 < r1)
@@ -160,25 +117,9 @@ __global__ __launch_bounds__(256, 1) void forest_nearest_kernel(const double *__
     best_k[yy] = kFNone;
     best_c[yy] = 0u;
   }
-  constexpr int NA = kFMaxW * kFDC / 256, NB = kFMaxTJ * kFDC / 256;
-  double ra[NA], rb[NB];
-  const uint32_t sc = threadIdx.x % kFDC, rbase = threadIdx.x / kFDC;
-  auto prefetch = [&](uint32_t i0, uint32_t c0) {
-    const uint32_t i1 = min(r1, i0 + w);
-    const bool cok = c0 + sc < n_dims;
-#pragma unroll
-    for (int q = 0; q < NA; ++q) {
-      const uint32_t row = rbase + q * 16;
-      ra[q] = (cok && row < w && i0 + row < i1) ? a[(uint64_t)(i0 + row) * n_dims + c0 + sc] : 0.0;
-    }
-#pragma unroll
-    for (int q = 0; q < NB; ++q) {
-      const uint32_t row = rbase + q * 16;
-      rb[q] = (cok && row < TJ && j0 + row < j1) ? a[(uint64_t)(j0 + row) * n_dims + c0 + sc] : 0.0;
-    }
-  };
+  PairStage<kFMaxW, kFMaxTJ> stage;
   uint32_t t = next_tile(t_begin);
-  if (t < t_end) prefetch(t * w, 0);
+  if (t < t_end) stage.load(a, t * w, min(r1, t * w + w), a, j0, j1, n_dims, 0, n_dims);
   while (t < t_end) {
     const uint32_t t_next = next_tile(t + 1);
     const uint32_t i0 = t * w, i1 = min(r1, i0 + w);
@@ -186,39 +127,15 @@ __global__ __launch_bounds__(256, 1) void forest_nearest_kernel(const double *__
 #pragma unroll
     for (int x = 0; x < 4; ++x) li[x] = (i0 + ti + x < i1) ? lab[i0 + ti + x] : 0u;
     double acc[TY][4];
-#pragma unroll
-    for (int yy = 0; yy < TY; ++yy)
-#pragma unroll
-      for (int x = 0; x < 4; ++x) acc[yy][x] = 0.0;
-    for (uint32_t c0 = 0; c0 < n_dims; c0 += kFDC) {
+    pair_zero(acc);
+    for (uint32_t c0 = 0; c0 < n_dims; c0 += kPairDC) {
       __syncthreads();
-#pragma unroll
-      for (int q = 0; q < NA; ++q) As[sc][rbase + q * 16] = ra[q];
-#pragma unroll
-      for (int q = 0; q < NB; ++q) Bs[sc][rbase + q * 16] = rb[q];
-      if (threadIdx.x < kFDC) s_metric[threadIdx.x] = (c0 + threadIdx.x < n_dims) ? metric[c0 + threadIdx.x] : 0.0;
+      stage.store(As, Bs, s_metric, metric, c0, n_dims);
       __syncthreads();
-      if (c0 + kFDC < n_dims) prefetch(i0, c0 + kFDC);
-      else if (t_next < t_end) prefetch(t_next * w, 0);
-      const uint32_t lim = min((uint32_t)kFDC, n_dims - c0);
-      if (worker) {
-        for (uint32_t cc = 0; cc < lim; ++cc) {
-          double av[4], bv[TY];
-#pragma unroll
-          for (int x = 0; x < 4; ++x) av[x] = As[cc][ti + x];
-#pragma unroll
-          for (int yy = 0; yy < TY; ++yy) bv[yy] = Bs[cc][tj + yy];
-          const double mc = s_metric[cc];
-#pragma unroll
-          for (int yy = 0; yy < TY; ++yy)
-#pragma unroll
-            for (int x = 0; x < 4; ++x) {
-              // lib/Space.ml:192-200: diff = a -. b ; acc +. (diff *. diff *. m)
-              double diff = __dsub_rn(av[x], bv[yy]);
-              acc[yy][x] = __dadd_rn(acc[yy][x], component<KIND>(diff, mc, p));
-            }
-        }
-      }
+      const bool more = c0 + kPairDC < n_dims;  // this tile's next dimensions, or the next tile's first
+      const uint32_t ni0 = more ? i0 : t_next * w;
+      if (more || t_next < t_end) stage.load(a, ni0, min(r1, ni0 + w), a, j0, j1, n_dims, more ? c0 + kPairDC : 0u, n_dims);
+      if (worker) pair_accumulate<KIND>(acc, As, Bs, s_metric, ti, tj, min((uint32_t)kPairDC, n_dims - c0), p);
     }
     // the epilogue: compare where clusters_tile_kernel compares (a NaN compares false: no edge), a row of another component only
     // (which the row itself never is); columns ascend within the tile and from tile to tile, so that `below` alone keeps, among
@@ -231,7 +148,7 @@ __global__ __launch_bounds__(256, 1) void forest_nearest_kernel(const double *__
           const double d = scale_distance<KIND>(acc[yy][x], p);
           const uint32_t i = i0 + ti + x, j = j0 + tj + yy;
           if (j < j1 && i < i1 && li[x] != lj[yy] && d <= max_distance) {
-            const uint64_t key = dist_key(d);
+            const uint64_t key = distance_key(d);
             if (key < best_k[yy]) {
               best_k[yy] = key;
               best_c[yy] = i;
@@ -317,7 +234,7 @@ __global__ __launch_bounds__(256) void forest_link_kernel(const uint32_t *__rest
       out_e[pos] = e;
     }
     atomicAdd(added, 1u);
-    fuf_unite(par, R, other);
+    uf_unite<__HIP_MEMORY_SCOPE_AGENT>(par, R, other);
   }
 }
 
@@ -327,7 +244,7 @@ __global__ __launch_bounds__(256) void forest_flatten_kernel(uint32_t *par, uint
                                                              uint64_t *__restrict__ comp_e, uint32_t r1, const uint32_t *gate) {
   FOREST_GATE();
   for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < r1; i += (uint64_t)gridDim.x * 256) {
-    const uint32_t root = fuf_find_readonly(par, (uint32_t)i);
+    const uint32_t root = uf_find_readonly<__HIP_MEMORY_SCOPE_AGENT>(par, (uint32_t)i);
     if (root != (uint32_t)i) __hip_atomic_store(par + i, root, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     lab[i] = root;
     comp_k[i] = kFNone;
@@ -346,7 +263,7 @@ __global__ __launch_bounds__(256) void forest_pair_keys_kernel(const uint64_t *_
 }
 
 // the second sort's key: the distance's, in the order the first sort left
-__global__ __launch_bounds__(256) void forest_dist_keys_kernel(const uint64_t *__restrict__ out_k, const uint32_t *__restrict__ slot, uint32_t m,
+__global__ __launch_bounds__(256) void forest_distance_keys_kernel(const uint64_t *__restrict__ out_k, const uint32_t *__restrict__ slot, uint32_t m,
                                                                uint64_t *__restrict__ keys, uint32_t *__restrict__ vals) {
   for (uint64_t q = (uint64_t)blockIdx.x * 256 + threadIdx.x; q < m; q += (uint64_t)gridDim.x * 256) {
     keys[q] = out_k[slot[q]];
@@ -362,7 +279,7 @@ __global__ __launch_bounds__(256) void forest_write_kernel(const uint64_t *__res
     const uint64_t e = out_e[slot[q]];
     edge_i[q] = (uint32_t)(e >> 32);
     edge_j[q] = (uint32_t)e;
-    edge_dist[q] = key_dist(keys[q]);
+    edge_dist[q] = key_f64(keys[q]);
   }
 }
 
@@ -495,7 +412,7 @@ static int forest_dev(kpop_refset *rs, double max_distance, void *d_work, uint32
   uint64_t *ks = nullptr, *k2s = nullptr;
   uint32_t *vs = nullptr, *v2s = nullptr;
   KPOP_TRY(radix_sort_pairs_u64(f.ka, f.kb, f.va, f.vb, m, (int)(2 * jb), f.radix, st, &ks, &vs));
-  forest_dist_keys_kernel<<<dim3(edges_grid), dim3(256), 0, st>>>(f.out_k, vs, m, f.k2a, f.v2a);
+  forest_distance_keys_kernel<<<dim3(edges_grid), dim3(256), 0, st>>>(f.out_k, vs, m, f.k2a, f.v2a);
   KPOP_LAUNCH_CHECK();
   KPOP_TRY(radix_sort_pairs_u64(f.k2a, f.k2b, f.v2a, f.v2b, m, 64, f.radix, st, &k2s, &v2s));
   forest_write_kernel<<<dim3(edges_grid), dim3(256), 0, st>>>(k2s, v2s, f.out_e, d_n_edges, m, d_edge_i, d_edge_j, d_edge_dist);

@@ -9,8 +9,7 @@
 //   is formed; every step is a function of the distances alone: the same bits on every run.
 //
 // Four launches, always the same four (the device form reads nothing back):
-//   knn_nearest_kernel   the arithmetic of distance_rowwise_kernel, operation for operation (the copy of within.hip's and forest.hip's
-//                        staging-and-accumulate loop, kept here so that those kernels stay the kernels they were).  A workgroup owns a
+//   knn_nearest_kernel   the arithmetic of distance_rowwise_kernel, operation for operation (pair_tile.h).  A workgroup owns a
 //                        strip of TJ query rows and walks the column tiles of its segment of the set, columns ascending.  Every row
 //                        has in LDS the sorted list of its k smallest (key, index) so far and the list's bound, its k-th key.  A
 //                        thread compares its 4 x TY finished distances with the bound; after the first tiles almost nothing passes.
@@ -33,98 +32,88 @@
 //                        (unflagged) or from the tables (flagged); the winner by (count descending, first (key, index) ascending).
 // The chain makes no -0 (a sum of terms added to +0, its square root, half or power): a key gives back the distance's bits.
 #include <algorithm>
+#include <type_traits>
 
 #include "common.h"
 #include "distance_routes.h"
 #include "knn_lists.h"
+#include "pair_tile.h"
 #include "refset.h"
 #include "space_ops.h"
 
 namespace kpop {
 
-// (the keys, a row's list and its insertion, the shapes, the workspace and the limits: knn_lists.h, shared with knn_validate.hip)
-// The tile loop.  a: the set's rows, b: the query rows, both as the chain reads them (divided by their rows' norms when the set
-// normalises).  The workgroup's rows j0 .. j1 (at most TJ), its column tiles t_begin .. t_end of W rows of the set each.
-// A thread 4 columns x TY rows, the dimensions ascending in one thread, 16 at a time through LDS: within_tile_kernel's; the next step's
-// operands -- the tile's next 16 dimensions, or the first of the next tile -- are loaded under the arithmetic: forest_nearest_kernel's.
-// epi(i0, i1, acc): what to do with a tile's finished sums.
+// (a row's list and its insertion, the shapes, the workspace and the limits: knn_lists.h, shared with knn_validate.hip)
+// The tile loop (pair_tile.h).  a: the set's rows, b: the query rows, both as the chain reads them (divided by their rows' norms when
+// the set normalises).  The workgroup's rows j0 .. j1 (at most TJ), its column tiles t_begin .. t_end of W rows of the set each; no
+// thread is idle.  The next step's operands -- the tile's next 16 dimensions, or the first of the next tile -- are loaded under the
+// arithmetic.  epi(i0, i1, acc): what to do with a tile's finished sums.
 template <int KIND, int TY, int W, class Epi>
 __device__ __forceinline__ void knn_tiles(const double *__restrict__ a, uint32_t r1, const double *__restrict__ b, uint32_t j0, uint32_t j1, uint32_t n_dims,
                                           const double *__restrict__ metric, double p, uint32_t t_begin, uint32_t t_end, double (*As)[W + 2],
                                           double (*Bs)[KnnShape<TY, W>::TJ + 2], double *s_metric, Epi &&epi) {
   using S = KnnShape<TY, W>;
-  constexpr uint32_t TJ = S::TJ;
-  const uint32_t cg = threadIdx.x % S::NCG, rg = threadIdx.x / S::NCG;
-  const uint32_t ti = cg * 4, tj = rg * TY;
-  constexpr int NA = W * kKDC / 256, NB = TJ * kKDC / 256;
-  double ra[NA], rb[NB];
-  const uint32_t sc = threadIdx.x % kKDC, rbase = threadIdx.x / kKDC;
-  auto prefetch = [&](uint32_t i0, uint32_t c0) {
-    const uint32_t i1 = min(r1, i0 + W);
-    const bool cok = c0 + sc < n_dims;
-#pragma unroll
-    for (int q = 0; q < NA; ++q) {
-      const uint32_t row = rbase + q * 16;
-      ra[q] = (cok && i0 + row < i1) ? a[(uint64_t)(i0 + row) * n_dims + c0 + sc] : 0.0;
-    }
-#pragma unroll
-    for (int q = 0; q < NB; ++q) {
-      const uint32_t row = rbase + q * 16;
-      rb[q] = (cok && j0 + row < j1) ? b[(uint64_t)(j0 + row) * n_dims + c0 + sc] : 0.0;
-    }
-  };
-  if (t_begin < t_end) prefetch(t_begin * W, 0);
+  const uint32_t ti = (threadIdx.x % S::NCG) * 4, tj = (threadIdx.x / S::NCG) * TY;
+  PairStage<W, S::TJ> stage;
+  if (t_begin < t_end) stage.load(a, t_begin * W, min(r1, t_begin * W + W), b, j0, j1, n_dims, 0, n_dims);
   for (uint32_t t = t_begin; t < t_end; ++t) {
     const uint32_t i0 = t * W, i1 = min(r1, i0 + W);
     double acc[TY][4];
-#pragma unroll
-    for (int yy = 0; yy < TY; ++yy)
-#pragma unroll
-      for (int x = 0; x < 4; ++x) acc[yy][x] = 0.0;
-    for (uint32_t c0 = 0; c0 < n_dims; c0 += kKDC) {
+    pair_zero(acc);
+    for (uint32_t c0 = 0; c0 < n_dims; c0 += kPairDC) {
       __syncthreads();
-#pragma unroll
-      for (int q = 0; q < NA; ++q) As[sc][rbase + q * 16] = ra[q];
-#pragma unroll
-      for (int q = 0; q < NB; ++q) Bs[sc][rbase + q * 16] = rb[q];
-      if (threadIdx.x < kKDC) s_metric[threadIdx.x] = (c0 + threadIdx.x < n_dims) ? metric[c0 + threadIdx.x] : 0.0;
+      stage.store(As, Bs, s_metric, metric, c0, n_dims);
       __syncthreads();
-      if (c0 + kKDC < n_dims) prefetch(i0, c0 + kKDC);
-      else if (t + 1 < t_end) prefetch((t + 1) * W, 0);
-      const uint32_t lim = min((uint32_t)kKDC, n_dims - c0);
-      for (uint32_t cc = 0; cc < lim; ++cc) {
-        double av[4], bv[TY];
-#pragma unroll
-        for (int x = 0; x < 4; ++x) av[x] = As[cc][ti + x];
-#pragma unroll
-        for (int yy = 0; yy < TY; ++yy) bv[yy] = Bs[cc][tj + yy];
-        const double mc = s_metric[cc];
-#pragma unroll
-        for (int yy = 0; yy < TY; ++yy)
-#pragma unroll
-          for (int x = 0; x < 4; ++x) {
-            // lib/Space.ml:192-200: diff = a -. b ; acc +. (diff *. diff *. m)
-            double diff = __dsub_rn(av[x], bv[yy]);
-            acc[yy][x] = __dadd_rn(acc[yy][x], component<KIND>(diff, mc, p));
-          }
-      }
+      const bool more = c0 + kPairDC < n_dims;  // this tile's next dimensions, or the next tile's first
+      const uint32_t ni0 = more ? i0 : i0 + W;
+      if (more || t + 1 < t_end) stage.load(a, ni0, min(r1, ni0 + W), b, j0, j1, n_dims, more ? c0 + kPairDC : 0u, n_dims);
+      pair_accumulate<KIND>(acc, As, Bs, s_metric, ti, tj, min((uint32_t)kPairDC, n_dims - c0), p);
     }
     epi(i0, i1, acc);
   }
 }
 
+// Who is left out of a row's list.  The vote: nobody -- every call folds away.  The validation (knn_validate.hip), whose query rows are
+// rows of the set: row j itself, or every row of j's group.  A thread knows its rows' groups (or their indices in the set) for the
+// launch, the tile's four columns' groups for the tile.  left_out(yy, x, i): column i, the thread's x-th, is not a neighbour of its
+// yy-th row
+struct KnnNobodyLeftOut {
+  __device__ __forceinline__ void rows(const uint32_t *, uint32_t, uint32_t) {}
+  __device__ __forceinline__ void columns(uint32_t, uint32_t) {}
+  __device__ __forceinline__ bool left_out(int, int, uint32_t) const { return false; }
+};
+template <int TY>
+struct KnnvLeftOut {
+  const uint32_t *group_of;
+  uint32_t own[TY], col[4];  // group_of set: groups; not set: own[] the rows' indices in the set
+  __device__ __forceinline__ void rows(const uint32_t *g, uint32_t jfirst, uint32_t r1) {
+    group_of = g;
+#pragma unroll
+    for (int yy = 0; yy < TY; ++yy) own[yy] = (g && jfirst + yy < r1) ? g[jfirst + yy] : jfirst + yy;
+  }
+  __device__ __forceinline__ void columns(uint32_t ifirst, uint32_t i1) {
+    if (!group_of) return;
+#pragma unroll
+    for (int x = 0; x < 4; ++x) col[x] = ifirst + x < i1 ? group_of[ifirst + x] : 0u;
+  }
+  __device__ __forceinline__ bool left_out(int yy, int x, uint32_t i) const { return group_of ? col[x] == own[yy] : i == own[yy]; }
+};
+
 // Strip blockIdx.x: query rows j0 .. j0 + TJ; segment blockIdx.y.  seg_key, seg_idx: [segment][r2][k], the list's first seg_n
-// entries ascending; seg_drop: the dropped ties of the list's last key.  TJ k <= SLOTS (the launch sees to it).
-template <int KIND, int TY, int W>
+// entries ascending; seg_drop: the dropped ties of the list's last key.  TJ k <= SLOTS (the launch sees to it).  Who: who is left out;
+// group_of, first_row are read by KnnvLeftOut alone (the query rows are then rows first_row .. first_row + r2 of the set).  A column
+// that is left out is refused before it can be inserted OR counted as a dropped tie: a row whose own index ties with its k-th key would
+// otherwise flag itself.
+template <int KIND, int TY, int W, class Who>
 __global__ __launch_bounds__(256, 1) void knn_nearest_kernel(const double *__restrict__ a, uint32_t r1, const double *__restrict__ b, uint32_t r2, uint32_t n_dims,
                                                              const double *__restrict__ metric, double p, uint32_t k, uint32_t n_ct, uint32_t tiles_per_seg,
-                                                             uint64_t *__restrict__ seg_key, uint32_t *__restrict__ seg_idx, uint32_t *__restrict__ seg_n,
-                                                             uint32_t *__restrict__ seg_drop) {
+                                                             const uint32_t *__restrict__ group_of, uint32_t first_row, uint64_t *__restrict__ seg_key,
+                                                             uint32_t *__restrict__ seg_idx, uint32_t *__restrict__ seg_n, uint32_t *__restrict__ seg_drop) {
   using S = KnnShape<TY, W>;
   constexpr uint32_t TJ = S::TJ;
-  __shared__ __attribute__((aligned(16))) double As[kKDC][W + 2];
-  __shared__ __attribute__((aligned(16))) double Bs[kKDC][TJ + 2];
-  __shared__ double s_metric[kKDC];
+  __shared__ __attribute__((aligned(16))) double As[kPairDC][W + 2];
+  __shared__ __attribute__((aligned(16))) double Bs[kPairDC][TJ + 2];
+  __shared__ double s_metric[kPairDC];
   __shared__ uint64_t s_key[S::SLOTS];
   __shared__ uint32_t s_idx[S::SLOTS];
   __shared__ uint64_t s_bound[TJ];
@@ -141,7 +130,10 @@ __global__ __launch_bounds__(256, 1) void knn_nearest_kernel(const double *__res
   __syncthreads();
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t ti = (threadIdx.x % S::NCG) * 4, tj = (threadIdx.x / S::NCG) * TY;  // (the rows of a wavefront: TJ / 4 in a row, nobody else's)
+  Who out;
+  out.rows(group_of, first_row + j0 + tj, r1);
   knn_tiles<KIND, TY, W>(a, r1, b, j0, j1, n_dims, metric, p, t_begin, t_end, As, Bs, s_metric, [&](uint32_t i0, uint32_t i1, double(&acc)[TY][4]) {
+    out.columns(i0 + ti, i1);
     // the rows' bounds as the step before left them (a row is this wavefront's alone): read again after every step that inserted
     uint64_t bound[TY];
     uint32_t bidx[TY];
@@ -160,8 +152,9 @@ __global__ __launch_bounds__(256, 1) void knn_nearest_kernel(const double *__res
       for (int x = 0; x < 4; ++x) {
         const double d = scale_distance<KIND>(acc[yy][x], p);
         const uint32_t i = i0 + ti + x;
-        const uint64_t key = knn_key(d);
-        const bool number = j0 + row < j1 && i < i1 && d == d;  // a NaN is never a neighbour
+        const uint64_t key = distance_key(d);
+        // a NaN is never a neighbour, and neither is a column that is left out: refused here, in front of the count of dropped ties
+        const bool number = j0 + row < j1 && i < i1 && d == d && !out.left_out(yy, x, i);
         // a tie of the k-th key behind the k-th entry is dropped and counted where it stands: a sum, whatever the order.  These
         // come first, the entries that go into the list after them: one of the orders of arrival, all of which give the same
         if (number && key == bound[yy] && i > bidx[yy]) atomicAdd(&s_drop[row], 1u);
@@ -241,7 +234,7 @@ __global__ __launch_bounds__(64) void knn_merge_kernel(const uint64_t *__restric
         uint32_t lo = 0, hi = seg_n[(uint64_t)s2 * r2 + row];
         while (lo < hi) {  // the first entry of the list that is not below (key, idx)
           const uint32_t mid = (lo + hi) >> 1;
-          if (knn_less(seg_key[b2 + mid], seg_idx[b2 + mid], key, idx)) lo = mid + 1;
+          if (key_less(seg_key[b2 + mid], seg_idx[b2 + mid], key, idx)) lo = mid + 1;
           else hi = mid;
         }
         rank += lo;
@@ -280,17 +273,18 @@ __global__ __launch_bounds__(64) void knn_merge_kernel(const uint64_t *__restric
 }
 
 // the grid of knn_nearest_kernel.  tie_total: [r2], every column of a flagged row at tau; tie_count, tie_first: [r2][n_classes], those
-// of a class and the least index among them (0xFFFFFFFF: none).  class_of is trusted, every table access guarded
-template <int KIND, int TY, int W>
+// of a class and the least index among them (0xFFFFFFFF: none), none of them left out.  class_of is trusted, every table access guarded
+template <int KIND, int TY, int W, class Who>
 __global__ __launch_bounds__(256, 1) void knn_ties_kernel(const double *__restrict__ a, uint32_t r1, const double *__restrict__ b, uint32_t r2, uint32_t n_dims,
                                                           const double *__restrict__ metric, double p, uint32_t n_ct, uint32_t tiles_per_seg,
-                                                          const uint32_t *__restrict__ class_of, uint32_t n_classes, const uint64_t *__restrict__ m_tau,
-                                                          const uint32_t *__restrict__ m_flag, uint32_t *tie_total, uint32_t *tie_count, uint32_t *tie_first) {
+                                                          const uint32_t *__restrict__ group_of, uint32_t first_row, const uint32_t *__restrict__ class_of,
+                                                          uint32_t n_classes, const uint64_t *__restrict__ m_tau, const uint32_t *__restrict__ m_flag,
+                                                          uint32_t *tie_total, uint32_t *tie_count, uint32_t *tie_first) {
   using S = KnnShape<TY, W>;
   constexpr uint32_t TJ = S::TJ;
-  __shared__ __attribute__((aligned(16))) double As[kKDC][W + 2];
-  __shared__ __attribute__((aligned(16))) double Bs[kKDC][TJ + 2];
-  __shared__ double s_metric[kKDC];
+  __shared__ __attribute__((aligned(16))) double As[kPairDC][W + 2];
+  __shared__ __attribute__((aligned(16))) double Bs[kPairDC][TJ + 2];
+  __shared__ double s_metric[kPairDC];
   const uint32_t j0 = blockIdx.x * TJ, j1 = min(r2, j0 + TJ);
   if (!__syncthreads_or(threadIdx.x < TJ && j0 + threadIdx.x < j1 && m_flag[j0 + threadIdx.x] != 0)) return;  // (nearly every workgroup)
   uint32_t t_begin, t_end;
@@ -304,7 +298,10 @@ __global__ __launch_bounds__(256, 1) void knn_ties_kernel(const double *__restri
     fl[yy] = j < j1 && m_flag[j] != 0;
     tau[yy] = fl[yy] ? m_tau[j] : kKNone;
   }
+  Who out;
+  out.rows(group_of, first_row + j0 + tj, r1);
   knn_tiles<KIND, TY, W>(a, r1, b, j0, j1, n_dims, metric, p, t_begin, t_end, As, Bs, s_metric, [&](uint32_t i0, uint32_t i1, double(&acc)[TY][4]) {
+    out.columns(i0 + ti, i1);
 #pragma unroll
     for (int yy = 0; yy < TY; ++yy) {
       if (!fl[yy]) continue;
@@ -313,7 +310,7 @@ __global__ __launch_bounds__(256, 1) void knn_ties_kernel(const double *__restri
       for (int x = 0; x < 4; ++x) {
         const double d = scale_distance<KIND>(acc[yy][x], p);
         const uint32_t i = i0 + ti + x;
-        if (i < i1 && d == d && knn_key(d) == tau[yy]) {
+        if (i < i1 && d == d && !out.left_out(yy, x, i) && distance_key(d) == tau[yy]) {
           atomicAdd(tie_total + j, 1u);
           const uint32_t c = class_of[i];
           if (c < n_classes) {
@@ -393,7 +390,7 @@ __global__ __launch_bounds__(64) void knn_vote_kernel(const uint64_t *__restrict
         const uint32_t pf = phys(f);
         if (s_c[pf] != c) continue;
         ++cnt;
-        if (knn_less(s_k[pf], s_i[pf], s_k[pe], s_i[pe])) first = false;
+        if (key_less(s_k[pf], s_i[pf], s_k[pe], s_i[pe])) first = false;
       }
       if (!first) continue;
       if (flagged) cnt += tie_count[(uint64_t)row * n_classes + c];
@@ -426,53 +423,65 @@ __global__ __launch_bounds__(64) void knn_vote_kernel(const uint64_t *__restrict
       out_class[row] = best.cnt ? best.cls : KPOP_NO_CLASS;
       out_votes[row] = best.cnt;
       out_n[row] = n_list;
-      if (out_first_dist) out_first_dist[row] = best.cnt ? knn_key_dist(best.key) : __longlong_as_double(0x7FF8000000000000ll);
+      if (out_first_dist) out_first_dist[row] = best.cnt ? key_f64(best.key) : __longlong_as_double(0x7FF8000000000000ll);
     }
   }
 }
 
-template <int KIND, int TY, int W>
+// the three passes over the pairs.  LEAVE_OUT: the query rows are rows first_row .. first_row + r2 of the set a, without the rows that
+// group_of leaves out of each list (knn_validate.hip); otherwise the rows of b, and group_of and first_row are not read
+template <int KIND, int TY, int W, bool LEAVE_OUT>
 static int knn_passes(const double *a, uint32_t r1, const double *b, uint32_t r2, uint32_t n_dims, const double *metric, double p, uint32_t k,
-                      const uint32_t *class_of, uint32_t n_classes, const KnnWork &w, uint32_t *n_seg_out, hipStream_t st) {
+                      const uint32_t *group_of, uint32_t first_row, const uint32_t *class_of, uint32_t n_classes, const KnnWork &w, uint32_t *n_seg_out,
+                      hipStream_t st) {
+  using Who = std::conditional_t<LEAVE_OUT, KnnvLeftOut<TY>, KnnNobodyLeftOut>;
   constexpr uint32_t TJ = KnnShape<TY, W>::TJ;
   const uint32_t n_ct = div_up(r1, W), strips = div_up(r2, TJ);
   const uint32_t n_seg_max = std::max(1u, std::min(knn_max_segments(r2, TJ), n_ct));
   const uint32_t tiles_per_seg = div_up(n_ct, n_seg_max), n_seg = div_up(n_ct, tiles_per_seg);  // (no segment is empty)
   *n_seg_out = n_seg;
   const dim3 grid(strips, n_seg);
-  knn_nearest_kernel<KIND, TY, W><<<grid, dim3(256), 0, st>>>(a, r1, b, r2, n_dims, metric, p, k, n_ct, tiles_per_seg, w.seg_key, w.seg_idx, w.seg_n, w.seg_drop);
+  knn_nearest_kernel<KIND, TY, W, Who><<<grid, dim3(256), 0, st>>>(a, r1, b, r2, n_dims, metric, p, k, n_ct, tiles_per_seg, group_of, first_row, w.seg_key, w.seg_idx,
+                                                                   w.seg_n, w.seg_drop);
   KPOP_LAUNCH_CHECK();
-  const uint32_t rows_grid = std::min(r2, 1u << 20);
-  knn_merge_kernel<<<dim3(rows_grid), dim3(64), 0, st>>>(w.seg_key, w.seg_idx, w.seg_n, w.seg_drop, n_seg, r2, k, w.m_key, w.m_idx, w.m_n, w.m_tau, w.m_flag);
-  KPOP_LAUNCH_CHECK();
-  knn_ties_kernel<KIND, TY, W><<<grid, dim3(256), 0, st>>>(a, r1, b, r2, n_dims, metric, p, n_ct, tiles_per_seg, class_of, n_classes, w.m_tau, w.m_flag, w.tie_total,
-                                                        w.tie_count, w.tie_first);
-  KPOP_LAUNCH_CHECK();
-  return 0;
-}
-
-template <int KIND>
-static int knn_passes_of(const double *a, uint32_t r1, const double *b, uint32_t r2, uint32_t n_dims, const double *metric, double p, uint32_t k,
-                         const uint32_t *class_of, uint32_t n_classes, const KnnWork &w, uint32_t *n_seg, hipStream_t st) {
-  const uint32_t TJ = knn_strip_rows(k);
-  if (TJ == 64) return knn_passes<KIND, 4, 64>(a, r1, b, r2, n_dims, metric, p, k, class_of, n_classes, w, n_seg, st);
-  if (TJ == 32) return knn_passes<KIND, 2, 64>(a, r1, b, r2, n_dims, metric, p, k, class_of, n_classes, w, n_seg, st);
-  return knn_passes<KIND, 1, 64>(a, r1, b, r2, n_dims, metric, p, k, class_of, n_classes, w, n_seg, st);
-}
-
-// (knn_lists.h) the three passes as knn_dev launches them, and the merge alone: for knn_validate.hip
-int knn_run_passes(int kind, const double *a, uint32_t r1, const double *b, uint32_t r2, uint32_t n_dims, const double *metric, double p, uint32_t k,
-                   const uint32_t *class_of, uint32_t n_classes, const KnnWork &w, uint32_t *n_seg, hipStream_t st) {
-  switch (kind) {
-    case KPOP_EUCLIDEAN: return knn_passes_of<KPOP_EUCLIDEAN>(a, r1, b, r2, n_dims, metric, p, k, class_of, n_classes, w, n_seg, st);
-    case KPOP_COSINE: return knn_passes_of<KPOP_COSINE>(a, r1, b, r2, n_dims, metric, p, k, class_of, n_classes, w, n_seg, st);
-    default: return knn_passes_of<KPOP_MINKOWSKI>(a, r1, b, r2, n_dims, metric, p, k, class_of, n_classes, w, n_seg, st);
-  }
-}
-int knn_run_merge(const KnnWork &w, uint32_t n_seg, uint32_t r2, uint32_t k, hipStream_t st) {
   knn_merge_kernel<<<dim3(std::min(r2, 1u << 20)), dim3(64), 0, st>>>(w.seg_key, w.seg_idx, w.seg_n, w.seg_drop, n_seg, r2, k, w.m_key, w.m_idx, w.m_n, w.m_tau, w.m_flag);
   KPOP_LAUNCH_CHECK();
+  knn_ties_kernel<KIND, TY, W, Who><<<grid, dim3(256), 0, st>>>(a, r1, b, r2, n_dims, metric, p, n_ct, tiles_per_seg, group_of, first_row, class_of, n_classes, w.m_tau,
+                                                                w.m_flag, w.tie_total, w.tie_count, w.tie_first);
+  KPOP_LAUNCH_CHECK();
   return 0;
+}
+
+template <int KIND, bool LEAVE_OUT>
+static int knn_passes_of(const double *a, uint32_t r1, const double *b, uint32_t r2, uint32_t n_dims, const double *metric, double p, uint32_t k,
+                         const uint32_t *group_of, uint32_t first_row, const uint32_t *class_of, uint32_t n_classes, const KnnWork &w, uint32_t *n_seg,
+                         hipStream_t st) {
+  const uint32_t TJ = knn_strip_rows(k);
+  if (TJ == 64) return knn_passes<KIND, 4, 64, LEAVE_OUT>(a, r1, b, r2, n_dims, metric, p, k, group_of, first_row, class_of, n_classes, w, n_seg, st);
+  if (TJ == 32) return knn_passes<KIND, 2, 64, LEAVE_OUT>(a, r1, b, r2, n_dims, metric, p, k, group_of, first_row, class_of, n_classes, w, n_seg, st);
+  return knn_passes<KIND, 1, 64, LEAVE_OUT>(a, r1, b, r2, n_dims, metric, p, k, group_of, first_row, class_of, n_classes, w, n_seg, st);
+}
+
+template <bool LEAVE_OUT>
+static int knn_passes_of_kind(int kind, const double *a, uint32_t r1, const double *b, uint32_t r2, uint32_t n_dims, const double *metric, double p, uint32_t k,
+                              const uint32_t *group_of, uint32_t first_row, const uint32_t *class_of, uint32_t n_classes, const KnnWork &w, uint32_t *n_seg,
+                              hipStream_t st) {
+  switch (kind) {
+    case KPOP_EUCLIDEAN: return knn_passes_of<KPOP_EUCLIDEAN, LEAVE_OUT>(a, r1, b, r2, n_dims, metric, p, k, group_of, first_row, class_of, n_classes, w, n_seg, st);
+    case KPOP_COSINE: return knn_passes_of<KPOP_COSINE, LEAVE_OUT>(a, r1, b, r2, n_dims, metric, p, k, group_of, first_row, class_of, n_classes, w, n_seg, st);
+    default: return knn_passes_of<KPOP_MINKOWSKI, LEAVE_OUT>(a, r1, b, r2, n_dims, metric, p, k, group_of, first_row, class_of, n_classes, w, n_seg, st);
+  }
+}
+
+// (knn_lists.h) the three passes as knn_dev launches them, and with rows left out: for knn_validate.hip
+int knn_run_passes(int kind, const double *a, uint32_t r1, const double *b, uint32_t r2, uint32_t n_dims, const double *metric, double p, uint32_t k,
+                   const uint32_t *class_of, uint32_t n_classes, const KnnWork &w, uint32_t *n_seg, hipStream_t st) {
+  return knn_passes_of_kind<false>(kind, a, r1, b, r2, n_dims, metric, p, k, nullptr, 0, class_of, n_classes, w, n_seg, st);
+}
+int knn_run_leave_out_passes(int kind, const double *a, uint32_t r1, uint32_t first_row, uint32_t n_rows, uint32_t n_dims, const double *metric, double p,
+                             uint32_t k, const uint32_t *group_of, const uint32_t *class_of, uint32_t n_classes, const KnnWork &w, uint32_t *n_seg,
+                             hipStream_t st) {
+  return knn_passes_of_kind<true>(kind, a, r1, a + (uint64_t)first_row * n_dims, n_rows, n_dims, metric, p, k, group_of, first_row, class_of, n_classes, w, n_seg, st);
 }
 
 // the body of both entry points: enqueues only
@@ -499,11 +508,7 @@ static int knn_dev(kpop_refset *rs, const uint32_t *d_class_of, uint32_t n_class
       KPOP_TRY(refset_query_norms(rs, d_m2, r2, w.n2, w.b, st));
       b = w.b;
     }
-    switch (rs->kind) {
-      case KPOP_EUCLIDEAN: KPOP_TRY(knn_passes_of<KPOP_EUCLIDEAN>(a, r1, b, r2, D, rs->metric, rs->p, k, d_class_of, n_classes, w, &n_seg, st)); break;
-      case KPOP_COSINE: KPOP_TRY(knn_passes_of<KPOP_COSINE>(a, r1, b, r2, D, rs->metric, rs->p, k, d_class_of, n_classes, w, &n_seg, st)); break;
-      default: KPOP_TRY(knn_passes_of<KPOP_MINKOWSKI>(a, r1, b, r2, D, rs->metric, rs->p, k, d_class_of, n_classes, w, &n_seg, st)); break;
-    }
+    KPOP_TRY(knn_run_passes(rs->kind, a, r1, b, r2, D, rs->metric, rs->p, k, d_class_of, n_classes, w, &n_seg, st));
   }
   knn_vote_kernel<<<dim3(rows_grid), dim3(64), 0, st>>>(w.seg_key, w.seg_idx, w.seg_n, n_seg, r2, k, w.m_key, w.m_idx, w.m_n, w.m_tau, w.m_flag, d_class_of, n_classes,
                                                         w.tie_total, w.tie_count, w.tie_first, d_out_class, d_out_votes, d_out_n, d_out_first_dist);

@@ -1,15 +1,15 @@
-// knn_lists.h -- what the k-NN vote (knn.hip) and the k-NN validation (knn_validate.hip) share: the keys and their order, a row's sorted
-// list in LDS and the insertion into it, the workgroup shapes, the workspace's layout and the limits.  The kernels stay in their files,
-// each with its own copy of the tile loop; knn.hip launches its own for knn_validate.hip's many-k vote (knn_run_passes) and its merge
-// for both (knn_run_merge).
+// knn_lists.h -- what the k-NN vote (knn.hip) and the k-NN validation (knn_validate.hip) share: a row's sorted list in LDS and the
+// insertion into it, the workgroup shapes, the workspace's layout and the limits (the keys and their order: space_ops.h).  The kernels
+// that walk the pairs are knn.hip's; it launches them for knn_validate.hip too (knn_run_passes, knn_run_leave_out_passes).
 #pragma once
 #include <algorithm>
 
 #include "common.h"
+#include "space_ops.h"
 
 namespace kpop {
 
-constexpr int kKDC = 16, kKMaxK = 128;
+constexpr int kKMaxK = 128;
 // a workgroup's shape: W columns (rows of the set) x TJ query rows, a thread 4 columns x TY rows
 template <int TY, int W>
 struct KnnShape {
@@ -19,18 +19,9 @@ struct KnnShape {
 constexpr int kKMaxSeg = 128, kKBlocks = 512;                // segments a strip at most; workgroups a launch aims at (two a CU)
 constexpr int kKMaxTies = 1024;                              // listed ties of a row that knn_vote_kernel takes from the lists; more: the tables
 constexpr int kKVoteList = kKMaxK + kKMaxTies;               // knn_vote_kernel: < k entries below tau, then the listed ties
-constexpr uint64_t kKNone = ~0ull;                           // (no key: knn_key maps only a NaN's bits there, and a NaN is never a key)
+constexpr uint64_t kKNone = ~0ull;                           // (no key: distance_key maps only a NaN's bits there, and a NaN is never a key)
 constexpr uint32_t kKMaxClasses = 65535;
 constexpr uint32_t kKMaxKs = 32;                             // the cut points of one list (knn_validate.hip)
-
-// a distance that is a number -> a key that orders as the distance does; -0 is taken as +0 (forest.hip's dist_key)
-__device__ __forceinline__ uint64_t knn_key(double d) {
-  if (d == 0.0) d = 0.0;
-  const uint64_t b = (uint64_t)__double_as_longlong(d);
-  return (b >> 63) ? ~b : (b | (1ull << 63));
-}
-__device__ __forceinline__ double knn_key_dist(uint64_t k) { return __longlong_as_double((long long)((k >> 63) ? (k & ~(1ull << 63)) : ~k)); }
-__device__ __forceinline__ bool knn_less(uint64_t ka, uint32_t ia, uint64_t kb, uint32_t ib) { return ka < kb || (ka == kb && ia < ib); }
 
 // One candidate into a row's sorted list, by the whole wavefront that owns the row (every argument is the same in all 64 lanes).
 // lk, li: the row's k slots; *np its length; *bp, *bip its bound (kKNone until the list is full, then its k-th key and index); *dp its
@@ -53,7 +44,7 @@ __device__ __forceinline__ void knn_insert(volatile uint64_t *lk, volatile uint3
   const uint32_t q0 = lane, q1 = lane + 64;
   const uint64_t e0k = q0 < n ? lk[q0] : 0, e1k = q1 < n ? lk[q1] : 0;
   const uint32_t e0i = q0 < n ? li[q0] : 0, e1i = q1 < n ? li[q1] : 0;
-  const uint32_t pos = (uint32_t)__popcll(__ballot(q0 < n && knn_less(e0k, e0i, ck, ci))) + (uint32_t)__popcll(__ballot(q1 < n && knn_less(e1k, e1i, ck, ci)));
+  const uint32_t pos = (uint32_t)__popcll(__ballot(q0 < n && key_less(e0k, e0i, ck, ci))) + (uint32_t)__popcll(__ballot(q1 < n && key_less(e1k, e1i, ck, ci)));
   // (pos <= n, and pos < k: a full list was entered only below its last entry)
   if (q0 < n && q0 >= pos && q0 + 1 < k) {
     lk[q0 + 1] = e0k;
@@ -100,7 +91,7 @@ struct KnnBest {
   uint64_t key;
 };
 __device__ __forceinline__ bool knn_better(const KnnBest &x, const KnnBest &y) {  // more members; among equally many, the nearer first member
-  return x.cnt > y.cnt || (x.cnt == y.cnt && x.cnt > 0 && knn_less(x.key, x.idx, y.key, y.idx));
+  return x.cnt > y.cnt || (x.cnt == y.cnt && x.cnt > 0 && key_less(x.key, x.idx, y.key, y.idx));
 }
 
 // the workspace, carved: the query rows' norms and divided copy, the segments' lists, the merged lists, the tie tables.  It depends on
@@ -160,10 +151,13 @@ static int knn_check_sizes(uint32_t k, uint32_t n_classes, const char *who) {
   return 0;
 }
 
-// knn.hip: its own three passes over the pairs -- knn_nearest_kernel, knn_merge_kernel, knn_ties_kernel -- for the set's kind, and the
-// merge alone over segments' lists that another nearest pass wrote (knn_validate.hip).  Both enqueue only
+// knn.hip: the three passes over the pairs -- knn_nearest_kernel, knn_merge_kernel, knn_ties_kernel -- for the set's kind.  The second
+// form takes rows first_row .. first_row + n_rows of the set a itself as the query rows and leaves out of each row's list the row
+// (group_of == NULL) or its whole group (knn_validate.hip).  Both enqueue only
 int knn_run_passes(int kind, const double *a, uint32_t r1, const double *b, uint32_t r2, uint32_t n_dims, const double *metric, double p, uint32_t k,
                    const uint32_t *class_of, uint32_t n_classes, const KnnWork &w, uint32_t *n_seg, hipStream_t st);
-int knn_run_merge(const KnnWork &w, uint32_t n_seg, uint32_t r2, uint32_t k, hipStream_t st);
+int knn_run_leave_out_passes(int kind, const double *a, uint32_t r1, uint32_t first_row, uint32_t n_rows, uint32_t n_dims, const double *metric, double p,
+                             uint32_t k, const uint32_t *group_of, const uint32_t *class_of, uint32_t n_classes, const KnnWork &w, uint32_t *n_seg,
+                             hipStream_t st);
 
 }  // namespace kpop

@@ -12,13 +12,9 @@
 //   class at ks[t] is their own.  No setting is read; every step is a function of the distances, classes and groups alone.
 //
 // The launches of a validation, always the same (the device form reads nothing back):
-//   knnv_nearest_kernel  knn_nearest_kernel's shape (KnnShape, the lists in LDS, knn_insert, the dropped ties, the column segments) with
-//                        its own copy of the tile loop, so that knn.hip's kernels stay the kernels they were.  The epilogue refuses an
-//                        excluded column before it can be inserted OR counted as a dropped tie: a row whose own index ties with its
-//                        k-th key would otherwise flag itself.  The groups of the tile's four columns are loaded once a tile, those of
-//                        the thread's rows once a launch.
-//   knn_merge_kernel     knn.hip's, as it is, with k = K (knn_run_merge).
-//   knnv_ties_kernel     knn_ties_kernel's shape with the same refusal.
+//   knn_nearest_kernel   knn.hip's three passes over the pairs with KnnvLeftOut for "who is left out" (knn_run_leave_out_passes): a
+//   knn_merge_kernel     column that is left out is refused before it can be inserted or counted as a dropped tie, and in the tie
+//   knn_ties_kernel      tables.  The groups of a tile's four columns are loaded once a tile, those of a thread's rows once a launch.
 //   knn_vote_ks_kernel   per row, the merged list read at every cut (below).  Also the vote of kpop_knn_ks_vote, whose three passes
 //                        are knn.hip's own (knn_run_passes).
 //   knn_correct_kernel   integers summed: any order gives the same bits.
@@ -37,236 +33,6 @@ struct KnnKs {
   uint32_t n;
   uint32_t k[kKMaxKs];
 };
-
-// The tile loop: knn_tiles (knn.hip), operation for operation; the query rows are rows of `a` too, from row jbase on.  The workgroup's
-// rows j0 .. j1 of the range (at most TJ), its column tiles t_begin .. t_end of W rows of the set each.  A thread 4 columns x TY rows, the
-// dimensions ascending in one thread, 16 at a time through LDS; the next step's operands are loaded under the arithmetic.
-// epi(i0, i1, acc): what to do with a tile's finished sums.
-template <int KIND, int TY, int W, class Epi>
-__device__ __forceinline__ void knnv_tiles(const double *__restrict__ a, uint32_t r1, uint32_t jbase, uint32_t j0, uint32_t j1, uint32_t n_dims,
-                                           const double *__restrict__ metric, double p, uint32_t t_begin, uint32_t t_end, double (*As)[W + 2],
-                                           double (*Bs)[KnnShape<TY, W>::TJ + 2], double *s_metric, Epi &&epi) {
-  using S = KnnShape<TY, W>;
-  constexpr uint32_t TJ = S::TJ;
-  const uint32_t cg = threadIdx.x % S::NCG, rg = threadIdx.x / S::NCG;
-  const uint32_t ti = cg * 4, tj = rg * TY;
-  constexpr int NA = W * kKDC / 256, NB = TJ * kKDC / 256;
-  double ra[NA], rb[NB];
-  const uint32_t sc = threadIdx.x % kKDC, rbase = threadIdx.x / kKDC;
-  const double *b = a + (uint64_t)jbase * n_dims;
-  auto prefetch = [&](uint32_t i0, uint32_t c0) {
-    const uint32_t i1 = min(r1, i0 + W);
-    const bool cok = c0 + sc < n_dims;
-#pragma unroll
-    for (int q = 0; q < NA; ++q) {
-      const uint32_t row = rbase + q * 16;
-      ra[q] = (cok && i0 + row < i1) ? a[(uint64_t)(i0 + row) * n_dims + c0 + sc] : 0.0;
-    }
-#pragma unroll
-    for (int q = 0; q < NB; ++q) {
-      const uint32_t row = rbase + q * 16;
-      rb[q] = (cok && j0 + row < j1) ? b[(uint64_t)(j0 + row) * n_dims + c0 + sc] : 0.0;
-    }
-  };
-  if (t_begin < t_end) prefetch(t_begin * W, 0);
-  for (uint32_t t = t_begin; t < t_end; ++t) {
-    const uint32_t i0 = t * W, i1 = min(r1, i0 + W);
-    double acc[TY][4];
-#pragma unroll
-    for (int yy = 0; yy < TY; ++yy)
-#pragma unroll
-      for (int x = 0; x < 4; ++x) acc[yy][x] = 0.0;
-    for (uint32_t c0 = 0; c0 < n_dims; c0 += kKDC) {
-      __syncthreads();
-#pragma unroll
-      for (int q = 0; q < NA; ++q) As[sc][rbase + q * 16] = ra[q];
-#pragma unroll
-      for (int q = 0; q < NB; ++q) Bs[sc][rbase + q * 16] = rb[q];
-      if (threadIdx.x < kKDC) s_metric[threadIdx.x] = (c0 + threadIdx.x < n_dims) ? metric[c0 + threadIdx.x] : 0.0;
-      __syncthreads();
-      if (c0 + kKDC < n_dims) prefetch(i0, c0 + kKDC);
-      else if (t + 1 < t_end) prefetch((t + 1) * W, 0);
-      const uint32_t lim = min((uint32_t)kKDC, n_dims - c0);
-      for (uint32_t cc = 0; cc < lim; ++cc) {
-        double av[4], bv[TY];
-#pragma unroll
-        for (int x = 0; x < 4; ++x) av[x] = As[cc][ti + x];
-#pragma unroll
-        for (int yy = 0; yy < TY; ++yy) bv[yy] = Bs[cc][tj + yy];
-        const double mc = s_metric[cc];
-#pragma unroll
-        for (int yy = 0; yy < TY; ++yy)
-#pragma unroll
-          for (int x = 0; x < 4; ++x) {
-            // lib/Space.ml:192-200: diff = a -. b ; acc +. (diff *. diff *. m)
-            double diff = __dsub_rn(av[x], bv[yy]);
-            acc[yy][x] = __dadd_rn(acc[yy][x], component<KIND>(diff, mc, p));
-          }
-      }
-    }
-    epi(i0, i1, acc);
-  }
-}
-
-// What a thread knows of who is left out: its rows' groups (or their indices in the set) for the launch, the tile's four columns' groups
-// for the tile.  left_out(yy, x, i): column i, the thread's x-th, is not a neighbour of its yy-th row
-template <int TY>
-struct KnnvLeftOut {
-  const uint32_t *group_of;
-  uint32_t own[TY], col[4];  // group_of set: groups; not set: own[] the rows' indices in the set
-  __device__ __forceinline__ void rows(const uint32_t *g, uint32_t jfirst, uint32_t r1) {
-    group_of = g;
-#pragma unroll
-    for (int yy = 0; yy < TY; ++yy) own[yy] = (g && jfirst + yy < r1) ? g[jfirst + yy] : jfirst + yy;
-  }
-  __device__ __forceinline__ void columns(uint32_t ifirst, uint32_t i1) {
-    if (!group_of) return;
-#pragma unroll
-    for (int x = 0; x < 4; ++x) col[x] = ifirst + x < i1 ? group_of[ifirst + x] : 0u;
-  }
-  __device__ __forceinline__ bool left_out(int yy, int x, uint32_t i) const { return group_of ? col[x] == own[yy] : i == own[yy]; }
-};
-
-// Strip blockIdx.x: rows first_row + j0 .. + TJ of the set as query rows; segment blockIdx.y.  seg_key, seg_idx: [segment][n_rows][k],
-// the list's first seg_n entries ascending; seg_drop: the dropped ties of the list's last key.  TJ k <= SLOTS (the launch sees to it).
-template <int KIND, int TY, int W>
-__global__ __launch_bounds__(256, 1) void knnv_nearest_kernel(const double *__restrict__ a, uint32_t r1, uint32_t first_row, uint32_t n_rows, uint32_t n_dims,
-                                                              const double *__restrict__ metric, double p, uint32_t k, uint32_t n_ct, uint32_t tiles_per_seg,
-                                                              const uint32_t *__restrict__ group_of, uint64_t *__restrict__ seg_key,
-                                                              uint32_t *__restrict__ seg_idx, uint32_t *__restrict__ seg_n, uint32_t *__restrict__ seg_drop) {
-  using S = KnnShape<TY, W>;
-  constexpr uint32_t TJ = S::TJ;
-  __shared__ __attribute__((aligned(16))) double As[kKDC][W + 2];
-  __shared__ __attribute__((aligned(16))) double Bs[kKDC][TJ + 2];
-  __shared__ double s_metric[kKDC];
-  __shared__ uint64_t s_key[S::SLOTS];
-  __shared__ uint32_t s_idx[S::SLOTS];
-  __shared__ uint64_t s_bound[TJ];
-  __shared__ uint32_t s_n[TJ], s_drop[TJ], s_bidx[TJ];
-  const uint32_t j0 = blockIdx.x * TJ, j1 = min(n_rows, j0 + TJ);  // (the grid has div_up(n_rows, TJ) strips: j0 < n_rows)
-  uint32_t t_begin, t_end;
-  knn_segment(n_ct, tiles_per_seg, &t_begin, &t_end);
-  if (threadIdx.x < TJ) {
-    s_bound[threadIdx.x] = kKNone;
-    s_bidx[threadIdx.x] = 0;
-    s_n[threadIdx.x] = 0;
-    s_drop[threadIdx.x] = 0;
-  }
-  __syncthreads();
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t ti = (threadIdx.x % S::NCG) * 4, tj = (threadIdx.x / S::NCG) * TY;  // (the rows of a wavefront: TJ / 4 in a row, nobody else's)
-  KnnvLeftOut<TY> out;
-  out.rows(group_of, first_row + j0 + tj, r1);
-  knnv_tiles<KIND, TY, W>(a, r1, first_row, j0, j1, n_dims, metric, p, t_begin, t_end, As, Bs, s_metric, [&](uint32_t i0, uint32_t i1, double(&acc)[TY][4]) {
-    out.columns(i0 + ti, i1);
-    // the rows' bounds as the step before left them (a row is this wavefront's alone): read again after every step that inserted
-    uint64_t bound[TY];
-    uint32_t bidx[TY];
-    auto bounds = [&]() {
-#pragma unroll
-      for (int yy = 0; yy < TY; ++yy) {
-        bound[yy] = *(volatile uint64_t *)&s_bound[tj + yy];
-        bidx[yy] = *(volatile uint32_t *)&s_bidx[tj + yy];
-      }
-    };
-    bounds();
-#pragma unroll
-    for (int yy = 0; yy < TY; ++yy) {
-      const uint32_t row = tj + yy;
-#pragma unroll
-      for (int x = 0; x < 4; ++x) {
-        const double d = scale_distance<KIND>(acc[yy][x], p);
-        const uint32_t i = i0 + ti + x;
-        const uint64_t key = knn_key(d);
-        // a NaN is never a neighbour, and neither is a column that is left out: refused here, in front of the count of dropped ties
-        const bool number = j0 + row < j1 && i < i1 && d == d && !out.left_out(yy, x, i);
-        // a tie of the k-th key behind the k-th entry is dropped and counted where it stands: a sum, whatever the order.  These
-        // come first, the entries that go into the list after them: one of the orders of arrival, all of which give the same
-        if (number && key == bound[yy] && i > bidx[yy]) atomicAdd(&s_drop[row], 1u);
-        __builtin_amdgcn_wave_barrier();
-        const bool c = number && (key < bound[yy] || (key == bound[yy] && i < bidx[yy]));
-        uint64_t m = __ballot(c);
-        const bool inserted = m != 0;
-        while (m) {  // (the same in every lane)
-          const int src = __ffsll((unsigned long long)m) - 1;
-          m &= m - 1;
-          const uint64_t ck = (uint64_t)__shfl((unsigned long long)key, src, 64);
-          const uint32_t ci = (uint32_t)__shfl((int)i, src, 64);
-          const uint32_t cr = (uint32_t)__shfl((int)row, src, 64);
-          knn_insert(s_key + cr * k, s_idx + cr * k, s_n + cr, s_bound + cr, s_bidx + cr, s_drop + cr, k, ck, ci, lane);
-        }
-        if (inserted) bounds();
-      }
-    }
-  });
-  __syncthreads();
-  const uint32_t seg = blockIdx.y;
-  for (uint32_t e = threadIdx.x; e < TJ * k; e += 256) {
-    const uint32_t row = e / k, q = e % k;
-    if (j0 + row < j1) {
-      const uint64_t o = ((uint64_t)seg * n_rows + j0 + row) * k + q;
-      const bool in = q < s_n[row];
-      seg_key[o] = in ? s_key[e] : kKNone;
-      seg_idx[o] = in ? s_idx[e] : 0u;
-    }
-  }
-  if (threadIdx.x < TJ && j0 + threadIdx.x < j1) {
-    seg_n[(uint64_t)seg * n_rows + j0 + threadIdx.x] = s_n[threadIdx.x];
-    seg_drop[(uint64_t)seg * n_rows + j0 + threadIdx.x] = s_drop[threadIdx.x];
-  }
-}
-
-// the grid of knnv_nearest_kernel.  tie_total: [n_rows], every column of a flagged row at tau that is not left out; tie_count,
-// tie_first: [n_rows][n_classes], those of a class and the least index among them (0xFFFFFFFF: none).  class_of is trusted, every table
-// access guarded
-template <int KIND, int TY, int W>
-__global__ __launch_bounds__(256, 1) void knnv_ties_kernel(const double *__restrict__ a, uint32_t r1, uint32_t first_row, uint32_t n_rows, uint32_t n_dims,
-                                                           const double *__restrict__ metric, double p, uint32_t n_ct, uint32_t tiles_per_seg,
-                                                           const uint32_t *__restrict__ group_of, const uint32_t *__restrict__ class_of, uint32_t n_classes,
-                                                           const uint64_t *__restrict__ m_tau, const uint32_t *__restrict__ m_flag, uint32_t *tie_total,
-                                                           uint32_t *tie_count, uint32_t *tie_first) {
-  using S = KnnShape<TY, W>;
-  constexpr uint32_t TJ = S::TJ;
-  __shared__ __attribute__((aligned(16))) double As[kKDC][W + 2];
-  __shared__ __attribute__((aligned(16))) double Bs[kKDC][TJ + 2];
-  __shared__ double s_metric[kKDC];
-  const uint32_t j0 = blockIdx.x * TJ, j1 = min(n_rows, j0 + TJ);
-  if (!__syncthreads_or(threadIdx.x < TJ && j0 + threadIdx.x < j1 && m_flag[j0 + threadIdx.x] != 0)) return;  // (nearly every workgroup)
-  uint32_t t_begin, t_end;
-  knn_segment(n_ct, tiles_per_seg, &t_begin, &t_end);
-  const uint32_t ti = (threadIdx.x % S::NCG) * 4, tj = (threadIdx.x / S::NCG) * TY;
-  uint64_t tau[TY];
-  bool fl[TY];
-#pragma unroll
-  for (int yy = 0; yy < TY; ++yy) {
-    const uint32_t j = j0 + tj + yy;
-    fl[yy] = j < j1 && m_flag[j] != 0;
-    tau[yy] = fl[yy] ? m_tau[j] : kKNone;
-  }
-  KnnvLeftOut<TY> out;
-  out.rows(group_of, first_row + j0 + tj, r1);
-  knnv_tiles<KIND, TY, W>(a, r1, first_row, j0, j1, n_dims, metric, p, t_begin, t_end, As, Bs, s_metric, [&](uint32_t i0, uint32_t i1, double(&acc)[TY][4]) {
-    out.columns(i0 + ti, i1);
-#pragma unroll
-    for (int yy = 0; yy < TY; ++yy) {
-      if (!fl[yy]) continue;
-      const uint32_t j = j0 + tj + yy;
-#pragma unroll
-      for (int x = 0; x < 4; ++x) {
-        const double d = scale_distance<KIND>(acc[yy][x], p);
-        const uint32_t i = i0 + ti + x;
-        if (i < i1 && d == d && !out.left_out(yy, x, i) && knn_key(d) == tau[yy]) {
-          atomicAdd(tie_total + j, 1u);
-          const uint32_t c = class_of[i];
-          if (c < n_classes) {
-            atomicAdd(tie_count + (uint64_t)j * n_classes + c, 1u);
-            atomicMin(tie_first + (uint64_t)j * n_classes + c, i);
-          }
-        }
-      }
-    }
-  });
-}
 
 // One list, many cuts: a block of 64 (one wavefront) a row.  The merged list holds the row's K nearest (fewer: everything), ascending by
 // (key, index); tau_K is its last key.  For cut t, tau_t is the min(ks[t], n)-th key of the merged list, and the list at k = ks[t] is the
@@ -312,7 +78,7 @@ __global__ __launch_bounds__(64) void knn_vote_ks_kernel(const uint64_t *__restr
         out_class[o] = best.cnt ? best.cls : KPOP_NO_CLASS;
         out_votes[o] = best.cnt;
         out_n[o] = n_list;
-        if (out_first_dist) out_first_dist[o] = best.cnt ? knn_key_dist(best.key) : nan;
+        if (out_first_dist) out_first_dist[o] = best.cnt ? key_f64(best.key) : nan;
       }
     };
     const uint32_t nm = m_n[row];
@@ -520,34 +286,6 @@ static int vote_ks_dev(kpop_refset *rs, const uint32_t *d_class_of, uint32_t n_c
   return KPOP_OK;
 }
 
-template <int KIND, int TY, int W>
-static int knnv_passes(const double *a, uint32_t r1, uint32_t first_row, uint32_t n_rows, uint32_t n_dims, const double *metric, double p, uint32_t k,
-                       const uint32_t *group_of, const uint32_t *class_of, uint32_t n_classes, const KnnWork &w, uint32_t *n_seg_out, hipStream_t st) {
-  constexpr uint32_t TJ = KnnShape<TY, W>::TJ;
-  const uint32_t n_ct = div_up(r1, W), strips = div_up(n_rows, TJ);
-  const uint32_t n_seg_max = std::max(1u, std::min(knn_max_segments(n_rows, TJ), n_ct));
-  const uint32_t tiles_per_seg = div_up(n_ct, n_seg_max), n_seg = div_up(n_ct, tiles_per_seg);  // (no segment is empty)
-  *n_seg_out = n_seg;
-  const dim3 grid(strips, n_seg);
-  knnv_nearest_kernel<KIND, TY, W><<<grid, dim3(256), 0, st>>>(a, r1, first_row, n_rows, n_dims, metric, p, k, n_ct, tiles_per_seg, group_of, w.seg_key, w.seg_idx,
-                                                            w.seg_n, w.seg_drop);
-  KPOP_LAUNCH_CHECK();
-  KPOP_TRY(knn_run_merge(w, n_seg, n_rows, k, st));
-  knnv_ties_kernel<KIND, TY, W><<<grid, dim3(256), 0, st>>>(a, r1, first_row, n_rows, n_dims, metric, p, n_ct, tiles_per_seg, group_of, class_of, n_classes, w.m_tau,
-                                                         w.m_flag, w.tie_total, w.tie_count, w.tie_first);
-  KPOP_LAUNCH_CHECK();
-  return 0;
-}
-
-template <int KIND>
-static int knnv_passes_of(const double *a, uint32_t r1, uint32_t first_row, uint32_t n_rows, uint32_t n_dims, const double *metric, double p, uint32_t k,
-                          const uint32_t *group_of, const uint32_t *class_of, uint32_t n_classes, const KnnWork &w, uint32_t *n_seg, hipStream_t st) {
-  const uint32_t TJ = knn_strip_rows(k);
-  if (TJ == 64) return knnv_passes<KIND, 4, 64>(a, r1, first_row, n_rows, n_dims, metric, p, k, group_of, class_of, n_classes, w, n_seg, st);
-  if (TJ == 32) return knnv_passes<KIND, 2, 64>(a, r1, first_row, n_rows, n_dims, metric, p, k, group_of, class_of, n_classes, w, n_seg, st);
-  return knnv_passes<KIND, 1, 64>(a, r1, first_row, n_rows, n_dims, metric, p, k, group_of, class_of, n_classes, w, n_seg, st);
-}
-
 // the body of the validation's entry points: enqueues only.  The workspace is the vote's without a query side
 static int validate_dev(kpop_refset *rs, const uint32_t *d_class_of, uint32_t n_classes, const uint32_t *d_group_of, uint32_t first_row, uint32_t n_rows,
                         const uint32_t *ks_host, uint32_t n_ks, void *d_work, uint32_t *d_out_class, uint32_t *d_out_votes, uint32_t *d_out_n,
@@ -573,13 +311,7 @@ static int validate_dev(kpop_refset *rs, const uint32_t *d_class_of, uint32_t n_
     KPOP_TRY(rs->divided(st, &a));
   }
   uint32_t n_seg = 0;
-  switch (rs->kind) {
-    case KPOP_EUCLIDEAN:
-      KPOP_TRY(knnv_passes_of<KPOP_EUCLIDEAN>(a, r1, first_row, n_rows, D, rs->metric, rs->p, K, d_group_of, d_class_of, n_classes, w, &n_seg, st));
-      break;
-    case KPOP_COSINE: KPOP_TRY(knnv_passes_of<KPOP_COSINE>(a, r1, first_row, n_rows, D, rs->metric, rs->p, K, d_group_of, d_class_of, n_classes, w, &n_seg, st)); break;
-    default: KPOP_TRY(knnv_passes_of<KPOP_MINKOWSKI>(a, r1, first_row, n_rows, D, rs->metric, rs->p, K, d_group_of, d_class_of, n_classes, w, &n_seg, st)); break;
-  }
+  KPOP_TRY(knn_run_leave_out_passes(rs->kind, a, r1, first_row, n_rows, D, rs->metric, rs->p, K, d_group_of, d_class_of, n_classes, w, &n_seg, st));
   knn_vote_ks_launch(w, n_seg, n_rows, K, d_class_of, n_classes, ks, d_out_class, d_out_votes, d_out_n, d_out_first_dist, st);
   KPOP_LAUNCH_CHECK();
   knn_correct_kernel<<<dim3(n_ks), dim3(1024), 0, st>>>(d_out_class, d_class_of, first_row, n_rows, reinterpret_cast<unsigned long long *>(d_out_correct));

@@ -25,14 +25,7 @@ namespace kpop {
 constexpr int kLT = 1024;             // threads per row
 constexpr uint32_t kLargeMaxNb = 2048;  // neighbours returned per row at most (= kLargeNeighbours, distance.hip)
 
-__device__ __forceinline__ uint64_t f64_key(double x) {  // order-preserving map to u64
-  const uint64_t b = (uint64_t)__double_as_longlong(x);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double key_f64(uint64_t k) {
-  const uint64_t b = (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
-  return __longlong_as_double((long long)b);
-}
+// (f64_key, key_f64: the order-preserving map of a double to a u64 and back, space_ops.h)
 
 // sum over the block, same value in every thread; fixed order => bitwise reproducible
 __device__ double block_sum(double v, double *s_w) {

@@ -7,7 +7,7 @@
 //   distance_rowwise_kernel (distance.hip), whatever kpop_tune says -- no setting is read here.
 //
 // The r2 x r1 matrix is never formed.  Five steps, each its own launch (no inter-workgroup hand-off inside a launch):
-//   within_tile_kernel     the arithmetic of distance_rowwise_kernel, operation for operation; its epilogue compares where that
+//   within_tile_kernel     the arithmetic of distance_rowwise_kernel, operation for operation (pair_tile.h); its epilogue compares where that
 //                          one stores.  A row's hits are counted through LDS, then with ONE global add per row and block (sums:
 //                          the counts do not depend on the order); the adds' old values give every hit a slot of its own inside
 //                          its row.  The hits of a wavefront go to a pool of `capacity` entries (distance, index, row, slot) at a
@@ -26,12 +26,13 @@
 
 #include "common.h"
 #include "distance_routes.h"
+#include "pair_tile.h"
 #include "scan.h"
 #include "space_ops.h"
 
 namespace kpop {
 
-constexpr int kWDC = 16, kWMaxW = 128, kWMaxTJ = 256;
+constexpr int kWMaxW = 128, kWMaxTJ = 256;
 constexpr uint32_t kWithinChunk = 4096;
 
 // a, b: the operands as the chain reads them (divided by their rows' norms when the set normalises).  Tiles as
@@ -43,67 +44,27 @@ __global__ __launch_bounds__(256, 1) void within_tile_kernel(const double *__res
                                                              uint32_t n_cg, uint32_t n_rg, uint32_t jbase, unsigned long long *__restrict__ counts,
                                                              uint64_t capacity, unsigned long long *__restrict__ cursor, double *__restrict__ pool_d,
                                                              uint32_t *__restrict__ pool_i, uint32_t *__restrict__ pool_r, uint32_t *__restrict__ pool_k) {
-  __shared__ __attribute__((aligned(16))) double As[kWDC][kWMaxW + 2];
-  __shared__ __attribute__((aligned(16))) double Bs[kWDC][kWMaxTJ + 2];
-  __shared__ double s_metric[kWDC];
+  __shared__ __attribute__((aligned(16))) double As[kPairDC][kWMaxW + 2];
+  __shared__ __attribute__((aligned(16))) double Bs[kPairDC][kWMaxTJ + 2];
+  __shared__ double s_metric[kPairDC];
   __shared__ uint32_t s_cnt[kWMaxTJ];
   const uint32_t TJ = TY * n_rg;
   const uint32_t i0 = blockIdx.x * w, j0 = blockIdx.y * TJ;
-  const uint32_t i1 = min(r1, i0 + w);
+  const uint32_t i1 = min(r1, i0 + w), j1 = min(r2, j0 + TJ);
   const uint32_t cg = threadIdx.x % n_cg, rg = threadIdx.x / n_cg;
   const bool worker = rg < n_rg;
   const uint32_t ti = cg * 4, tj = (worker ? rg : 0) * TY;
   s_cnt[threadIdx.x] = 0;  // (kWMaxTJ == blockDim.x; the loop's barriers come before anybody adds)
   double acc[TY][4];
-#pragma unroll
-  for (int y = 0; y < TY; ++y)
-#pragma unroll
-    for (int x = 0; x < 4; ++x) acc[y][x] = 0.0;
-  constexpr int NA = kWMaxW * kWDC / 256, NB = kWMaxTJ * kWDC / 256;
-  double ra[NA], rb[NB];
-  const uint32_t sc = threadIdx.x % kWDC, rbase = threadIdx.x / kWDC;
-  auto prefetch = [&](uint32_t c0) {
-    const bool cok = c0 + sc < n_dims;
-#pragma unroll
-    for (int q = 0; q < NA; ++q) {
-      const uint32_t row = rbase + q * 16;
-      ra[q] = (cok && row < w && i0 + row < i1) ? a[(uint64_t)(i0 + row) * n_dims + c0 + sc] : 0.0;
-    }
-#pragma unroll
-    for (int q = 0; q < NB; ++q) {
-      const uint32_t row = rbase + q * 16;
-      rb[q] = (cok && row < TJ && j0 + row < r2) ? b[(uint64_t)(j0 + row) * n_dims + c0 + sc] : 0.0;
-    }
-  };
-  prefetch(0);
-  for (uint32_t c0 = 0; c0 < n_dims; c0 += kWDC) {
+  pair_zero(acc);
+  PairStage<kWMaxW, kWMaxTJ> stage;
+  stage.load(a, i0, i1, b, j0, j1, n_dims, 0, n_dims);
+  for (uint32_t c0 = 0; c0 < n_dims; c0 += kPairDC) {
     __syncthreads();
-#pragma unroll
-    for (int q = 0; q < NA; ++q) As[sc][rbase + q * 16] = ra[q];
-#pragma unroll
-    for (int q = 0; q < NB; ++q) Bs[sc][rbase + q * 16] = rb[q];
-    if (threadIdx.x < kWDC) s_metric[threadIdx.x] = (c0 + threadIdx.x < n_dims) ? metric[c0 + threadIdx.x] : 0.0;
+    stage.store(As, Bs, s_metric, metric, c0, n_dims);
     __syncthreads();
-    if (c0 + kWDC < n_dims) prefetch(c0 + kWDC);
-    const uint32_t lim = min((uint32_t)kWDC, n_dims - c0);
-    if (worker) {
-      for (uint32_t cc = 0; cc < lim; ++cc) {
-        double av[4], bv[TY];
-#pragma unroll
-        for (int x = 0; x < 4; ++x) av[x] = As[cc][ti + x];
-#pragma unroll
-        for (int y = 0; y < TY; ++y) bv[y] = Bs[cc][tj + y];
-        const double mc = s_metric[cc];
-#pragma unroll
-        for (int y = 0; y < TY; ++y)
-#pragma unroll
-          for (int x = 0; x < 4; ++x) {
-            // lib/Space.ml:192-200: diff = a -. b ; acc +. (diff *. diff *. m)
-            double diff = __dsub_rn(av[x], bv[y]);
-            acc[y][x] = __dadd_rn(acc[y][x], component<KIND>(diff, mc, p));
-          }
-      }
-    }
+    if (c0 + kPairDC < n_dims) stage.load(a, i0, i1, b, j0, j1, n_dims, c0 + kPairDC, n_dims);
+    if (worker) pair_accumulate<KIND>(acc, As, Bs, s_metric, ti, tj, min((uint32_t)kPairDC, n_dims - c0), p);
   }
   // the epilogue: compare where distance_rowwise_kernel stores (a NaN compares false: never a hit)
   uint32_t mask = 0;

@@ -113,14 +113,20 @@ def test_the_kernels_are_built_from_their_own_file():
     csrc = os.path.join(ROOT, "kpop_amd", "csrc")
     assert "knn_validate.hip" in open(os.path.join(csrc, "Makefile")).read()
     src = open(os.path.join(csrc, "knn_validate.hip")).read()
-    for kernel in ("knnv_nearest_kernel", "knnv_ties_kernel", "knn_vote_ks_kernel", "knn_correct_kernel"):
+    for kernel in ("knn_vote_ks_kernel", "knn_correct_kernel"):
         assert "void " + kernel in src
     assert "asm" not in re.sub(r"//.*", "", src)  # plain HIP C++ throughout
-    # the vote's four kernels stay in knn.hip, and the merge is launched from there alone
+    # the kernels that walk the pairs, the merge and the vote stay in knn.hip, one body each for the vote and the leave-out votes
+    # (a "who is left out" policy), and are launched from there alone
     vote = open(os.path.join(csrc, "knn.hip")).read()
     for kernel in ("knn_nearest_kernel", "knn_merge_kernel", "knn_ties_kernel", "knn_vote_kernel"):
-        assert "void " + kernel in vote and "void " + kernel not in src
-    assert "knn_run_merge(" in src and "knn_merge_kernel<<<" not in src
+        assert vote.count("void " + kernel + "(") == 1 and "void " + kernel not in src
+        assert kernel + "<" not in src  # neither launched nor instantiated in this translation unit
+    assert "KnnvLeftOut" in vote and "KnnNobodyLeftOut" in vote
+    assert "knn_run_leave_out_passes(" in src and "knn_run_passes(" in src
+    # one tile loop: the reference chain's line stands in pair_tile.h and in neither k-NN file
+    assert "__dsub_rn(av[" not in src and "__dsub_rn(av[" not in vote and '#include "pair_tile.h"' in vote
+    assert "__dsub_rn(av[" in open(os.path.join(csrc, "pair_tile.h")).read()
 
 
 @pytest.mark.skipif(os.path.exists("/dev/kfd"), reason="a GPU is present")
