@@ -830,6 +830,42 @@ int kpop_distance_knn_validate(const double *m, uint32_t rows, uint32_t n_dims, 
                                const uint32_t *ks, uint32_t n_ks, uint32_t *out_class, uint32_t *out_votes,
                                uint32_t *out_n, double *out_first_dist, uint64_t *out_correct);
 
+/* ------------------------------------------------- representatives at a distance (the greedy cover of a resident set)
+ * Thinning (dereplication, leader clustering): keep one row per neighbourhood of radius max_distance, in row order, and
+ * say which kept row stands for each dropped one.  d(j, i) is the reference chain's distance (lib/Space.ml:182-205 with
+ * the adaptors of lib/Matrix.ml:243-250) -- the bits kpop_refset_distance_rowwise writes under
+ * kpop_tune("distance_mfma", 0) when the set's own rows are the query -- whatever kpop_tune says; symmetric bit for bit;
+ * a NaN distance is within nothing.  Row i is a REPRESENTATIVE iff no representative r < i has d(i, r) <= max_distance
+ * (row 0 always is): the lexicographically first maximal independent set of kpop_clusters_within's graph.  For a
+ * representative rep_of[i] = i and rep_dist[i] = +0; otherwise rep_of[i] is the representative r < i within max_distance
+ * that is least under (d with -0 taken as +0, r) -- the nearest EARLIER one, ties to the smaller index, even when a later
+ * representative is nearer -- and rep_dist[i] that distance, a zero written as +0.  rep_of[i] <= i,
+ * rep_of[rep_of[i]] == rep_of[i], *n_reps the number of i with rep_of[i] == i; two representatives lie farther apart
+ * than max_distance (or at a NaN), every other row within it of its own: these properties determine the result, the
+ * same bits on every run.  It DEPENDS ON THE ROW ORDER, by design, and rows 0 .. n of it on no later row.
+ * max_distance negative: every row stands for itself; +inf: a row is a representative iff its distance to every earlier
+ * one is NaN; NaN: KPOP_ERR_INVALID.  r1 = 0: KPOP_OK and *n_reps = 0.  A row with a NaN in it stands for itself alone.
+ * known_rows <= r1 (0: none) says that rep_of[0 .. known_rows) hold, on entry, what this call returned for those rows at
+ * the same max_distance: they are not examined against each other, rep_dist[0 .. known_rows) is neither read nor
+ * written, and the result is that of known_rows = 0, bit for bit -- after kpop_refset_append a re-thin costs new rows x
+ * representatives.  known_rows = r1 examines nothing.  Semantics: INTEGRATION.md 6h; timings: profiles/representatives.md. */
+/* (lib/Space.ml:182-205; lib/Matrix.ml:243-250.)  rep_of: r1 entries, the first known_rows read and checked against the
+   two invariants above (KPOP_ERR_INVALID), the others written; rep_dist: r1 entries or NULL.  Synchronises.            */
+int kpop_representatives_within(kpop_refset *rs, double max_distance, uint32_t known_rows, uint32_t *rep_of,
+                                double *rep_dist, uint32_t *n_reps);
+/* bytes of d_work for kpop_dev_representatives_within (lib/Space.ml:182-205 over the set against itself, see the block
+   above), for the set's r1 at the time of the call: the representatives' indices and a step's tables; no copy of rows  */
+uint64_t kpop_dev_representatives_within_workspace_bytes(const kpop_refset *rs);
+/* (lib/Space.ml:182-205; lib/Matrix.ml:243-250.)  Enqueues only, reads nothing back.  d_rep_of[r1] (the first known_rows
+   TRUSTED to be an earlier result), d_rep_dist[r1] or NULL, d_n_reps[1].                                               */
+int kpop_dev_representatives_within(kpop_refset *rs, double max_distance, uint32_t known_rows, void *d_work,
+                                    uint32_t *d_rep_of, double *d_rep_dist, uint32_t *d_n_reps, void *stream);
+/* unprepared convenience (lib/Matrix.ml:191-266 for the distances, m against itself): a temporary set over m, then
+   kpop_representatives_within with known_rows = 0                                                                      */
+int kpop_distance_representatives(const double *m, uint32_t rows, uint32_t n_dims, const double *metric, int kind,
+                                  double p, int normalize, double max_distance, uint32_t *rep_of, double *rep_dist,
+                                  uint32_t *n_reps);
+
 /* ------------------------------------------------- k-mer database (KPopCountDB)
  * the operations of lib/KMerDB.ml that touch every count.  A database is the reference's
  * `storage: I32BAVector.t array` (lib/KMerDB.ml:54-63): n_cols spectra ("columns"), each a vector of n_rows int32

@@ -193,6 +193,11 @@ SIGNATURES = {
     "kpop_dev_knn_validate": (C.c_int, [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, u32p, C.c_uint32, vp, vp, vp, vp, vp, vp, vp]),
     "kpop_distance_knn_validate": (C.c_int, [f64p, C.c_uint32, C.c_uint32, f64p, C.c_int, C.c_double, C.c_int, u32p, C.c_uint32, u32p, u32p, C.c_uint32,
                                              u32p, u32p, u32p, f64p, u64p]),
+    # representatives at a distance: the greedy cover in row order (representatives.hip)
+    "kpop_representatives_within": (C.c_int, [vp, C.c_double, C.c_uint32, u32p, f64p, u32p]),
+    "kpop_dev_representatives_within_workspace_bytes": (C.c_uint64, [vp]),
+    "kpop_dev_representatives_within": (C.c_int, [vp, C.c_double, C.c_uint32, vp, vp, vp, vp, vp]),
+    "kpop_distance_representatives": (C.c_int, [f64p, C.c_uint32, C.c_uint32, f64p, C.c_int, C.c_double, C.c_int, C.c_double, u32p, f64p, u32p]),
 }
 
 

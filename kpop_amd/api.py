@@ -844,6 +844,32 @@ class RefSet:
         check(_lib.load().kpop_clusters_within(self._h, float(max_distance), known_rows, _p(labels, C.c_uint32), C.byref(n)))
         return labels[:r1], int(n.value)
 
+    def representatives(self, max_distance, known=None):
+        """The greedy cover of the set in row order -> (rep_of u32 [r1], rep_dist f64 [r1], n_reps): row i is a representative iff no
+        representative below it lies within max_distance; rep_of[i] is i for a representative and otherwise the nearest representative
+        BELOW row i (ties to the smaller index), rep_dist[i] its distance.  The same bits on every run; the result depends on the row
+        order, and its first n rows on no later row.  known: the rep_of an earlier call returned at the same max_distance for the first
+        len(known) rows (the set has grown since: append), or the whole tuple it returned; those rows are not examined against each
+        other, the result is the from-scratch one.  rep_dist of the known rows is not computed again: it is taken from the tuple, and
+        NaN where only rep_of was given (kpop_representatives_within, include/kpop_hip.h)."""
+        r1 = self.info()["r1"]
+        rep_of = np.zeros(max(r1, 1), dtype=np.uint32)
+        rep_dist = np.zeros(max(r1, 1), dtype=np.float64)
+        known_rows = 0
+        if known is not None:
+            known_dist = None
+            if isinstance(known, tuple):
+                known, known_dist = known[0], np.asarray(known[1])
+            known = np.asarray(known)
+            if known.ndim != 1 or len(known) > r1 or (known_dist is not None and known_dist.shape != known.shape):
+                raise ValueError("known: the rep_of of the first rows of the set, at most %d" % r1)
+            known_rows = len(known)
+            rep_of[:known_rows] = known
+            rep_dist[:known_rows] = np.nan if known_dist is None else known_dist
+        n = C.c_uint32()
+        check(_lib.load().kpop_representatives_within(self._h, float(max_distance), known_rows, _p(rep_of, C.c_uint32), _p(rep_dist, C.c_double), C.byref(n)))
+        return rep_of[:r1], rep_dist[:r1], int(n.value)
+
     def spanning_forest(self, max_distance=float("inf")):
         """The single-linkage tree of the set: the minimum spanning forest of the graph that joins rows i < j iff d(j, i) <= max_distance,
         under the order (d, i, j) -> (edge_i u32, edge_j u32, edge_dist f64, labels u32 [r1]).  The order is strict, so the forest is
@@ -1241,6 +1267,33 @@ def distance_clusters(m, metric, kind=EUCLIDEAN, p=2.0, normalize=True, max_dist
     check(_lib.load().kpop_distance_clusters(_p(_nz(m, np.float64), C.c_double), rows, len(metric), _p(_nz(metric, np.float64), C.c_double), int(kind),
                                              float(p), 1 if normalize else 0, float(max_distance), _p(labels, C.c_uint32), C.byref(n)))
     return labels[:rows], int(n.value)
+
+
+def dev_representatives_within_workspace_bytes(rs):
+    """the size of d_work for dev_representatives_within, for the set's r1 at the time of the call"""
+    return int(_lib.load().kpop_dev_representatives_within_workspace_bytes(rs.handle))
+
+
+def dev_representatives_within(rs, max_distance, d_work, d_rep_of, d_rep_dist, d_n_reps, known_rows=0, stream=0):
+    """enqueue only: d_rep_of[r1] (u32; the first known_rows an earlier result at the same max_distance, trusted), d_rep_dist[r1] (f64, or
+    None), d_n_reps[1] (u32)"""
+    check(_lib.load().kpop_dev_representatives_within(rs.handle, float(max_distance), int(known_rows), d_work, d_rep_of, d_rep_dist, d_n_reps, stream))
+
+
+def distance_representatives(m, metric, kind=EUCLIDEAN, p=2.0, normalize=True, max_distance=0.0):
+    """RefSet(m, ...).representatives(max_distance) without keeping the set: one call of kpop_distance_representatives ->
+    (rep_of u32 [rows], rep_dist f64 [rows], n_reps)"""
+    m, metric = _c(m, np.float64), _c(metric, np.float64)
+    if m.ndim != 2 or m.shape[1] != len(metric):
+        raise ValueError("Incompatible_geometries")  # lib/Matrix.ml:193-194
+    rows = m.shape[0]
+    rep_of = np.zeros(max(rows, 1), dtype=np.uint32)
+    rep_dist = np.zeros(max(rows, 1), dtype=np.float64)
+    n = C.c_uint32()
+    check(_lib.load().kpop_distance_representatives(_p(_nz(m, np.float64), C.c_double), rows, len(metric), _p(_nz(metric, np.float64), C.c_double), int(kind),
+                                                    float(p), 1 if normalize else 0, float(max_distance), _p(rep_of, C.c_uint32), _p(rep_dist, C.c_double),
+                                                    C.byref(n)))
+    return rep_of[:rows], rep_dist[:rows], int(n.value)
 
 
 def dev_spanning_forest_workspace_bytes(rs):

@@ -1,6 +1,6 @@
 // pair_tile.h -- the f64 pair tile of the vector pipe, once: the loop that every kernel computing the reference chain's distances
-// of a tile of pairs is built on (within.hip, clusters.hip, forest.hip, knn.hip; distance_rowwise_kernel keeps the form it was
-// written in, see distance.hip).
+// of a tile of pairs is built on (within.hip, clusters.hip, forest.hip, knn.hip, representatives.hip; distance_rowwise_kernel keeps
+// the form it was written in, see distance.hip).
 //
 //   A workgroup of 256 threads owns columns i0 .. i1 (rows of the first operand) x rows j0 .. j1 (rows of the second); a thread
 //   4 columns x TY rows.  The chain of a pair (lib/Space.ml:192-200 with the adaptors of lib/Matrix.ml:243-250) is ONE thread's,
@@ -44,6 +44,25 @@ struct PairStage {
     for (int q = 0; q < NA; ++q) {
       const uint32_t row = rbase + q * 16;
       ra[q] = (cok && i0 + row < i1) ? a[(uint64_t)(i0 + row) * n_dims + c0 + sc] : 0.0;
+    }
+#pragma unroll
+    for (int q = 0; q < NB; ++q) {
+      const uint32_t row = rbase + q * 16;
+      rb[q] = (cok && j0 + row < j1) ? b[(uint64_t)(j0 + row) * n_dims + c0 + sc] : 0.0;
+    }
+  }
+
+  // load, the columns gathered: column i0 + k of the tile is row idx[i0 + k] of a, i0 .. i1 positions in the index list (an index
+  // is held below a_rows, the rows of a: a list that was never written cannot lead a load out of a); the rows of b as in load.  The
+  // staging, and so store and the arithmetic, are the same
+  __device__ __forceinline__ void load_indexed(const double *__restrict__ a, uint32_t a_rows, const uint32_t *__restrict__ idx, uint32_t i0, uint32_t i1,
+                                               const double *__restrict__ b, uint32_t j0, uint32_t j1, uint32_t n_dims, uint32_t c0, uint32_t d_end) {
+    const uint32_t sc = threadIdx.x % kPairDC, rbase = threadIdx.x / kPairDC;
+    const bool cok = c0 + sc < d_end;
+#pragma unroll
+    for (int q = 0; q < NA; ++q) {
+      const uint32_t row = rbase + q * 16;
+      ra[q] = (cok && i0 + row < i1) ? a[(uint64_t)min(idx[i0 + row], a_rows - 1) * n_dims + c0 + sc] : 0.0;
     }
 #pragma unroll
     for (int q = 0; q < NB; ++q) {
