@@ -866,6 +866,52 @@ int kpop_distance_representatives(const double *m, uint32_t rows, uint32_t n_dim
                                   double p, int normalize, double max_distance, uint32_t *rep_of, double *rep_dist,
                                   uint32_t *n_reps);
 
+/* ------------------------------------------------- DBSCAN on a resident set (core rows, border rows and noise)
+ * The density-based cut of kpop_clusters_within's graph: a cluster is where at least min_pts rows sit within eps of each
+ * other, a row on the rim belongs to the cluster it touches, everything else is noise -- one pair of stray rows between
+ * two lineages no longer chains them into one.  d(j, i) is the reference chain's distance (lib/Space.ml:182-205 with the
+ * adaptors of lib/Matrix.ml:243-250) -- the bits kpop_refset_distance_rowwise writes under kpop_tune("distance_mfma", 0)
+ * when the set's own rows are the query -- whatever kpop_tune says; symmetric bit for bit, so only i < j is examined and
+ * the pair i == j never; a NaN distance is within nothing.  degree[i] = 1 + #{ j != i : d(i, j) <= eps }: the row counts
+ * itself, whatever its values are (a row with a NaN in it has degree 1).  Row i is a CORE row iff degree[i] >= min_pts.
+ * THE CLUSTERS are the connected components of the graph restricted to the core rows; a core row's label is the smallest
+ * core row index of its component, and core_of[i] = i.  A row that is not core and has a core row within eps is a BORDER
+ * row: core_of[i] is the core row least under (d with -0 taken as +0, index) among those within eps -- the nearest, ties
+ * to the smaller ROW INDEX, not to the smaller label -- and labels[i] = labels[core_of[i]].  A border row joins nothing:
+ * two clusters that share only a border row stay two.  Every other row is NOISE: labels[i] = core_of[i] = KPOP_NOISE.
+ * counts[0]: the clusters (core rows with labels[i] == i); counts[1]: the core rows; counts[2]: the noise rows.  For a
+ * row that is not noise labels[labels[i]] == labels[i] and labels[i] is a core row; for a core row labels[i] <= i (a
+ * border row's label may exceed its index).  Integer sums, canonical labels, the minimum of a strict total order: a
+ * function of the distances alone, the same bits on every run.
+ * eps NaN: KPOP_ERR_INVALID; eps negative: every degree is 1 (min_pts = 1: every row a cluster of its own; otherwise all
+ * noise); +inf: every pair whose distance is a number, +inf included.  min_pts = 0: KPOP_ERR_INVALID; min_pts > r1: all
+ * noise.  r1 = 0: KPOP_OK and the counts all zero.  min_pts = 1: the labels of kpop_clusters_within(eps), bit for bit,
+ * and no noise; min_pts = 2: a component of two or more rows keeps that label and a singleton is noise; for eps >= 0 and
+ * a row of finite values degree[i] is the length of row i's list in kpop_neighbours_within(the set's rows, eps).
+ * THERE IS NO known_rows: a new row can turn old rows that were not core into core rows, so no earlier result is a valid
+ * start; after kpop_refset_append the call is made again in full.  Neither the r1 x r1 matrix nor a neighbour list is
+ * formed.  The set's limits, slot and thread ownership hold as for every call on a set.  Semantics: INTEGRATION.md 6i;
+ * timings: profiles/dbscan.md. */
+#define KPOP_NOISE 0xFFFFFFFFu
+/* (lib/Space.ml:182-205; lib/Matrix.ml:243-250.)  Host arrays: labels[r1], core_of[r1] or NULL, degree[r1] or NULL,
+   counts[3].  Synchronises.                                                                                            */
+int kpop_dbscan(kpop_refset *rs, double eps, uint32_t min_pts, uint32_t *labels, uint32_t *core_of, uint32_t *degree,
+                uint32_t *counts);
+/* bytes of d_work for kpop_dev_dbscan (lib/Space.ml:182-205 over the set against itself, see the block above), for the
+   set's r1 at the time of the call.  It grows with r1 and holds: the rows' hit counters (the degrees, 4 bytes a row), two
+   tile bitmaps (a bit a tile of the triangle's grid each: the tiles with a hit, and those with a hit that has one core
+   end) and the border rows' least key and core row (12 bytes a row); 1.8 MiB for 100,000 rows; no copy of rows         */
+uint64_t kpop_dev_dbscan_workspace_bytes(const kpop_refset *rs);
+/* (lib/Space.ml:182-205; lib/Matrix.ml:243-250.)  Enqueues only, reads nothing back, allocates nothing.  d_labels[r1],
+   d_core_of[r1] or NULL, d_degree[r1] or NULL (the workspace holds the degrees either way), d_counts[3].              */
+int kpop_dev_dbscan(kpop_refset *rs, double eps, uint32_t min_pts, void *d_work, uint32_t *d_labels,
+                    uint32_t *d_core_of, uint32_t *d_degree, uint32_t *d_counts, void *stream);
+/* unprepared convenience (lib/Matrix.ml:191-266 for the distances, m against itself): a temporary set over m, then
+   kpop_dbscan                                                                                                          */
+int kpop_distance_dbscan(const double *m, uint32_t rows, uint32_t n_dims, const double *metric, int kind, double p,
+                         int normalize, double eps, uint32_t min_pts, uint32_t *labels, uint32_t *core_of,
+                         uint32_t *degree, uint32_t *counts);
+
 /* ------------------------------------------------- k-mer database (KPopCountDB)
  * the operations of lib/KMerDB.ml that touch every count.  A database is the reference's
  * `storage: I32BAVector.t array` (lib/KMerDB.ml:54-63): n_cols spectra ("columns"), each a vector of n_rows int32

@@ -198,6 +198,11 @@ SIGNATURES = {
     "kpop_dev_representatives_within_workspace_bytes": (C.c_uint64, [vp]),
     "kpop_dev_representatives_within": (C.c_int, [vp, C.c_double, C.c_uint32, vp, vp, vp, vp, vp]),
     "kpop_distance_representatives": (C.c_int, [f64p, C.c_uint32, C.c_uint32, f64p, C.c_int, C.c_double, C.c_int, C.c_double, u32p, f64p, u32p]),
+    # DBSCAN on a resident set: core rows, border rows and noise (dbscan.hip)
+    "kpop_dbscan": (C.c_int, [vp, C.c_double, C.c_uint32, u32p, u32p, u32p, u32p]),
+    "kpop_dev_dbscan_workspace_bytes": (C.c_uint64, [vp]),
+    "kpop_dev_dbscan": (C.c_int, [vp, C.c_double, C.c_uint32, vp, vp, vp, vp, vp, vp]),
+    "kpop_distance_dbscan": (C.c_int, [f64p, C.c_uint32, C.c_uint32, f64p, C.c_int, C.c_double, C.c_int, C.c_double, C.c_uint32, u32p, u32p, u32p, u32p]),
 }
 
 

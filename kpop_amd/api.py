@@ -870,6 +870,21 @@ class RefSet:
         check(_lib.load().kpop_representatives_within(self._h, float(max_distance), known_rows, _p(rep_of, C.c_uint32), _p(rep_dist, C.c_double), C.byref(n)))
         return rep_of[:r1], rep_dist[:r1], int(n.value)
 
+    def dbscan(self, eps, min_pts):
+        """DBSCAN of the set -> (labels u32 [r1], core_of u32 [r1], degree u32 [r1], counts u32 [3]).  degree[i] = 1 + the rows within
+        eps of row i; row i is a core row iff degree[i] >= min_pts; the clusters are the connected components of the core rows, a core
+        row's label the smallest core row index of its component and core_of[i] = i; a row that is not core and has a core row within
+        eps is a border row: core_of[i] its nearest core row (ties to the smaller row index), labels[i] that row's label, and it joins
+        nothing; every other row is noise: labels[i] = core_of[i] = NOISE.  counts: the clusters, the core rows, the noise rows.  The
+        same bits on every run.  No earlier result is a valid start: after append the call is made again in full (kpop_dbscan,
+        include/kpop_hip.h)."""
+        r1 = self.info()["r1"]
+        labels, core_of, degree = (np.zeros(max(r1, 1), dtype=np.uint32) for _ in range(3))
+        counts = np.zeros(3, dtype=np.uint32)
+        check(_lib.load().kpop_dbscan(self._h, float(eps), _min_pts(min_pts), _p(labels, C.c_uint32), _p(core_of, C.c_uint32), _p(degree, C.c_uint32),
+                                      _p(counts, C.c_uint32)))
+        return labels[:r1], core_of[:r1], degree[:r1], counts
+
     def spanning_forest(self, max_distance=float("inf")):
         """The single-linkage tree of the set: the minimum spanning forest of the graph that joins rows i < j iff d(j, i) <= max_distance,
         under the order (d, i, j) -> (edge_i u32, edge_j u32, edge_dist f64, labels u32 [r1]).  The order is strict, so the forest is
@@ -1294,6 +1309,42 @@ def distance_representatives(m, metric, kind=EUCLIDEAN, p=2.0, normalize=True, m
                                                     float(p), 1 if normalize else 0, float(max_distance), _p(rep_of, C.c_uint32), _p(rep_dist, C.c_double),
                                                     C.byref(n)))
     return rep_of[:rows], rep_dist[:rows], int(n.value)
+
+
+NOISE = 0xFFFFFFFF  # KPOP_NOISE: the label and the core row of a row that is neither a core row nor within eps of one
+
+
+def _min_pts(min_pts):
+    """a count a uint32 holds (zero goes through: the library says what is wrong with it)"""
+    min_pts = int(min_pts)
+    if not 0 <= min_pts <= 0xFFFFFFFF:
+        raise ValueError("min_pts: a count of rows")
+    return min_pts
+
+
+def dev_dbscan_workspace_bytes(rs):
+    """the size of d_work for dev_dbscan, for the set's r1 at the time of the call"""
+    return int(_lib.load().kpop_dev_dbscan_workspace_bytes(rs.handle))
+
+
+def dev_dbscan(rs, eps, min_pts, d_work, d_labels, d_core_of, d_degree, d_counts, stream=0):
+    """enqueue only: d_labels[r1] (u32), d_core_of[r1] (u32, or None), d_degree[r1] (u32, or None), d_counts[3] (u32)"""
+    check(_lib.load().kpop_dev_dbscan(rs.handle, float(eps), _min_pts(min_pts), d_work, d_labels, d_core_of, d_degree, d_counts, stream))
+
+
+def distance_dbscan(m, metric, kind=EUCLIDEAN, p=2.0, normalize=True, eps=0.0, min_pts=1):
+    """RefSet(m, ...).dbscan(eps, min_pts) without keeping the set: one call of kpop_distance_dbscan ->
+    (labels u32 [rows], core_of u32 [rows], degree u32 [rows], counts u32 [3])"""
+    m, metric = _c(m, np.float64), _c(metric, np.float64)
+    if m.ndim != 2 or m.shape[1] != len(metric):
+        raise ValueError("Incompatible_geometries")  # lib/Matrix.ml:193-194
+    rows = m.shape[0]
+    labels, core_of, degree = (np.zeros(max(rows, 1), dtype=np.uint32) for _ in range(3))
+    counts = np.zeros(3, dtype=np.uint32)
+    check(_lib.load().kpop_distance_dbscan(_p(_nz(m, np.float64), C.c_double), rows, len(metric), _p(_nz(metric, np.float64), C.c_double), int(kind),
+                                           float(p), 1 if normalize else 0, float(eps), _min_pts(min_pts), _p(labels, C.c_uint32), _p(core_of, C.c_uint32),
+                                           _p(degree, C.c_uint32), _p(counts, C.c_uint32)))
+    return labels[:rows], core_of[:rows], degree[:rows], counts
 
 
 def dev_spanning_forest_workspace_bytes(rs):

@@ -1,0 +1,543 @@
+// dbscan.hip -- DBSCAN on a resident set: core rows, border rows and noise, the density-based cut of the graph of clusters.hip.
+//
+//   The graph: the set's r1 rows, d(j, i) the reference chain's distance (lib/Space.ml:182-205 with the adaptors of
+//   lib/Matrix.ml:243-250): the bits kpop_refset_distance_rowwise writes on the vector pipe when the set's own rows are the query -- no
+//   kpop_tune setting is read.  Symmetric bit for bit (clusters.hip), so only i < j is examined and i == j never; a NaN is within
+//   nothing.  degree[i] = 1 + #{ j != i : d(i, j) <= eps }; row i is a CORE row iff degree[i] >= min_pts; the clusters are the
+//   connected components of the graph restricted to the core rows, a core row's label the smallest core row index of its component;
+//   a row that is not core and has a core row within eps is a BORDER row: core_of[i] the core row least under (d with -0 taken as +0,
+//   index), labels[i] = labels[core_of[i]], and it joins nothing; every other row is NOISE (labels = core_of = KPOP_NOISE).
+//   Integer sums, canonical labels, the minimum of a strict total order: a function of the distances alone, the same bits on every run.
+//
+// Neither the matrix nor a neighbour list is formed, nothing is read back, nothing synchronises.  Three launches walk
+// clusters_tile_kernel's grid (the folded upper triangle, both tile shapes) with its loop (pair_tile.h) and its compare; the second
+// and the third compute only the tiles that a bitmap of the launch before names:
+//   dbscan_degree_kernel    a hit (i, j) counts for both ends: the counts of a tile's w + TJ nodes are summed in registers, across
+//                           lanes with shuffles and across the wavefronts in LDS, and one global atomicAdd a node whose count is not
+//                           zero leaves the tile -- a dense lineage costs LDS traffic, not a global atomic a hit.  A tile with a hit
+//                           sets its bit in the tile bitmap
+//   dbscan_classify_kernel  degree[i] = 1 + counter, parent[i] = i (the forest lives in the labels, as in clusters.hip), counts[1]
+//   dbscan_union_kernel     a block whose tile bit is clear returns before it loads anything, and so does one whose nodes hold no
+//                           core row.  A hit between two core rows goes into the tile's forest in LDS, then one global union a node
+//                           (union_find.h); a row that is not core is never hooked.  A hit with ONE core end is a border row's: the
+//                           least distance key of a node -- registers, shuffles -- goes into best_k[row] by one 64-bit atomicMin a
+//                           wavefront and node, and the tile sets its bit in the second bitmap
+//   dbscan_border_kernel    the tiles of the second bitmap, the same arithmetic, the same bits: among a border row's hits whose key
+//                           IS best_k[row], the least core row index goes into best_c[row] by a 32-bit atomicMin.  (key, then index:
+//                           the least under (d, index), with two integer minima and no 96-bit atomic)
+//   dbscan_finalize_kernel  a core row: its root (clusters_flatten_kernel's finds) and the count of the roots; any other row:
+//                           best_c[row] and that core row's root, or KPOP_NOISE, and the count of the noise
+// On a sparse graph the second launch costs its share of tiles with a hit and the third next to nothing: this is the point of the
+// bitmaps.  eps < 0: no tile kernel runs (every degree is 1).  No known_rows: a new row can turn old rows that were not core into core
+// rows, so no earlier result is a valid start; after kpop_refset_append the call is made again in full.
+#include <algorithm>
+
+#include "common.h"
+#include "distance_routes.h"
+#include "pair_tile.h"
+#include "refset.h"
+#include "space_ops.h"
+#include "union_find.h"
+
+namespace kpop {
+
+constexpr int kDbMaxW = 64, kDbMaxTJ = 256;
+constexpr uint64_t kDbNone = ~0ull;         // (no key: distance_key maps only a NaN's bits there, and a NaN is never a key)
+constexpr uint32_t kDbNoise = 0xFFFFFFFFu;  // KPOP_NOISE; best_k and best_c start as all ones: one memset
+
+// the two shapes of clusters_tiles (clusters.hip): 32 columns x 256 rows, a thread 4 x 8, for a long set; 64 x 64, a thread 4 x 4,
+// below.  Either way n_cg n_rg = 256: every thread of a workgroup holds pairs.  (The choice moves no bit.)
+struct DbShape {
+  bool big;
+  uint32_t w, n_cg, n_rg, TJ, kf, n_rt, n_ct;
+};
+
+static DbShape dbscan_shape(uint32_t r1) {
+  DbShape s;
+  s.big = r1 >= 65536;
+  s.w = s.big ? 32 : 64;
+  s.n_cg = s.w / 4;
+  s.n_rg = 256 / s.n_cg;
+  s.TJ = (s.big ? 8 : 4) * s.n_rg;
+  s.kf = s.TJ / s.w;
+  s.n_rt = div_up(std::max(r1, 1u), s.TJ);
+  s.n_ct = s.n_rt * s.kf;  // the column tiles of a line of a bitmap
+  return s;
+}
+
+// cnt[r1]: the hits of a row (degree - 1); hit_map, mixed_map: a bit a tile, line by of n_ct bits -- a tile with a hit, a tile with
+// a hit that has one core end; these three are cleared by one memset.  best_k[r1], best_c[r1]: the least key of a row's hits with
+// one core end, and the least core row index among the hits of that key; filled with ones by one memset
+struct DbWork {
+  uint32_t *cnt, *hit_map, *mixed_map, *best_c;
+  uint64_t *best_k;
+  uint64_t clear_bytes, fill_bytes, bytes;
+};
+
+static DbWork dbscan_carve(void *base, uint32_t r1) {
+  const uint64_t n = std::max(r1, 1u);
+  const DbShape s = dbscan_shape(r1);
+  char *c = reinterpret_cast<char *>(base);
+  uint64_t off = 0;
+  auto take = [&](uint64_t b) {
+    char *q = c + off;
+    off += (b + 255) & ~255ull;
+    return q;
+  };
+  const uint64_t map_bytes = ((uint64_t)s.n_rt * s.n_ct + 31) / 32 * 4;
+  DbWork f;
+  f.cnt = reinterpret_cast<uint32_t *>(take(n * 4));
+  f.hit_map = reinterpret_cast<uint32_t *>(take(map_bytes));
+  f.mixed_map = reinterpret_cast<uint32_t *>(take(map_bytes));
+  f.clear_bytes = off;
+  f.best_k = reinterpret_cast<uint64_t *>(take(n * 8));
+  f.best_c = reinterpret_cast<uint32_t *>(take(n * 4));
+  f.fill_bytes = off - f.clear_bytes;
+  f.bytes = off;
+  return f;
+}
+
+// which tile of the folded upper triangle a block of clusters_tile_kernel's grid owns (by_first = 0: every row is new)
+struct DbTile {
+  uint32_t bx, by, i0, i1, j0, j1;
+  bool live;
+};
+
+__device__ __forceinline__ DbTile dbscan_tile(uint32_t w, uint32_t TJ, uint32_t r1, uint32_t kf, uint32_t n_rt, uint32_t ybase) {
+  DbTile t;
+  t.live = false;
+  const uint32_t y = ybase + blockIdx.y;
+  const uint32_t by_lo = y, by_hi = n_rt - 1 - y;
+  const uint32_t n_lo = (by_lo + 1) * kf;
+  t.bx = blockIdx.x;
+  t.by = by_lo;
+  if (t.bx >= n_lo) {
+    if (by_hi == by_lo) return t;  // (the middle line of an odd number: once)
+    t.bx -= n_lo;
+    t.by = by_hi;
+  }
+  t.i0 = t.bx * w;
+  t.j0 = t.by * TJ;
+  t.j1 = min(r1, t.j0 + TJ);
+  if (t.i0 + 1 >= t.j1) return t;  // (the last row tile is ragged: no column below its last row)
+  t.i1 = min(r1, t.i0 + w);
+  t.live = true;
+  return t;
+}
+
+__device__ __forceinline__ bool dbscan_tile_bit(const uint32_t *__restrict__ map, const DbTile &t, uint32_t n_ct) {
+  const uint64_t bit = (uint64_t)t.by * n_ct + t.bx;
+  return (map[bit >> 5] >> (bit & 31)) & 1u;
+}
+
+__device__ __forceinline__ void dbscan_set_tile_bit(uint32_t *__restrict__ map, const DbTile &t, uint32_t n_ct) {
+  const uint64_t bit = (uint64_t)t.by * n_ct + t.bx;
+  atomicOr(map + (bit >> 5), 1u << (bit & 31));
+}
+
+// the distances of the tile's pairs, a thread 4 columns x TY rows: clusters_tile_kernel's loop and scaling
+template <int KIND, int TY>
+__device__ __forceinline__ void dbscan_tile_distances(double (&acc)[TY][4], double (*As)[kDbMaxW + 2], double (*Bs)[kDbMaxTJ + 2], double *s_metric,
+                                                      const double *__restrict__ a, const DbTile &t, uint32_t n_dims, const double *__restrict__ metric,
+                                                      double p, uint32_t ti, uint32_t tj) {
+  pair_zero(acc);
+  PairStage<kDbMaxW, kDbMaxTJ> stage;
+  stage.load(a, t.i0, t.i1, a, t.j0, t.j1, n_dims, 0, n_dims);
+  for (uint32_t c0 = 0; c0 < n_dims; c0 += kPairDC) {
+    __syncthreads();
+    stage.store(As, Bs, s_metric, metric, c0, n_dims);
+    __syncthreads();
+    if (c0 + kPairDC < n_dims) stage.load(a, t.i0, t.i1, a, t.j0, t.j1, n_dims, c0 + kPairDC, n_dims);
+    pair_accumulate<KIND>(acc, As, Bs, s_metric, ti, tj, min((uint32_t)kPairDC, n_dims - c0), p);
+  }
+#pragma unroll
+  for (int yy = 0; yy < TY; ++yy)
+#pragma unroll
+    for (int x = 0; x < 4; ++x) acc[yy][x] = scale_distance<KIND>(acc[yy][x], p);
+}
+
+// the tile's core flags, the columns first, then the rows (a node beyond the set is not core) -> does the tile hold a core row
+__device__ __forceinline__ bool dbscan_stage_core(uint8_t *s_core, const DbTile &t, uint32_t w, uint32_t TJ, uint32_t r1, const uint32_t *__restrict__ cnt,
+                                                  uint32_t need) {
+  bool any = false;
+  for (uint32_t n = threadIdx.x; n < w + TJ; n += 256) {
+    const uint32_t row = n < w ? t.i0 + n : t.j0 + (n - w);
+    const bool core = row < r1 && cnt[row] >= need;
+    s_core[n] = core ? 1 : 0;
+    any = any || core;
+  }
+  return __syncthreads_or(any);
+}
+
+// the hits of a thread's pairs: bit yy * 4 + x of `both` when both ends are core rows, of `mixed` when one is
+struct DbHits {
+  uint32_t both, mixed;
+};
+
+template <int TY>
+__device__ __forceinline__ DbHits dbscan_hits(const double (&acc)[TY][4], const DbTile &t, uint32_t w, uint32_t ti, uint32_t tj, double eps,
+                                              const uint8_t *s_core) {
+  uint32_t both = 0, mixed = 0;
+#pragma unroll
+  for (int yy = 0; yy < TY; ++yy)
+#pragma unroll
+    for (int x = 0; x < 4; ++x) {
+      const uint32_t i = t.i0 + ti + x, j = t.j0 + tj + yy;
+      // compare where clusters_tile_kernel compares (a NaN compares false); only i < j
+      if (j < t.j1 && i < t.i1 && i < j && acc[yy][x] <= eps) {
+        const bool ci = s_core[ti + x], cj = s_core[w + tj + yy];
+        if (ci && cj) both |= 1u << (yy * 4 + x);
+        else if (ci != cj) mixed |= 1u << (yy * 4 + x);
+      }
+    }
+  return DbHits{both, mixed};
+}
+
+// a: the set's rows as the chain reads them (divided by their norms when the set normalises), both operands.  The grid, the tiles
+// and the thread's pairs are clusters_tile_kernel's.  cnt[i] += the hits of row i in this tile, from either side
+template <int KIND, int TY>
+__global__ __launch_bounds__(256, 1) void dbscan_degree_kernel(const double *__restrict__ a, uint32_t w, uint32_t r1, uint32_t n_dims,
+                                                               const double *__restrict__ metric, double p, double eps, uint32_t n_cg, uint32_t n_rg,
+                                                               uint32_t kf, uint32_t n_rt, uint32_t ybase, uint32_t *__restrict__ cnt,
+                                                               uint32_t *__restrict__ hit_map) {
+  __shared__ __attribute__((aligned(16))) double As[kPairDC][kDbMaxW + 2];
+  __shared__ __attribute__((aligned(16))) double Bs[kPairDC][kDbMaxTJ + 2];
+  __shared__ double s_metric[kPairDC];
+  __shared__ uint32_t s_cnt[kDbMaxW + kDbMaxTJ];  // the tile's counts: the columns first, then the rows
+  const uint32_t TJ = TY * n_rg;
+  const DbTile t = dbscan_tile(w, TJ, r1, kf, n_rt, ybase);
+  if (!t.live) return;
+  const uint32_t cg = threadIdx.x % n_cg, rg = threadIdx.x / n_cg;
+  const uint32_t ti = cg * 4, tj = rg * TY;
+  for (uint32_t n = threadIdx.x; n < w + TJ; n += 256) s_cnt[n] = 0;  // (the loop's barriers come before anybody adds)
+  double acc[TY][4];
+  dbscan_tile_distances<KIND, TY>(acc, As, Bs, s_metric, a, t, n_dims, metric, p, ti, tj);
+  // the epilogue: compare where clusters_tile_kernel compares (a NaN compares false); only i < j
+  uint32_t mask = 0;
+#pragma unroll
+  for (int yy = 0; yy < TY; ++yy)
+#pragma unroll
+    for (int x = 0; x < 4; ++x) {
+      const uint32_t i = t.i0 + ti + x, j = t.j0 + tj + yy;
+      if (j < t.j1 && i < t.i1 && i < j && acc[yy][x] <= eps) mask |= 1u << (yy * 4 + x);
+    }
+  if (!__syncthreads_or(mask != 0)) return;  // most tiles of a sparse graph
+  // a row's n_cg threads are neighbouring lanes of one wavefront, and nobody else holds that row: a sum over them and a plain store
+#pragma unroll
+  for (int yy = 0; yy < TY; ++yy) {
+    uint32_t c = __popc((mask >> (4 * yy)) & 0xFu);
+    for (uint32_t o = n_cg >> 1; o > 0; o >>= 1) c += (uint32_t)__shfl_xor((int)c, (int)o, 64);
+    if (cg == 0) s_cnt[w + tj + yy] = c;
+  }
+  // a column's threads are the lanes of a wavefront that share cg, in every wavefront: a sum over those lanes, then one LDS add a
+  // wavefront and column
+#pragma unroll
+  for (int x = 0; x < 4; ++x) {
+    uint32_t c = __popc(mask & (0x11111111u << x));
+    for (uint32_t o = n_cg; o < 64; o <<= 1) c += (uint32_t)__shfl_xor((int)c, (int)o, 64);
+    if ((threadIdx.x & 63) < n_cg && c) atomicAdd(&s_cnt[ti + x], c);
+  }
+  __syncthreads();
+  for (uint32_t n = threadIdx.x; n < w + TJ; n += 256) {
+    const uint32_t c = s_cnt[n];
+    if (c) atomicAdd(cnt + (n < w ? t.i0 + n : t.j0 + (n - w)), c);  // (a node with a count lies inside the set: its pair was in bounds)
+  }
+  if (threadIdx.x == 0) dbscan_set_tile_bit(hit_map, t, n_rt * kf);
+}
+
+// after the degrees: row i is a core row iff 1 + cnt[i] >= min_pts, that is cnt[i] >= need = min_pts - 1.  The degrees, a forest of
+// single rows in the labels, and the number of core rows, an integer sum
+__global__ __launch_bounds__(256) void dbscan_classify_kernel(const uint32_t *__restrict__ cnt, uint32_t r1, uint32_t need, uint32_t *__restrict__ parent,
+                                                              uint32_t *__restrict__ degree, uint32_t *__restrict__ counts) {
+  __shared__ uint32_t s_core;
+  if (threadIdx.x == 0) s_core = 0;
+  __syncthreads();
+  uint32_t mine = 0;
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < r1; i += (uint64_t)gridDim.x * 256) {
+    const uint32_t c = cnt[i];
+    parent[i] = (uint32_t)i;
+    if (degree) degree[i] = c + 1;
+    if (c >= need) ++mine;
+  }
+  if (mine) atomicAdd(&s_core, mine);
+  __syncthreads();
+  if (threadIdx.x == 0 && s_core) atomicAdd(counts + 1, s_core);
+}
+
+// the grid, the tiles and the arithmetic of dbscan_degree_kernel, in the tiles where it found a hit.  A hit between two core rows
+// goes where clusters_tile_kernel's hits go; a hit with one core end gives the end that is not core a key
+template <int KIND, int TY>
+__global__ __launch_bounds__(256, 1) void dbscan_union_kernel(const double *__restrict__ a, uint32_t w, uint32_t r1, uint32_t n_dims,
+                                                              const double *__restrict__ metric, double p, double eps, uint32_t n_cg, uint32_t n_rg,
+                                                              uint32_t kf, uint32_t n_rt, uint32_t ybase, const uint32_t *__restrict__ cnt, uint32_t need,
+                                                              const uint32_t *__restrict__ hit_map, uint32_t *__restrict__ mixed_map, uint32_t *parent,
+                                                              uint64_t *__restrict__ best_k) {
+  __shared__ __attribute__((aligned(16))) double As[kPairDC][kDbMaxW + 2];
+  __shared__ __attribute__((aligned(16))) double Bs[kPairDC][kDbMaxTJ + 2];
+  __shared__ double s_metric[kPairDC];
+  __shared__ uint32_t s_par[kDbMaxW + kDbMaxTJ];  // the tile's forest: the columns first, then the rows
+  __shared__ uint8_t s_core[kDbMaxW + kDbMaxTJ];
+  const uint32_t TJ = TY * n_rg;
+  const DbTile t = dbscan_tile(w, TJ, r1, kf, n_rt, ybase);
+  if (!t.live) return;
+  if (!dbscan_tile_bit(hit_map, t, n_rt * kf)) return;  // no hit in this tile: most tiles of a sparse graph, and nothing was loaded
+  for (uint32_t n = threadIdx.x; n < w + TJ; n += 256) s_par[n] = n;
+  if (!dbscan_stage_core(s_core, t, w, TJ, r1, cnt, need)) return;  // hits, but no core row at either end of any
+  const uint32_t cg = threadIdx.x % n_cg, rg = threadIdx.x / n_cg;
+  const uint32_t ti = cg * 4, tj = rg * TY;
+  double acc[TY][4];
+  dbscan_tile_distances<KIND, TY>(acc, As, Bs, s_metric, a, t, n_dims, metric, p, ti, tj);
+  const DbHits hits = dbscan_hits<TY>(acc, t, w, ti, tj, eps, s_core);
+  const uint32_t mask = hits.both, mixed = hits.mixed;
+  if (__syncthreads_or(mixed != 0)) {
+    // the end of a mixed hit that is not core: the row when the column is core, otherwise the column.  A row's threads are n_cg
+    // neighbouring lanes, a column's the lanes of a wavefront that share cg: the least key over them, one atomicMin a wavefront and node
+#pragma unroll
+    for (int yy = 0; yy < TY; ++yy) {
+      uint64_t k = kDbNone;
+#pragma unroll
+      for (int x = 0; x < 4; ++x)
+        if ((mixed & (1u << (yy * 4 + x))) && s_core[ti + x]) k = min(k, distance_key(acc[yy][x]));
+      for (uint32_t o = n_cg >> 1; o > 0; o >>= 1) k = min(k, (uint64_t)__shfl_xor((unsigned long long)k, (int)o, 64));
+      if (cg == 0 && k != kDbNone) atomicMin(reinterpret_cast<unsigned long long *>(best_k + t.j0 + tj + yy), (unsigned long long)k);
+    }
+#pragma unroll
+    for (int x = 0; x < 4; ++x) {
+      uint64_t k = kDbNone;
+#pragma unroll
+      for (int yy = 0; yy < TY; ++yy)
+        if ((mixed & (1u << (yy * 4 + x))) && !s_core[ti + x]) k = min(k, distance_key(acc[yy][x]));
+      for (uint32_t o = n_cg; o < 64; o <<= 1) k = min(k, (uint64_t)__shfl_xor((unsigned long long)k, (int)o, 64));
+      if ((threadIdx.x & 63) < n_cg && k != kDbNone) atomicMin(reinterpret_cast<unsigned long long *>(best_k + t.i0 + ti + x), (unsigned long long)k);
+    }
+    if (threadIdx.x == 0) dbscan_set_tile_bit(mixed_map, t, n_rt * kf);
+  }
+  if (!__syncthreads_or(mask != 0)) return;
+  // the tile's own forest, in LDS: whatever the number of hits, what leaves the tile is one union per node
+  constexpr int WG = __HIP_MEMORY_SCOPE_WORKGROUP, DEV = __HIP_MEMORY_SCOPE_AGENT;
+  if (mask) {
+#pragma unroll
+    for (int yy = 0; yy < TY; ++yy)
+#pragma unroll
+      for (int x = 0; x < 4; ++x)
+        if (mask & (1u << (yy * 4 + x))) uf_unite<WG>(s_par, ti + x, w + tj + yy);
+  }
+  __syncthreads();
+  for (uint32_t n = threadIdx.x; n < w + TJ; n += 256) {
+    const uint32_t root = uf_find_readonly<WG>(s_par, n);
+    if (root != n) uf_unite<DEV>(parent, n < w ? t.i0 + n : t.j0 + (n - w), root < w ? t.i0 + root : t.j0 + (root - w));
+  }
+}
+
+// the same grid a third time, in the tiles where dbscan_union_kernel found a hit with one core end; the same arithmetic gives the
+// same bits, so a hit's key IS best_k of its end that is not core or lies above it.  Among those that are it: the least core row index
+template <int KIND, int TY>
+__global__ __launch_bounds__(256, 1) void dbscan_border_kernel(const double *__restrict__ a, uint32_t w, uint32_t r1, uint32_t n_dims,
+                                                               const double *__restrict__ metric, double p, double eps, uint32_t n_cg, uint32_t n_rg,
+                                                               uint32_t kf, uint32_t n_rt, uint32_t ybase, const uint32_t *__restrict__ cnt, uint32_t need,
+                                                               const uint32_t *__restrict__ mixed_map, const uint64_t *__restrict__ best_k,
+                                                               uint32_t *__restrict__ best_c) {
+  __shared__ __attribute__((aligned(16))) double As[kPairDC][kDbMaxW + 2];
+  __shared__ __attribute__((aligned(16))) double Bs[kPairDC][kDbMaxTJ + 2];
+  __shared__ double s_metric[kPairDC];
+  __shared__ uint8_t s_core[kDbMaxW + kDbMaxTJ];
+  const uint32_t TJ = TY * n_rg;
+  const DbTile t = dbscan_tile(w, TJ, r1, kf, n_rt, ybase);
+  if (!t.live) return;
+  if (!dbscan_tile_bit(mixed_map, t, n_rt * kf)) return;  // no border row's hit in this tile: nothing is loaded
+  dbscan_stage_core(s_core, t, w, TJ, r1, cnt, need);
+  const uint32_t cg = threadIdx.x % n_cg, rg = threadIdx.x / n_cg;
+  const uint32_t ti = cg * 4, tj = rg * TY;
+  double acc[TY][4];
+  dbscan_tile_distances<KIND, TY>(acc, As, Bs, s_metric, a, t, n_dims, metric, p, ti, tj);
+  const uint32_t mixed = dbscan_hits<TY>(acc, t, w, ti, tj, eps, s_core).mixed;
+  if (!__syncthreads_or(mixed != 0)) return;
+  // rows that are not core against core columns: the least column index among the hits of the row's key
+#pragma unroll
+  for (int yy = 0; yy < TY; ++yy) {
+    uint32_t c = kDbNoise;
+    const uint32_t m = (mixed >> (4 * yy)) & 0xFu;
+    if (m) {
+      const uint64_t k = best_k[t.j0 + tj + yy];  // (a mixed hit lies inside the set)
+#pragma unroll
+      for (int x = 3; x >= 0; --x)
+        if ((m & (1u << x)) && s_core[ti + x] && distance_key(acc[yy][x]) == k) c = t.i0 + ti + x;
+    }
+    for (uint32_t o = n_cg >> 1; o > 0; o >>= 1) c = min(c, (uint32_t)__shfl_xor((int)c, (int)o, 64));
+    if (cg == 0 && c != kDbNoise) atomicMin(best_c + t.j0 + tj + yy, c);
+  }
+  // columns that are not core against core rows
+#pragma unroll
+  for (int x = 0; x < 4; ++x) {
+    uint32_t c = kDbNoise;
+    if ((mixed & (0x11111111u << x)) && !s_core[ti + x]) {
+      const uint64_t k = best_k[t.i0 + ti + x];
+#pragma unroll
+      for (int yy = TY - 1; yy >= 0; --yy)
+        if ((mixed & (1u << (yy * 4 + x))) && distance_key(acc[yy][x]) == k) c = t.j0 + tj + yy;
+    }
+    for (uint32_t o = n_cg; o < 64; o <<= 1) c = min(c, (uint32_t)__shfl_xor((int)c, (int)o, 64));
+    if ((threadIdx.x & 63) < n_cg && c != kDbNoise) atomicMin(best_c + t.i0 + ti + x, c);
+  }
+}
+
+// after everything else.  A core row: its root, as in clusters_flatten_kernel (a root is a row whose word is its own index: no store
+// here changes that, and a word on somebody's path is that row's ancestor before the store and after it; only core rows lie on a
+// path).  Any other row: its core row's root, or the noise.  counts[0]: the roots; counts[2]: the noise
+__global__ __launch_bounds__(256) void dbscan_finalize_kernel(const uint32_t *__restrict__ cnt, uint32_t r1, uint32_t need, const uint32_t *__restrict__ best_c,
+                                                              uint32_t *parent, uint32_t *__restrict__ core_of, uint32_t *__restrict__ counts) {
+  __shared__ uint32_t s_roots, s_noise;
+  if (threadIdx.x == 0) s_roots = s_noise = 0;
+  __syncthreads();
+  constexpr int DEV = __HIP_MEMORY_SCOPE_AGENT;
+  uint32_t roots = 0, noise = 0;
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < r1; i += (uint64_t)gridDim.x * 256) {
+    if (cnt[i] >= need) {
+      const uint32_t root = uf_find_readonly<DEV>(parent, (uint32_t)i);
+      if (root == (uint32_t)i) ++roots;
+      else __hip_atomic_store(parent + i, root, __ATOMIC_RELAXED, DEV);
+      if (core_of) core_of[i] = (uint32_t)i;
+      continue;
+    }
+    const uint32_t of = best_c[i];
+    uint32_t label = kDbNoise;
+    if (of < r1) label = uf_find_readonly<DEV>(parent, of);  // (an index a kernel wrote is a core row of the set; all ones: none)
+    else ++noise;
+    __hip_atomic_store(parent + i, label, __ATOMIC_RELAXED, DEV);  // (nobody's path holds a row that is not core)
+    if (core_of) core_of[i] = of < r1 ? of : kDbNoise;
+  }
+  if (roots) atomicAdd(&s_roots, roots);
+  if (noise) atomicAdd(&s_noise, noise);
+  __syncthreads();
+  if (threadIdx.x == 0 && s_roots) atomicAdd(counts, s_roots);
+  if (threadIdx.x == 0 && s_noise) atomicAdd(counts + 2, s_noise);
+}
+
+// one of the three launches over the triangle's grid: pass 0 the degrees, 1 the unions and the border keys, 2 the border indices
+template <int KIND>
+static int dbscan_tiles(const double *a, uint32_t r1, uint32_t n_dims, const double *metric, double p, double eps, uint32_t need, const DbShape &s,
+                        const DbWork &f, uint32_t *parent, int pass, hipStream_t st) {
+  const uint32_t lines = (s.n_rt + 1) / 2;
+  const uint32_t gx = (s.n_rt + 1) * s.kf;  // the tiles of a row tile and of its partner from the end
+  for (uint32_t ybase = 0; ybase < lines; ybase += 65535u) {
+    const dim3 grid(gx, std::min(65535u, lines - ybase));
+    if (pass == 0) {
+      if (s.big)
+        dbscan_degree_kernel<KIND, 8><<<grid, dim3(256), 0, st>>>(a, s.w, r1, n_dims, metric, p, eps, s.n_cg, s.n_rg, s.kf, s.n_rt, ybase, f.cnt, f.hit_map);
+      else
+        dbscan_degree_kernel<KIND, 4><<<grid, dim3(256), 0, st>>>(a, s.w, r1, n_dims, metric, p, eps, s.n_cg, s.n_rg, s.kf, s.n_rt, ybase, f.cnt, f.hit_map);
+    } else if (pass == 1) {
+      if (s.big)
+        dbscan_union_kernel<KIND, 8><<<grid, dim3(256), 0, st>>>(a, s.w, r1, n_dims, metric, p, eps, s.n_cg, s.n_rg, s.kf, s.n_rt, ybase, f.cnt, need, f.hit_map,
+                                                                 f.mixed_map, parent, f.best_k);
+      else
+        dbscan_union_kernel<KIND, 4><<<grid, dim3(256), 0, st>>>(a, s.w, r1, n_dims, metric, p, eps, s.n_cg, s.n_rg, s.kf, s.n_rt, ybase, f.cnt, need, f.hit_map,
+                                                                 f.mixed_map, parent, f.best_k);
+    } else {
+      if (s.big)
+        dbscan_border_kernel<KIND, 8><<<grid, dim3(256), 0, st>>>(a, s.w, r1, n_dims, metric, p, eps, s.n_cg, s.n_rg, s.kf, s.n_rt, ybase, f.cnt, need, f.mixed_map,
+                                                                  f.best_k, f.best_c);
+      else
+        dbscan_border_kernel<KIND, 4><<<grid, dim3(256), 0, st>>>(a, s.w, r1, n_dims, metric, p, eps, s.n_cg, s.n_rg, s.kf, s.n_rt, ybase, f.cnt, need, f.mixed_map,
+                                                                  f.best_k, f.best_c);
+    }
+    KPOP_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+static int dbscan_pass(const kpop_refset *rs, const double *a, double eps, uint32_t need, const DbShape &s, const DbWork &f, uint32_t *parent, int pass,
+                       hipStream_t st) {
+  switch (rs->kind) {
+    case KPOP_EUCLIDEAN: return dbscan_tiles<KPOP_EUCLIDEAN>(a, rs->r1, rs->n_dims, rs->metric, rs->p, eps, need, s, f, parent, pass, st);
+    case KPOP_COSINE: return dbscan_tiles<KPOP_COSINE>(a, rs->r1, rs->n_dims, rs->metric, rs->p, eps, need, s, f, parent, pass, st);
+    default: return dbscan_tiles<KPOP_MINKOWSKI>(a, rs->r1, rs->n_dims, rs->metric, rs->p, eps, need, s, f, parent, pass, st);
+  }
+}
+
+// the body of both entry points: enqueues only
+static int dbscan_dev(kpop_refset *rs, double eps, uint32_t min_pts, void *d_work, uint32_t *d_labels, uint32_t *d_core_of, uint32_t *d_degree,
+                      uint32_t *d_counts, hipStream_t st, const char *who) {
+  if (eps != eps) KPOP_FAIL(KPOP_ERR_INVALID, "%s: eps is not a number", who);
+  if (min_pts == 0) KPOP_FAIL(KPOP_ERR_INVALID, "%s: min_pts is zero (a row counts itself: 1 makes every row a core row)", who);
+  if (!d_counts) KPOP_FAIL(KPOP_ERR_INVALID, "%s: null counts", who);
+  KPOP_HIP(hipMemsetAsync(d_counts, 0, 12, st));
+  const uint32_t r1 = rs->r1;
+  if (r1 == 0) return KPOP_OK;
+  if (!d_labels) KPOP_FAIL(KPOP_ERR_INVALID, "%s: null labels", who);
+  const DbShape s = dbscan_shape(r1);
+  const DbWork f = dbscan_carve(d_work, r1);
+  const uint32_t need = min_pts - 1;
+  const bool tiles = eps >= 0.0;  // (no distance is negative: below zero every degree is 1)
+  const double *a = rs->rows;
+  if (tiles && rs->normalize) {
+    KPOP_TRY(rs->prepared(st));
+    KPOP_TRY(rs->divided(st, &a));
+  }
+  KPOP_HIP(hipMemsetAsync(f.cnt, 0, f.clear_bytes, st));
+  KPOP_HIP(hipMemsetAsync(f.best_k, 0xFF, f.fill_bytes, st));
+  if (tiles) KPOP_TRY(dbscan_pass(rs, a, eps, need, s, f, d_labels, 0, st));
+  const dim3 rows_grid(std::min(div_up(r1, 256), 4096u));
+  dbscan_classify_kernel<<<rows_grid, dim3(256), 0, st>>>(f.cnt, r1, need, d_labels, d_degree, d_counts);
+  KPOP_LAUNCH_CHECK();
+  if (tiles) {
+    KPOP_TRY(dbscan_pass(rs, a, eps, need, s, f, d_labels, 1, st));
+    KPOP_TRY(dbscan_pass(rs, a, eps, need, s, f, d_labels, 2, st));
+  }
+  dbscan_finalize_kernel<<<rows_grid, dim3(256), 0, st>>>(f.cnt, r1, need, f.best_c, d_labels, d_core_of, d_counts);
+  KPOP_LAUNCH_CHECK();
+  return KPOP_OK;
+}
+
+}  // namespace kpop
+
+using namespace kpop;
+
+extern "C" uint64_t kpop_dev_dbscan_workspace_bytes(const kpop_refset *rs) {
+  if (!rs) return 0;
+  return dbscan_carve(nullptr, rs->r1).bytes;
+}
+
+extern "C" int kpop_dev_dbscan(kpop_refset *rs, double eps, uint32_t min_pts, void *d_work, uint32_t *d_labels, uint32_t *d_core_of, uint32_t *d_degree,
+                               uint32_t *d_counts, void *stream) {
+  const char *who = "kpop_dev_dbscan";
+  KPOP_TRY(refset_check_handle(rs, who));
+  if (!d_work) KPOP_FAIL(KPOP_ERR_INVALID, "%s: null workspace", who);
+  return dbscan_dev(rs, eps, min_pts, d_work, d_labels, d_core_of, d_degree, d_counts, as_stream(stream), who);
+}
+
+extern "C" int kpop_dbscan(kpop_refset *rs, double eps, uint32_t min_pts, uint32_t *labels, uint32_t *core_of, uint32_t *degree, uint32_t *counts) {
+  const char *who = "kpop_dbscan";
+  KPOP_TRY(refset_check_handle(rs, who));
+  ArenaScope scratch;
+  if (eps != eps) KPOP_FAIL(KPOP_ERR_INVALID, "%s: eps is not a number", who);
+  if (min_pts == 0) KPOP_FAIL(KPOP_ERR_INVALID, "%s: min_pts is zero (a row counts itself: 1 makes every row a core row)", who);
+  if (!counts || (rs->r1 && !labels)) KPOP_FAIL(KPOP_ERR_INVALID, "%s: null argument", who);
+  counts[0] = counts[1] = counts[2] = 0;
+  const uint32_t r1 = rs->r1;
+  if (r1 == 0) return KPOP_OK;
+  hipStream_t st = nullptr;
+  DevBuf work, dl, dc, dd, dn;
+  KPOP_TRY(work.alloc(dbscan_carve(nullptr, r1).bytes));
+  KPOP_TRY(dl.alloc((uint64_t)r1 * 4));
+  if (core_of) KPOP_TRY(dc.alloc((uint64_t)r1 * 4));
+  if (degree) KPOP_TRY(dd.alloc((uint64_t)r1 * 4));
+  KPOP_TRY(dn.alloc(256));
+  KPOP_TRY(dbscan_dev(rs, eps, min_pts, work.p, dl.as<uint32_t>(), core_of ? dc.as<uint32_t>() : nullptr, degree ? dd.as<uint32_t>() : nullptr,
+                      dn.as<uint32_t>(), st, who));
+  KPOP_HIP(hipMemcpyAsync(labels, dl.p, (uint64_t)r1 * 4, hipMemcpyDeviceToHost, st));
+  if (core_of) KPOP_HIP(hipMemcpyAsync(core_of, dc.p, (uint64_t)r1 * 4, hipMemcpyDeviceToHost, st));
+  if (degree) KPOP_HIP(hipMemcpyAsync(degree, dd.p, (uint64_t)r1 * 4, hipMemcpyDeviceToHost, st));
+  KPOP_HIP(hipMemcpyAsync(counts, dn.p, 12, hipMemcpyDeviceToHost, st));
+  KPOP_HIP(hipStreamSynchronize(st));
+  return KPOP_OK;
+}
+
+extern "C" int kpop_distance_dbscan(const double *m, uint32_t rows, uint32_t n_dims, const double *metric, int kind, double p, int normalize, double eps,
+                                    uint32_t min_pts, uint32_t *labels, uint32_t *core_of, uint32_t *degree, uint32_t *counts) {
+  kpop_refset *rs = nullptr;
+  KPOP_TRY(kpop_refset_create(m, rows, n_dims, metric, kind, p, normalize, 0, &rs));
+  const int rc = kpop_dbscan(rs, eps, min_pts, labels, core_of, degree, counts);
+  const int rc_free = kpop_refset_free(rs);
+  return rc ? rc : rc_free;
+}
