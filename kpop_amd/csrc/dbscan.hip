@@ -9,23 +9,23 @@
 //   index), labels[i] = labels[core_of[i]], and it joins nothing; every other row is NOISE (labels = core_of = KPOP_NOISE).
 //   Integer sums, canonical labels, the minimum of a strict total order: a function of the distances alone, the same bits on every run.
 //
-// Neither the matrix nor a neighbour list is formed, nothing is read back, nothing synchronises.  Three launches walk
-// clusters_tile_kernel's grid (the folded upper triangle, both tile shapes) with its loop (pair_tile.h) and its compare; the second
-// and the third compute only the tiles that a bitmap of the launch before names:
+// Neither the matrix nor a neighbour list is formed, nothing is read back, nothing synchronises.  Three launches walk the folded
+// upper triangle (tri_tile.h, both tile shapes) with the tile's distances and the compare of self_tile.h (the loop pair_tile.h's);
+// the second and the third compute only the tiles that a bitmap of the launch before names:
 //   dbscan_degree_kernel    a hit (i, j) counts for both ends: the counts of a tile's w + TJ nodes are summed in registers, across
 //                           lanes with shuffles and across the wavefronts in LDS, and one global atomicAdd a node whose count is not
 //                           zero leaves the tile -- a dense lineage costs LDS traffic, not a global atomic a hit.  A tile with a hit
 //                           sets its bit in the tile bitmap
-//   dbscan_classify_kernel  degree[i] = 1 + counter, parent[i] = i (the forest lives in the labels, as in clusters.hip), counts[1]
+//   dbscan_classify_kernel  degree[i] = 1 + counter, parent[i] = i (the forest lives in the labels), counts[1]
 //   dbscan_union_kernel     a block whose tile bit is clear returns before it loads anything, and so does one whose nodes hold no
 //                           core row.  A hit between two core rows goes into the tile's forest in LDS, then one global union a node
-//                           (union_find.h); a row that is not core is never hooked.  A hit with ONE core end is a border row's: the
+//                           (tile_forest_unite, self_tile.h); a row that is not core is never hooked.  A hit with ONE core end is a border row's: the
 //                           least distance key of a node -- registers, shuffles -- goes into best_k[row] by one 64-bit atomicMin a
 //                           wavefront and node, and the tile sets its bit in the second bitmap
 //   dbscan_border_kernel    the tiles of the second bitmap, the same arithmetic, the same bits: among a border row's hits whose key
 //                           IS best_k[row], the least core row index goes into best_c[row] by a 32-bit atomicMin.  (key, then index:
 //                           the least under (d, index), with two integer minima and no 96-bit atomic)
-//   dbscan_finalize_kernel  a core row: its root (clusters_flatten_kernel's finds) and the count of the roots; any other row:
+//   dbscan_finalize_kernel  a core row: its root (uf_settle, union_find.h) and the count of the roots; any other row:
 //                           best_c[row] and that core row's root, or KPOP_NOISE, and the count of the noise
 // On a sparse graph the second launch costs its share of tiles with a hit and the third next to nothing: this is the point of the
 // bitmaps.  eps < 0: no tile kernel runs (every degree is 1).  No known_rows: a new row can turn old rows that were not core into core
@@ -34,10 +34,8 @@
 
 #include "common.h"
 #include "distance_routes.h"
-#include "pair_tile.h"
-#include "refset.h"
-#include "space_ops.h"
-#include "union_find.h"
+#include "refset_call.h"
+#include "self_tile.h"
 
 namespace kpop {
 
@@ -45,119 +43,46 @@ constexpr int kDbMaxW = 64, kDbMaxTJ = 256;
 constexpr uint64_t kDbNone = ~0ull;         // (no key: distance_key maps only a NaN's bits there, and a NaN is never a key)
 constexpr uint32_t kDbNoise = 0xFFFFFFFFu;  // KPOP_NOISE; best_k and best_c start as all ones: one memset
 
-// the two shapes of clusters_tiles (clusters.hip): 32 columns x 256 rows, a thread 4 x 8, for a long set; 64 x 64, a thread 4 x 4,
-// below.  Either way n_cg n_rg = 256: every thread of a workgroup holds pairs.  (The choice moves no bit.)
-struct DbShape {
-  bool big;
-  uint32_t w, n_cg, n_rg, TJ, kf, n_rt, n_ct;
-};
-
-static DbShape dbscan_shape(uint32_t r1) {
-  DbShape s;
-  s.big = r1 >= 65536;
-  s.w = s.big ? 32 : 64;
-  s.n_cg = s.w / 4;
-  s.n_rg = 256 / s.n_cg;
-  s.TJ = (s.big ? 8 : 4) * s.n_rg;
-  s.kf = s.TJ / s.w;
-  s.n_rt = div_up(std::max(r1, 1u), s.TJ);
-  s.n_ct = s.n_rt * s.kf;  // the column tiles of a line of a bitmap
-  return s;
-}
-
-// cnt[r1]: the hits of a row (degree - 1); hit_map, mixed_map: a bit a tile, line by of n_ct bits -- a tile with a hit, a tile with
-// a hit that has one core end; these three are cleared by one memset.  best_k[r1], best_c[r1]: the least key of a row's hits with
-// one core end, and the least core row index among the hits of that key; filled with ones by one memset
+// cnt[r1]: the hits of a row (degree - 1); hit_map, mixed_map: a bit a tile, line by (of n_rt, the set's row tiles) of n_rt kf bits --
+// a tile with a hit, a tile with a hit that has one core end; these three are cleared by one memset.  best_k[r1], best_c[r1]: the
+// least key of a row's hits with one core end, and the least core row index among the hits of that key; filled with ones by one memset
 struct DbWork {
   uint32_t *cnt, *hit_map, *mixed_map, *best_c;
   uint64_t *best_k;
   uint64_t clear_bytes, fill_bytes, bytes;
+  uint32_t n_rt;
 };
 
 static DbWork dbscan_carve(void *base, uint32_t r1) {
   const uint64_t n = std::max(r1, 1u);
-  const DbShape s = dbscan_shape(r1);
-  char *c = reinterpret_cast<char *>(base);
-  uint64_t off = 0;
-  auto take = [&](uint64_t b) {
-    char *q = c + off;
-    off += (b + 255) & ~255ull;
-    return q;
-  };
-  const uint64_t map_bytes = ((uint64_t)s.n_rt * s.n_ct + 31) / 32 * 4;
+  const SelfShape s = self_shape(r1);
+  Carver c(base);
   DbWork f;
-  f.cnt = reinterpret_cast<uint32_t *>(take(n * 4));
-  f.hit_map = reinterpret_cast<uint32_t *>(take(map_bytes));
-  f.mixed_map = reinterpret_cast<uint32_t *>(take(map_bytes));
-  f.clear_bytes = off;
-  f.best_k = reinterpret_cast<uint64_t *>(take(n * 8));
-  f.best_c = reinterpret_cast<uint32_t *>(take(n * 4));
-  f.fill_bytes = off - f.clear_bytes;
-  f.bytes = off;
+  f.n_rt = div_up(n, s.TJ);
+  const uint64_t map_bytes = ((uint64_t)f.n_rt * f.n_rt * s.kf + 31) / 32 * 4;
+  f.cnt = c.take<uint32_t>(n * 4);
+  f.hit_map = c.take<uint32_t>(map_bytes);
+  f.mixed_map = c.take<uint32_t>(map_bytes);
+  f.clear_bytes = c.off;
+  f.best_k = c.take<uint64_t>(n * 8);
+  f.best_c = c.take<uint32_t>(n * 4);
+  f.fill_bytes = c.off - f.clear_bytes;
+  f.bytes = c.off;
   return f;
 }
 
-// which tile of the folded upper triangle a block of clusters_tile_kernel's grid owns (by_first = 0: every row is new)
-struct DbTile {
-  uint32_t bx, by, i0, i1, j0, j1;
-  bool live;
-};
-
-__device__ __forceinline__ DbTile dbscan_tile(uint32_t w, uint32_t TJ, uint32_t r1, uint32_t kf, uint32_t n_rt, uint32_t ybase) {
-  DbTile t;
-  t.live = false;
-  const uint32_t y = ybase + blockIdx.y;
-  const uint32_t by_lo = y, by_hi = n_rt - 1 - y;
-  const uint32_t n_lo = (by_lo + 1) * kf;
-  t.bx = blockIdx.x;
-  t.by = by_lo;
-  if (t.bx >= n_lo) {
-    if (by_hi == by_lo) return t;  // (the middle line of an odd number: once)
-    t.bx -= n_lo;
-    t.by = by_hi;
-  }
-  t.i0 = t.bx * w;
-  t.j0 = t.by * TJ;
-  t.j1 = min(r1, t.j0 + TJ);
-  if (t.i0 + 1 >= t.j1) return t;  // (the last row tile is ragged: no column below its last row)
-  t.i1 = min(r1, t.i0 + w);
-  t.live = true;
-  return t;
-}
-
-__device__ __forceinline__ bool dbscan_tile_bit(const uint32_t *__restrict__ map, const DbTile &t, uint32_t n_ct) {
+__device__ __forceinline__ bool dbscan_tile_bit(const uint32_t *__restrict__ map, const TriTile &t, uint32_t n_ct) {
   const uint64_t bit = (uint64_t)t.by * n_ct + t.bx;
   return (map[bit >> 5] >> (bit & 31)) & 1u;
 }
 
-__device__ __forceinline__ void dbscan_set_tile_bit(uint32_t *__restrict__ map, const DbTile &t, uint32_t n_ct) {
+__device__ __forceinline__ void dbscan_set_tile_bit(uint32_t *__restrict__ map, const TriTile &t, uint32_t n_ct) {
   const uint64_t bit = (uint64_t)t.by * n_ct + t.bx;
   atomicOr(map + (bit >> 5), 1u << (bit & 31));
 }
 
-// the distances of the tile's pairs, a thread 4 columns x TY rows: clusters_tile_kernel's loop and scaling
-template <int KIND, int TY>
-__device__ __forceinline__ void dbscan_tile_distances(double (&acc)[TY][4], double (*As)[kDbMaxW + 2], double (*Bs)[kDbMaxTJ + 2], double *s_metric,
-                                                      const double *__restrict__ a, const DbTile &t, uint32_t n_dims, const double *__restrict__ metric,
-                                                      double p, uint32_t ti, uint32_t tj) {
-  pair_zero(acc);
-  PairStage<kDbMaxW, kDbMaxTJ> stage;
-  stage.load(a, t.i0, t.i1, a, t.j0, t.j1, n_dims, 0, n_dims);
-  for (uint32_t c0 = 0; c0 < n_dims; c0 += kPairDC) {
-    __syncthreads();
-    stage.store(As, Bs, s_metric, metric, c0, n_dims);
-    __syncthreads();
-    if (c0 + kPairDC < n_dims) stage.load(a, t.i0, t.i1, a, t.j0, t.j1, n_dims, c0 + kPairDC, n_dims);
-    pair_accumulate<KIND>(acc, As, Bs, s_metric, ti, tj, min((uint32_t)kPairDC, n_dims - c0), p);
-  }
-#pragma unroll
-  for (int yy = 0; yy < TY; ++yy)
-#pragma unroll
-    for (int x = 0; x < 4; ++x) acc[yy][x] = scale_distance<KIND>(acc[yy][x], p);
-}
-
 // the tile's core flags, the columns first, then the rows (a node beyond the set is not core) -> does the tile hold a core row
-__device__ __forceinline__ bool dbscan_stage_core(uint8_t *s_core, const DbTile &t, uint32_t w, uint32_t TJ, uint32_t r1, const uint32_t *__restrict__ cnt,
+__device__ __forceinline__ bool dbscan_stage_core(uint8_t *s_core, const TriTile &t, uint32_t w, uint32_t TJ, uint32_t r1, const uint32_t *__restrict__ cnt,
                                                   uint32_t need) {
   bool any = false;
   for (uint32_t n = threadIdx.x; n < w + TJ; n += 256) {
@@ -175,26 +100,25 @@ struct DbHits {
 };
 
 template <int TY>
-__device__ __forceinline__ DbHits dbscan_hits(const double (&acc)[TY][4], const DbTile &t, uint32_t w, uint32_t ti, uint32_t tj, double eps,
+__device__ __forceinline__ DbHits dbscan_hits(const double (&acc)[TY][4], const TriTile &t, uint32_t w, uint32_t ti, uint32_t tj, double eps,
                                               const uint8_t *s_core) {
+  const uint32_t hits = self_hit_mask<TY>(acc, t, ti, tj, eps);
   uint32_t both = 0, mixed = 0;
 #pragma unroll
   for (int yy = 0; yy < TY; ++yy)
 #pragma unroll
-    for (int x = 0; x < 4; ++x) {
-      const uint32_t i = t.i0 + ti + x, j = t.j0 + tj + yy;
-      // compare where clusters_tile_kernel compares (a NaN compares false); only i < j
-      if (j < t.j1 && i < t.i1 && i < j && acc[yy][x] <= eps) {
+    for (int x = 0; x < 4; ++x)
+      if (hits & (1u << (yy * 4 + x))) {
         const bool ci = s_core[ti + x], cj = s_core[w + tj + yy];
         if (ci && cj) both |= 1u << (yy * 4 + x);
         else if (ci != cj) mixed |= 1u << (yy * 4 + x);
       }
-    }
   return DbHits{both, mixed};
 }
 
 // a: the set's rows as the chain reads them (divided by their norms when the set normalises), both operands.  The grid, the tiles
-// and the thread's pairs are clusters_tile_kernel's.  cnt[i] += the hits of row i in this tile, from either side
+// and the thread's pairs are tri_tile.h's: every row is new (by_first = 0, all n_rt row tiles), and n_cg n_rg = 256 in both shapes --
+// every thread of the workgroup holds pairs.  cnt[i] += the hits of row i in this tile, from either side
 template <int KIND, int TY>
 __global__ __launch_bounds__(256, 1) void dbscan_degree_kernel(const double *__restrict__ a, uint32_t w, uint32_t r1, uint32_t n_dims,
                                                                const double *__restrict__ metric, double p, double eps, uint32_t n_cg, uint32_t n_rg,
@@ -205,36 +129,26 @@ __global__ __launch_bounds__(256, 1) void dbscan_degree_kernel(const double *__r
   __shared__ double s_metric[kPairDC];
   __shared__ uint32_t s_cnt[kDbMaxW + kDbMaxTJ];  // the tile's counts: the columns first, then the rows
   const uint32_t TJ = TY * n_rg;
-  const DbTile t = dbscan_tile(w, TJ, r1, kf, n_rt, ybase);
+  const TriTile t = tri_tile(blockIdx.x, ybase + blockIdx.y, w, TJ, kf, 0, n_rt, r1);
   if (!t.live) return;
   const uint32_t cg = threadIdx.x % n_cg, rg = threadIdx.x / n_cg;
   const uint32_t ti = cg * 4, tj = rg * TY;
   for (uint32_t n = threadIdx.x; n < w + TJ; n += 256) s_cnt[n] = 0;  // (the loop's barriers come before anybody adds)
   double acc[TY][4];
-  dbscan_tile_distances<KIND, TY>(acc, As, Bs, s_metric, a, t, n_dims, metric, p, ti, tj);
-  // the epilogue: compare where clusters_tile_kernel compares (a NaN compares false); only i < j
-  uint32_t mask = 0;
-#pragma unroll
-  for (int yy = 0; yy < TY; ++yy)
-#pragma unroll
-    for (int x = 0; x < 4; ++x) {
-      const uint32_t i = t.i0 + ti + x, j = t.j0 + tj + yy;
-      if (j < t.j1 && i < t.i1 && i < j && acc[yy][x] <= eps) mask |= 1u << (yy * 4 + x);
-    }
+  pair_tile_distances<KIND, TY, kDbMaxW, kDbMaxTJ>(acc, As, Bs, s_metric, a, t.i0, t.i1, a, t.j0, t.j1, n_dims, metric, p, ti, tj, true);
+  const uint32_t mask = self_hit_mask<TY>(acc, t, ti, tj, eps);
   if (!__syncthreads_or(mask != 0)) return;  // most tiles of a sparse graph
-  // a row's n_cg threads are neighbouring lanes of one wavefront, and nobody else holds that row: a sum over them and a plain store
+  const auto sum = [](uint32_t x, uint32_t y) { return x + y; };
+  // nobody else holds the row: the sum over its lanes and a plain store
 #pragma unroll
   for (int yy = 0; yy < TY; ++yy) {
-    uint32_t c = __popc((mask >> (4 * yy)) & 0xFu);
-    for (uint32_t o = n_cg >> 1; o > 0; o >>= 1) c += (uint32_t)__shfl_xor((int)c, (int)o, 64);
+    const uint32_t c = reduce_row_lanes((uint32_t)__popc((mask >> (4 * yy)) & 0xFu), n_cg, sum);
     if (cg == 0) s_cnt[w + tj + yy] = c;
   }
-  // a column's threads are the lanes of a wavefront that share cg, in every wavefront: a sum over those lanes, then one LDS add a
-  // wavefront and column
+  // a column's sum over a wavefront's lanes, then one LDS add a wavefront and column
 #pragma unroll
   for (int x = 0; x < 4; ++x) {
-    uint32_t c = __popc(mask & (0x11111111u << x));
-    for (uint32_t o = n_cg; o < 64; o <<= 1) c += (uint32_t)__shfl_xor((int)c, (int)o, 64);
+    const uint32_t c = reduce_column_lanes((uint32_t)__popc(mask & (0x11111111u << x)), n_cg, sum);
     if ((threadIdx.x & 63) < n_cg && c) atomicAdd(&s_cnt[ti + x], c);
   }
   __syncthreads();
@@ -265,7 +179,7 @@ __global__ __launch_bounds__(256) void dbscan_classify_kernel(const uint32_t *__
 }
 
 // the grid, the tiles and the arithmetic of dbscan_degree_kernel, in the tiles where it found a hit.  A hit between two core rows
-// goes where clusters_tile_kernel's hits go; a hit with one core end gives the end that is not core a key
+// goes into the tile's forest (tile_forest_unite); a hit with one core end gives the end that is not core a key
 template <int KIND, int TY>
 __global__ __launch_bounds__(256, 1) void dbscan_union_kernel(const double *__restrict__ a, uint32_t w, uint32_t r1, uint32_t n_dims,
                                                               const double *__restrict__ metric, double p, double eps, uint32_t n_cg, uint32_t n_rg,
@@ -278,7 +192,7 @@ __global__ __launch_bounds__(256, 1) void dbscan_union_kernel(const double *__re
   __shared__ uint32_t s_par[kDbMaxW + kDbMaxTJ];  // the tile's forest: the columns first, then the rows
   __shared__ uint8_t s_core[kDbMaxW + kDbMaxTJ];
   const uint32_t TJ = TY * n_rg;
-  const DbTile t = dbscan_tile(w, TJ, r1, kf, n_rt, ybase);
+  const TriTile t = tri_tile(blockIdx.x, ybase + blockIdx.y, w, TJ, kf, 0, n_rt, r1);
   if (!t.live) return;
   if (!dbscan_tile_bit(hit_map, t, n_rt * kf)) return;  // no hit in this tile: most tiles of a sparse graph, and nothing was loaded
   for (uint32_t n = threadIdx.x; n < w + TJ; n += 256) s_par[n] = n;
@@ -286,19 +200,20 @@ __global__ __launch_bounds__(256, 1) void dbscan_union_kernel(const double *__re
   const uint32_t cg = threadIdx.x % n_cg, rg = threadIdx.x / n_cg;
   const uint32_t ti = cg * 4, tj = rg * TY;
   double acc[TY][4];
-  dbscan_tile_distances<KIND, TY>(acc, As, Bs, s_metric, a, t, n_dims, metric, p, ti, tj);
+  pair_tile_distances<KIND, TY, kDbMaxW, kDbMaxTJ>(acc, As, Bs, s_metric, a, t.i0, t.i1, a, t.j0, t.j1, n_dims, metric, p, ti, tj, true);
   const DbHits hits = dbscan_hits<TY>(acc, t, w, ti, tj, eps, s_core);
   const uint32_t mask = hits.both, mixed = hits.mixed;
   if (__syncthreads_or(mixed != 0)) {
-    // the end of a mixed hit that is not core: the row when the column is core, otherwise the column.  A row's threads are n_cg
-    // neighbouring lanes, a column's the lanes of a wavefront that share cg: the least key over them, one atomicMin a wavefront and node
+    // the end of a mixed hit that is not core: the row when the column is core, otherwise the column.  The least key over the
+    // node's lanes, one atomicMin a wavefront and node
+    const auto least = [](uint64_t x, uint64_t y) { return min(x, y); };
 #pragma unroll
     for (int yy = 0; yy < TY; ++yy) {
       uint64_t k = kDbNone;
 #pragma unroll
       for (int x = 0; x < 4; ++x)
         if ((mixed & (1u << (yy * 4 + x))) && s_core[ti + x]) k = min(k, distance_key(acc[yy][x]));
-      for (uint32_t o = n_cg >> 1; o > 0; o >>= 1) k = min(k, (uint64_t)__shfl_xor((unsigned long long)k, (int)o, 64));
+      k = reduce_row_lanes(k, n_cg, least);
       if (cg == 0 && k != kDbNone) atomicMin(reinterpret_cast<unsigned long long *>(best_k + t.j0 + tj + yy), (unsigned long long)k);
     }
 #pragma unroll
@@ -307,26 +222,13 @@ __global__ __launch_bounds__(256, 1) void dbscan_union_kernel(const double *__re
 #pragma unroll
       for (int yy = 0; yy < TY; ++yy)
         if ((mixed & (1u << (yy * 4 + x))) && !s_core[ti + x]) k = min(k, distance_key(acc[yy][x]));
-      for (uint32_t o = n_cg; o < 64; o <<= 1) k = min(k, (uint64_t)__shfl_xor((unsigned long long)k, (int)o, 64));
+      k = reduce_column_lanes(k, n_cg, least);
       if ((threadIdx.x & 63) < n_cg && k != kDbNone) atomicMin(reinterpret_cast<unsigned long long *>(best_k + t.i0 + ti + x), (unsigned long long)k);
     }
     if (threadIdx.x == 0) dbscan_set_tile_bit(mixed_map, t, n_rt * kf);
   }
   if (!__syncthreads_or(mask != 0)) return;
-  // the tile's own forest, in LDS: whatever the number of hits, what leaves the tile is one union per node
-  constexpr int WG = __HIP_MEMORY_SCOPE_WORKGROUP, DEV = __HIP_MEMORY_SCOPE_AGENT;
-  if (mask) {
-#pragma unroll
-    for (int yy = 0; yy < TY; ++yy)
-#pragma unroll
-      for (int x = 0; x < 4; ++x)
-        if (mask & (1u << (yy * 4 + x))) uf_unite<WG>(s_par, ti + x, w + tj + yy);
-  }
-  __syncthreads();
-  for (uint32_t n = threadIdx.x; n < w + TJ; n += 256) {
-    const uint32_t root = uf_find_readonly<WG>(s_par, n);
-    if (root != n) uf_unite<DEV>(parent, n < w ? t.i0 + n : t.j0 + (n - w), root < w ? t.i0 + root : t.j0 + (root - w));
-  }
+  tile_forest_unite<TY>(mask, s_par, t, w, TJ, ti, tj, parent);
 }
 
 // the same grid a third time, in the tiles where dbscan_union_kernel found a hit with one core end; the same arithmetic gives the
@@ -342,16 +244,17 @@ __global__ __launch_bounds__(256, 1) void dbscan_border_kernel(const double *__r
   __shared__ double s_metric[kPairDC];
   __shared__ uint8_t s_core[kDbMaxW + kDbMaxTJ];
   const uint32_t TJ = TY * n_rg;
-  const DbTile t = dbscan_tile(w, TJ, r1, kf, n_rt, ybase);
+  const TriTile t = tri_tile(blockIdx.x, ybase + blockIdx.y, w, TJ, kf, 0, n_rt, r1);
   if (!t.live) return;
   if (!dbscan_tile_bit(mixed_map, t, n_rt * kf)) return;  // no border row's hit in this tile: nothing is loaded
   dbscan_stage_core(s_core, t, w, TJ, r1, cnt, need);
   const uint32_t cg = threadIdx.x % n_cg, rg = threadIdx.x / n_cg;
   const uint32_t ti = cg * 4, tj = rg * TY;
   double acc[TY][4];
-  dbscan_tile_distances<KIND, TY>(acc, As, Bs, s_metric, a, t, n_dims, metric, p, ti, tj);
+  pair_tile_distances<KIND, TY, kDbMaxW, kDbMaxTJ>(acc, As, Bs, s_metric, a, t.i0, t.i1, a, t.j0, t.j1, n_dims, metric, p, ti, tj, true);
   const uint32_t mixed = dbscan_hits<TY>(acc, t, w, ti, tj, eps, s_core).mixed;
   if (!__syncthreads_or(mixed != 0)) return;
+  const auto least = [](uint32_t x, uint32_t y) { return min(x, y); };
   // rows that are not core against core columns: the least column index among the hits of the row's key
 #pragma unroll
   for (int yy = 0; yy < TY; ++yy) {
@@ -363,7 +266,7 @@ __global__ __launch_bounds__(256, 1) void dbscan_border_kernel(const double *__r
       for (int x = 3; x >= 0; --x)
         if ((m & (1u << x)) && s_core[ti + x] && distance_key(acc[yy][x]) == k) c = t.i0 + ti + x;
     }
-    for (uint32_t o = n_cg >> 1; o > 0; o >>= 1) c = min(c, (uint32_t)__shfl_xor((int)c, (int)o, 64));
+    c = reduce_row_lanes(c, n_cg, least);
     if (cg == 0 && c != kDbNoise) atomicMin(best_c + t.j0 + tj + yy, c);
   }
   // columns that are not core against core rows
@@ -376,14 +279,13 @@ __global__ __launch_bounds__(256, 1) void dbscan_border_kernel(const double *__r
       for (int yy = TY - 1; yy >= 0; --yy)
         if ((mixed & (1u << (yy * 4 + x))) && distance_key(acc[yy][x]) == k) c = t.j0 + tj + yy;
     }
-    for (uint32_t o = n_cg; o < 64; o <<= 1) c = min(c, (uint32_t)__shfl_xor((int)c, (int)o, 64));
+    c = reduce_column_lanes(c, n_cg, least);
     if ((threadIdx.x & 63) < n_cg && c != kDbNoise) atomicMin(best_c + t.i0 + ti + x, c);
   }
 }
 
-// after everything else.  A core row: its root, as in clusters_flatten_kernel (a root is a row whose word is its own index: no store
-// here changes that, and a word on somebody's path is that row's ancestor before the store and after it; only core rows lie on a
-// path).  Any other row: its core row's root, or the noise.  counts[0]: the roots; counts[2]: the noise
+// after everything else.  A core row: its root (uf_settle; only core rows lie on a path).  Any other row: its core row's root, or the
+// noise.  counts[0]: the roots; counts[2]: the noise
 __global__ __launch_bounds__(256) void dbscan_finalize_kernel(const uint32_t *__restrict__ cnt, uint32_t r1, uint32_t need, const uint32_t *__restrict__ best_c,
                                                               uint32_t *parent, uint32_t *__restrict__ core_of, uint32_t *__restrict__ counts) {
   __shared__ uint32_t s_roots, s_noise;
@@ -393,9 +295,7 @@ __global__ __launch_bounds__(256) void dbscan_finalize_kernel(const uint32_t *__
   uint32_t roots = 0, noise = 0;
   for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < r1; i += (uint64_t)gridDim.x * 256) {
     if (cnt[i] >= need) {
-      const uint32_t root = uf_find_readonly<DEV>(parent, (uint32_t)i);
-      if (root == (uint32_t)i) ++roots;
-      else __hip_atomic_store(parent + i, root, __ATOMIC_RELAXED, DEV);
+      if (uf_settle<DEV>(parent, (uint32_t)i) == (uint32_t)i) ++roots;
       if (core_of) core_of[i] = (uint32_t)i;
       continue;
     }
@@ -413,76 +313,50 @@ __global__ __launch_bounds__(256) void dbscan_finalize_kernel(const uint32_t *__
   if (threadIdx.x == 0 && s_noise) atomicAdd(counts + 2, s_noise);
 }
 
-// one of the three launches over the triangle's grid: pass 0 the degrees, 1 the unions and the border keys, 2 the border indices
-template <int KIND>
-static int dbscan_tiles(const double *a, uint32_t r1, uint32_t n_dims, const double *metric, double p, double eps, uint32_t need, const DbShape &s,
-                        const DbWork &f, uint32_t *parent, int pass, hipStream_t st) {
-  const uint32_t lines = (s.n_rt + 1) / 2;
-  const uint32_t gx = (s.n_rt + 1) * s.kf;  // the tiles of a row tile and of its partner from the end
-  for (uint32_t ybase = 0; ybase < lines; ybase += 65535u) {
-    const dim3 grid(gx, std::min(65535u, lines - ybase));
-    if (pass == 0) {
-      if (s.big)
-        dbscan_degree_kernel<KIND, 8><<<grid, dim3(256), 0, st>>>(a, s.w, r1, n_dims, metric, p, eps, s.n_cg, s.n_rg, s.kf, s.n_rt, ybase, f.cnt, f.hit_map);
-      else
-        dbscan_degree_kernel<KIND, 4><<<grid, dim3(256), 0, st>>>(a, s.w, r1, n_dims, metric, p, eps, s.n_cg, s.n_rg, s.kf, s.n_rt, ybase, f.cnt, f.hit_map);
-    } else if (pass == 1) {
-      if (s.big)
-        dbscan_union_kernel<KIND, 8><<<grid, dim3(256), 0, st>>>(a, s.w, r1, n_dims, metric, p, eps, s.n_cg, s.n_rg, s.kf, s.n_rt, ybase, f.cnt, need, f.hit_map,
-                                                                 f.mixed_map, parent, f.best_k);
-      else
-        dbscan_union_kernel<KIND, 4><<<grid, dim3(256), 0, st>>>(a, s.w, r1, n_dims, metric, p, eps, s.n_cg, s.n_rg, s.kf, s.n_rt, ybase, f.cnt, need, f.hit_map,
-                                                                 f.mixed_map, parent, f.best_k);
-    } else {
-      if (s.big)
-        dbscan_border_kernel<KIND, 8><<<grid, dim3(256), 0, st>>>(a, s.w, r1, n_dims, metric, p, eps, s.n_cg, s.n_rg, s.kf, s.n_rt, ybase, f.cnt, need, f.mixed_map,
-                                                                  f.best_k, f.best_c);
-      else
-        dbscan_border_kernel<KIND, 4><<<grid, dim3(256), 0, st>>>(a, s.w, r1, n_dims, metric, p, eps, s.n_cg, s.n_rg, s.kf, s.n_rt, ybase, f.cnt, need, f.mixed_map,
-                                                                  f.best_k, f.best_c);
-    }
-    KPOP_LAUNCH_CHECK();
-  }
+static int dbscan_check(double eps, uint32_t min_pts, const char *who) {
+  if (eps != eps) KPOP_FAIL(KPOP_ERR_INVALID, "%s: eps is not a number", who);
+  if (min_pts == 0) KPOP_FAIL(KPOP_ERR_INVALID, "%s: min_pts is zero (a row counts itself: 1 makes every row a core row)", who);
   return 0;
-}
-
-static int dbscan_pass(const kpop_refset *rs, const double *a, double eps, uint32_t need, const DbShape &s, const DbWork &f, uint32_t *parent, int pass,
-                       hipStream_t st) {
-  switch (rs->kind) {
-    case KPOP_EUCLIDEAN: return dbscan_tiles<KPOP_EUCLIDEAN>(a, rs->r1, rs->n_dims, rs->metric, rs->p, eps, need, s, f, parent, pass, st);
-    case KPOP_COSINE: return dbscan_tiles<KPOP_COSINE>(a, rs->r1, rs->n_dims, rs->metric, rs->p, eps, need, s, f, parent, pass, st);
-    default: return dbscan_tiles<KPOP_MINKOWSKI>(a, rs->r1, rs->n_dims, rs->metric, rs->p, eps, need, s, f, parent, pass, st);
-  }
 }
 
 // the body of both entry points: enqueues only
 static int dbscan_dev(kpop_refset *rs, double eps, uint32_t min_pts, void *d_work, uint32_t *d_labels, uint32_t *d_core_of, uint32_t *d_degree,
                       uint32_t *d_counts, hipStream_t st, const char *who) {
-  if (eps != eps) KPOP_FAIL(KPOP_ERR_INVALID, "%s: eps is not a number", who);
-  if (min_pts == 0) KPOP_FAIL(KPOP_ERR_INVALID, "%s: min_pts is zero (a row counts itself: 1 makes every row a core row)", who);
+  KPOP_TRY(dbscan_check(eps, min_pts, who));
   if (!d_counts) KPOP_FAIL(KPOP_ERR_INVALID, "%s: null counts", who);
   KPOP_HIP(hipMemsetAsync(d_counts, 0, 12, st));
-  const uint32_t r1 = rs->r1;
+  const uint32_t r1 = rs->r1, D = rs->n_dims;
   if (r1 == 0) return KPOP_OK;
   if (!d_labels) KPOP_FAIL(KPOP_ERR_INVALID, "%s: null labels", who);
-  const DbShape s = dbscan_shape(r1);
+  const SelfShape s = self_shape(r1);
   const DbWork f = dbscan_carve(d_work, r1);
   const uint32_t need = min_pts - 1;
   const bool tiles = eps >= 0.0;  // (no distance is negative: below zero every degree is 1)
   const double *a = rs->rows;
-  if (tiles && rs->normalize) {
-    KPOP_TRY(rs->prepared(st));
-    KPOP_TRY(rs->divided(st, &a));
-  }
+  if (tiles) KPOP_TRY(refset_chain_rows(rs, st, &a));
   KPOP_HIP(hipMemsetAsync(f.cnt, 0, f.clear_bytes, st));
   KPOP_HIP(hipMemsetAsync(f.best_k, 0xFF, f.fill_bytes, st));
-  if (tiles) KPOP_TRY(dbscan_pass(rs, a, eps, need, s, f, d_labels, 0, st));
+  // one of the three launches over the triangle's grid: launch(K, TY, grid, ybase), K and TY integral_constants
+  const auto pass = [&](auto launch) {
+    return by_kind(rs->kind, [&](auto K) { return self_triangle_launch(s, r1, 0, [&](auto TY, dim3 grid, uint32_t ybase) { launch(K, TY, grid, ybase); }); });
+  };
+  if (tiles)
+    KPOP_TRY(pass([&](auto K, auto TY, dim3 grid, uint32_t ybase) {
+      dbscan_degree_kernel<decltype(K)::value, decltype(TY)::value><<<grid, dim3(256), 0, st>>>(a, s.w, r1, D, rs->metric, rs->p, eps, s.n_cg, s.n_rg, s.kf, f.n_rt, ybase,
+                                                                                               f.cnt, f.hit_map);
+    }));
   const dim3 rows_grid(std::min(div_up(r1, 256), 4096u));
   dbscan_classify_kernel<<<rows_grid, dim3(256), 0, st>>>(f.cnt, r1, need, d_labels, d_degree, d_counts);
   KPOP_LAUNCH_CHECK();
   if (tiles) {
-    KPOP_TRY(dbscan_pass(rs, a, eps, need, s, f, d_labels, 1, st));
-    KPOP_TRY(dbscan_pass(rs, a, eps, need, s, f, d_labels, 2, st));
+    KPOP_TRY(pass([&](auto K, auto TY, dim3 grid, uint32_t ybase) {
+      dbscan_union_kernel<decltype(K)::value, decltype(TY)::value><<<grid, dim3(256), 0, st>>>(a, s.w, r1, D, rs->metric, rs->p, eps, s.n_cg, s.n_rg, s.kf, f.n_rt, ybase,
+                                                                                              f.cnt, need, f.hit_map, f.mixed_map, d_labels, f.best_k);
+    }));
+    KPOP_TRY(pass([&](auto K, auto TY, dim3 grid, uint32_t ybase) {
+      dbscan_border_kernel<decltype(K)::value, decltype(TY)::value><<<grid, dim3(256), 0, st>>>(a, s.w, r1, D, rs->metric, rs->p, eps, s.n_cg, s.n_rg, s.kf, f.n_rt, ybase,
+                                                                                               f.cnt, need, f.mixed_map, f.best_k, f.best_c);
+    }));
   }
   dbscan_finalize_kernel<<<rows_grid, dim3(256), 0, st>>>(f.cnt, r1, need, f.best_c, d_labels, d_core_of, d_counts);
   KPOP_LAUNCH_CHECK();
@@ -510,8 +384,7 @@ extern "C" int kpop_dbscan(kpop_refset *rs, double eps, uint32_t min_pts, uint32
   const char *who = "kpop_dbscan";
   KPOP_TRY(refset_check_handle(rs, who));
   ArenaScope scratch;
-  if (eps != eps) KPOP_FAIL(KPOP_ERR_INVALID, "%s: eps is not a number", who);
-  if (min_pts == 0) KPOP_FAIL(KPOP_ERR_INVALID, "%s: min_pts is zero (a row counts itself: 1 makes every row a core row)", who);
+  KPOP_TRY(dbscan_check(eps, min_pts, who));
   if (!counts || (rs->r1 && !labels)) KPOP_FAIL(KPOP_ERR_INVALID, "%s: null argument", who);
   counts[0] = counts[1] = counts[2] = 0;
   const uint32_t r1 = rs->r1;
@@ -535,9 +408,5 @@ extern "C" int kpop_dbscan(kpop_refset *rs, double eps, uint32_t min_pts, uint32
 
 extern "C" int kpop_distance_dbscan(const double *m, uint32_t rows, uint32_t n_dims, const double *metric, int kind, double p, int normalize, double eps,
                                     uint32_t min_pts, uint32_t *labels, uint32_t *core_of, uint32_t *degree, uint32_t *counts) {
-  kpop_refset *rs = nullptr;
-  KPOP_TRY(kpop_refset_create(m, rows, n_dims, metric, kind, p, normalize, 0, &rs));
-  const int rc = kpop_dbscan(rs, eps, min_pts, labels, core_of, degree, counts);
-  const int rc_free = kpop_refset_free(rs);
-  return rc ? rc : rc_free;
+  return with_temporary_refset(m, rows, n_dims, metric, kind, p, normalize, [&](kpop_refset *rs) { return kpop_dbscan(rs, eps, min_pts, labels, core_of, degree, counts); });
 }

@@ -1643,15 +1643,7 @@ static int check_kind(int kind, double p, const char *who) {
   return 0;
 }
 
-// the three kinds of every entry point: f(K), K an integral_constant of the kind
-template <class F>
-static int by_kind(int kind, F &&f) {
-  switch (kind) {
-    case KPOP_EUCLIDEAN: return f(std::integral_constant<int, KPOP_EUCLIDEAN>{});
-    case KPOP_COSINE: return f(std::integral_constant<int, KPOP_COSINE>{});
-    default: return f(std::integral_constant<int, KPOP_MINKOWSKI>{});
-  }
-}
+// (by_kind, the three kinds of every entry point: distance_routes.h)
 static int rowwise_by_kind(int kind, const DistOperands &o, const double *d_norms1, double *d_out) {
   return by_kind(kind, [&](auto K) { return rowwise_impl<decltype(K)::value>(o, d_out, d_norms1); });
 }

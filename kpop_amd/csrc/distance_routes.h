@@ -2,10 +2,22 @@
 // distance_mfma.hip and class_set.hip hold the kernels of their routes with the launchers, refset.hip / within.hip the resident set.  Every
 // declaration once, default arguments here and nowhere else; the defining files include it, so a signature that drifts does not compile.
 #pragma once
+#include <type_traits>
+
 #include "refset.h"
 #include "summary_types.h"
 
 namespace kpop {
+
+// the three kinds of every entry point: f(K), K an integral_constant of the kind
+template <class F>
+static int by_kind(int kind, F &&f) {
+  switch (kind) {
+    case KPOP_EUCLIDEAN: return f(std::integral_constant<int, KPOP_EUCLIDEAN>{});
+    case KPOP_COSINE: return f(std::integral_constant<int, KPOP_COSINE>{});
+    default: return f(std::integral_constant<int, KPOP_MINKOWSKI>{});
+  }
+}
 
 // the operands of a distance or a summary as the entry points take them (m1 x m2 rows of n_dims; work: the caller's workspace, needed when
 // normalising); prep: the first operand is a resident set (refset.h) that brings its own norms and copies, nullptr otherwise

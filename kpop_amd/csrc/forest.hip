@@ -8,11 +8,11 @@
 // Boruvka rounds over the implicit complete graph; neither a matrix nor a neighbour list is formed.  A round:
 //   forest_tile_labels_kernel  per tile of w rows: the label its rows share, or "mixed" -- a tile of the pass below whose rows and
 //                              columns all carry one label holds no foreign pair and is skipped (the late rounds are mostly that)
-//   forest_nearest_kernel      per row, the least allowed edge to a row of ANOTHER component.  The arithmetic of
-//                              clusters_tile_kernel (clusters.hip), the same loop (pair_tile.h): a pair's bits are the chain's.  A
+//   forest_nearest_kernel      per row, the least allowed edge to a row of ANOTHER component.  The self-join's tile shapes
+//                              (tri_tile.h) and the loop of pair_tile.h: a pair's bits are the chain's.  A
 //                              workgroup owns a strip of TJ rows and walks the column tiles of its segment of the set, columns
-//                              ascending; every thread keeps the best (key, column) of its TY rows in registers, the threads of a
-//                              row are neighbouring lanes and reduce with shuffles, one store a row and segment.  For a fixed row r
+//                              ascending; every thread keeps the best (key, column) of its TY rows in registers, the lanes of a
+//                              row reduce with shuffles (self_tile.h), one store a row and segment.  For a fixed row r
 //                              the order of the edges {r, c} is (d, c): whichever side of r the columns lie on, (min, max) ascends
 //                              with c.  Each pair is computed twice (once from either end); the key is 96 bits, which no atomic of
 //                              gfx950 holds, and this shape needs none
@@ -30,16 +30,15 @@
 // many; every kernel of a round returns at once when the word of the round before says that it added no edge -- nothing is read
 // back.  The host form reads the word and stops.  Edges arrive in any order; they are sorted on the device by (d, i, j): two stable
 // radix sorts (radix_sort.h), the pair first, the distance's key second.
-// The tile loop is pair_tile.h's, the union union_find.h's, the distance's key space_ops.h's.
+// The tile loop is pair_tile.h's, the shapes and the lanes' reduction self_tile.h's, the union union_find.h's, the distance's key
+// space_ops.h's.
 #include <algorithm>
 
 #include "common.h"
 #include "distance_routes.h"
-#include "pair_tile.h"
 #include "radix_sort.h"
-#include "refset.h"
-#include "space_ops.h"
-#include "union_find.h"
+#include "refset_call.h"
+#include "self_tile.h"
 
 namespace kpop {
 
@@ -82,7 +81,7 @@ __global__ __launch_bounds__(256) void forest_tile_labels_kernel(const uint32_t 
 
 // a: the set's rows as the chain reads them (divided by their norms when the set normalises), both operands.  Strip blockIdx.x:
 // rows j0 .. j0 + TJ, TJ = TY n_rg = kf w; segment blockIdx.y: the column tiles (w rows of the set each) t_begin .. t_end.  A thread
-// 4 columns x TY rows, the dimensions ascending in one thread, 16 at a time through LDS: clusters_tile_kernel's.  The next step's
+// 4 columns x TY rows, the dimensions ascending in one thread, 16 at a time through LDS (pair_tile.h).  The next step's
 // operands -- the tile's next 16 dimensions, or the first of the next tile that is not skipped -- are loaded under the arithmetic.
 template <int KIND, int TY>
 __global__ __launch_bounds__(256, 1) void forest_nearest_kernel(const double *__restrict__ a, uint32_t w, uint32_t r1, uint32_t n_dims,
@@ -137,7 +136,7 @@ __global__ __launch_bounds__(256, 1) void forest_nearest_kernel(const double *__
       if (more || t_next < t_end) stage.load(a, ni0, min(r1, ni0 + w), a, j0, j1, n_dims, more ? c0 + kPairDC : 0u, n_dims);
       if (worker) pair_accumulate<KIND>(acc, As, Bs, s_metric, ti, tj, min((uint32_t)kPairDC, n_dims - c0), p);
     }
-    // the epilogue: compare where clusters_tile_kernel compares (a NaN compares false: no edge), a row of another component only
+    // the epilogue: the scaled distance against the bound (a NaN compares false: no edge), a row of another component only
     // (which the row itself never is); columns ascend within the tile and from tile to tile, so that `below` alone keeps, among
     // equal keys, the least column
     if (worker) {
@@ -158,26 +157,14 @@ __global__ __launch_bounds__(256, 1) void forest_nearest_kernel(const double *__
     }
     t = t_next;
   }
-  // the n_cg threads of a row are neighbouring lanes of one wavefront (n_cg divides 64, a row group starts at a multiple of it)
-  for (uint32_t o = n_cg >> 1; o > 0; o >>= 1) {
+  // the least (key, column) over a row's lanes
 #pragma unroll
-    for (int yy = 0; yy < TY; ++yy) {
-      const uint64_t ok = (uint64_t)__shfl_xor((unsigned long long)best_k[yy], (int)o, 64);
-      const uint32_t oc = (uint32_t)__shfl_xor((int)best_c[yy], (int)o, 64);
-      if (ok < best_k[yy] || (ok == best_k[yy] && oc < best_c[yy])) {
-        best_k[yy] = ok;
-        best_c[yy] = oc;
-      }
-    }
-  }
-  if (worker && cg == 0) {
-#pragma unroll
-    for (int yy = 0; yy < TY; ++yy) {
-      const uint32_t j = j0 + tj + yy;
-      if (j < j1) {
-        part_k[(uint64_t)seg * r1 + j] = best_k[yy];
-        part_c[(uint64_t)seg * r1 + j] = best_c[yy];
-      }
+  for (int yy = 0; yy < TY; ++yy) {
+    const KeyAt best = reduce_row_lanes(KeyAt{best_k[yy], best_c[yy]}, n_cg, key_at_min);
+    const uint32_t j = j0 + tj + yy;
+    if (worker && cg == 0 && j < j1) {
+      part_k[(uint64_t)seg * r1 + j] = best.k;
+      part_c[(uint64_t)seg * r1 + j] = best.c;
     }
   }
 }
@@ -238,15 +225,12 @@ __global__ __launch_bounds__(256) void forest_link_kernel(const uint32_t *__rest
   }
 }
 
-// every row's root into par and lab, the components' words cleared for the next round.  A root is a row whose word is its own
-// index: no store here changes that, and a word on somebody's path is that row's ancestor before the store and after it
+// every row's root into par (uf_settle) and lab, the components' words cleared for the next round
 __global__ __launch_bounds__(256) void forest_flatten_kernel(uint32_t *par, uint32_t *__restrict__ lab, uint64_t *__restrict__ comp_k,
                                                              uint64_t *__restrict__ comp_e, uint32_t r1, const uint32_t *gate) {
   FOREST_GATE();
   for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < r1; i += (uint64_t)gridDim.x * 256) {
-    const uint32_t root = uf_find_readonly<__HIP_MEMORY_SCOPE_AGENT>(par, (uint32_t)i);
-    if (root != (uint32_t)i) __hip_atomic_store(par + i, root, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    lab[i] = root;
+    lab[i] = uf_settle<__HIP_MEMORY_SCOPE_AGENT>(par, (uint32_t)i);
     comp_k[i] = kFNone;
     comp_e[i] = kFNone;
   }
@@ -293,45 +277,36 @@ struct ForestWork {
 
 static ForestWork forest_carve(void *base, uint32_t r1) {
   const uint64_t n = std::max(r1, 1u), m = std::max(r1, 2u) - 1;
-  char *c = reinterpret_cast<char *>(base);
-  uint64_t off = 0;
-  auto take = [&](uint64_t b) {
-    char *q = c + off;
-    off += (b + 255) & ~255ull;
-    return q;
-  };
+  Carver c(base);
   ForestWork f;
-  f.words = reinterpret_cast<uint32_t *>(take(4 * (kFMaxRounds + 1)));  // what each round added
-  f.lab = reinterpret_cast<uint32_t *>(take(n * 4));
-  f.par = reinterpret_cast<uint32_t *>(take(n * 4));
-  f.tile_lab = reinterpret_cast<uint32_t *>(take(n * 4));
-  f.comp_k = reinterpret_cast<uint64_t *>(take(n * 8));
-  f.comp_e = reinterpret_cast<uint64_t *>(take(n * 8));
-  f.part_k = reinterpret_cast<uint64_t *>(take(n * 8 * kFMaxSeg));
-  f.part_c = reinterpret_cast<uint32_t *>(take(n * 4 * kFMaxSeg));
-  f.out_k = reinterpret_cast<uint64_t *>(take(m * 8));
-  f.out_e = reinterpret_cast<uint64_t *>(take(m * 8));
-  f.ka = reinterpret_cast<uint64_t *>(take(m * 8));
-  f.kb = reinterpret_cast<uint64_t *>(take(m * 8));
-  f.k2a = reinterpret_cast<uint64_t *>(take(m * 8));
-  f.k2b = reinterpret_cast<uint64_t *>(take(m * 8));
-  f.va = reinterpret_cast<uint32_t *>(take(m * 4));
-  f.vb = reinterpret_cast<uint32_t *>(take(m * 4));
-  f.v2a = reinterpret_cast<uint32_t *>(take(m * 4));
-  f.v2b = reinterpret_cast<uint32_t *>(take(m * 4));
-  f.radix = take(radix_scratch_bytes(m));
-  f.bytes = off;
+  f.words = c.take<uint32_t>(4 * (kFMaxRounds + 1));  // what each round added
+  f.lab = c.take<uint32_t>(n * 4);
+  f.par = c.take<uint32_t>(n * 4);
+  f.tile_lab = c.take<uint32_t>(n * 4);
+  f.comp_k = c.take<uint64_t>(n * 8);
+  f.comp_e = c.take<uint64_t>(n * 8);
+  f.part_k = c.take<uint64_t>(n * 8 * kFMaxSeg);
+  f.part_c = c.take<uint32_t>(n * 4 * kFMaxSeg);
+  f.out_k = c.take<uint64_t>(m * 8);
+  f.out_e = c.take<uint64_t>(m * 8);
+  f.ka = c.take<uint64_t>(m * 8);
+  f.kb = c.take<uint64_t>(m * 8);
+  f.k2a = c.take<uint64_t>(m * 8);
+  f.k2b = c.take<uint64_t>(m * 8);
+  f.va = c.take<uint32_t>(m * 4);
+  f.vb = c.take<uint32_t>(m * 4);
+  f.v2a = c.take<uint32_t>(m * 4);
+  f.v2b = c.take<uint32_t>(m * 4);
+  f.radix = c.take<void>(radix_scratch_bytes(m));
+  f.bytes = c.off;
   return f;
 }
 
 template <int KIND>
 static int forest_nearest(const double *a, uint32_t r1, uint32_t n_dims, const double *metric, double p, double max_distance, const ForestWork &f,
                           uint32_t *lab, uint32_t *n_seg_out, const uint32_t *gate, hipStream_t st) {
-  // clusters_tiles' two shapes (clusters.hip): 32 columns x 256 rows, a thread 4 x 8, for a long set; 64 x 64, a thread 4 x 4, below.
-  // (The choice moves no bit: a pair's chain is one thread's either way.)
-  const bool big = r1 >= 65536;
-  const uint32_t w = big ? 32 : 64, n_cg = w / 4, n_rg = 256 / n_cg, TJ = (big ? 8 : 4) * n_rg, kf = TJ / w;
-  const uint32_t n_ct = div_up(r1, w), strips = div_up(r1, TJ);
+  const SelfShape s = self_shape(r1);
+  const uint32_t w = s.w, n_ct = div_up(r1, w), strips = div_up(r1, s.TJ);
   // the columns in a few segments when the strips alone do not fill the chip twice over
   const uint32_t want = div_up(2 * (uint64_t)std::max(ctx().n_cus, 1), strips);
   const uint32_t n_seg_max = std::max(1u, std::min({want, (uint32_t)kFMaxSeg, n_ct}));
@@ -341,12 +316,10 @@ static int forest_nearest(const double *a, uint32_t r1, uint32_t n_dims, const d
   KPOP_LAUNCH_CHECK();
   if (strips > 0x7FFFFFFFu) KPOP_FAIL(KPOP_ERR_UNSUPPORTED, "kpop_dev_spanning_forest: %u rows", r1);
   const dim3 grid(strips, n_seg);
-  if (big)
-    forest_nearest_kernel<KIND, 8><<<grid, dim3(256), 0, st>>>(a, w, r1, n_dims, metric, p, max_distance, n_cg, n_rg, kf, n_ct, tiles_per_seg, lab, f.tile_lab,
-                                                               f.part_k, f.part_c, gate);
-  else
-    forest_nearest_kernel<KIND, 4><<<grid, dim3(256), 0, st>>>(a, w, r1, n_dims, metric, p, max_distance, n_cg, n_rg, kf, n_ct, tiles_per_seg, lab, f.tile_lab,
-                                                               f.part_k, f.part_c, gate);
+  by_shape_rows(s, [&](auto TY) {
+    forest_nearest_kernel<KIND, decltype(TY)::value><<<grid, dim3(256), 0, st>>>(a, w, r1, n_dims, metric, p, max_distance, s.n_cg, s.n_rg, s.kf, n_ct, tiles_per_seg, lab,
+                                                                                f.tile_lab, f.part_k, f.part_c, gate);
+  });
   KPOP_LAUNCH_CHECK();
   return 0;
 }
@@ -374,20 +347,13 @@ static int forest_dev(kpop_refset *rs, double max_distance, void *d_work, uint32
   forest_init_kernel<<<dim3(rows_grid), dim3(256), 0, st>>>(lab, f.par, f.comp_k, f.comp_e, f.out_k, f.out_e, r1, r1 > 1 ? m : 0);
   KPOP_LAUNCH_CHECK();
   if (r1 == 1 || !(max_distance >= 0.0)) return KPOP_OK;  // (no distance is negative: below zero every row stays alone)
-  const double *a = rs->rows;
-  if (rs->normalize) {
-    KPOP_TRY(rs->prepared(st));
-    KPOP_TRY(rs->divided(st, &a));
-  }
+  const double *a;
+  KPOP_TRY(refset_chain_rows(rs, st, &a));
   const uint32_t rounds = forest_rounds(r1);
   for (uint32_t k = 0; k < rounds; ++k) {
     const uint32_t *gate = k ? f.words + (k - 1) : nullptr;
     uint32_t n_seg = 1;
-    switch (rs->kind) {
-      case KPOP_EUCLIDEAN: KPOP_TRY(forest_nearest<KPOP_EUCLIDEAN>(a, r1, rs->n_dims, rs->metric, rs->p, max_distance, f, lab, &n_seg, gate, st)); break;
-      case KPOP_COSINE: KPOP_TRY(forest_nearest<KPOP_COSINE>(a, r1, rs->n_dims, rs->metric, rs->p, max_distance, f, lab, &n_seg, gate, st)); break;
-      default: KPOP_TRY(forest_nearest<KPOP_MINKOWSKI>(a, r1, rs->n_dims, rs->metric, rs->p, max_distance, f, lab, &n_seg, gate, st)); break;
-    }
+    KPOP_TRY(by_kind(rs->kind, [&](auto K) { return forest_nearest<decltype(K)::value>(a, r1, rs->n_dims, rs->metric, rs->p, max_distance, f, lab, &n_seg, gate, st); }));
     forest_row_min_kernel<<<dim3(rows_grid), dim3(256), 0, st>>>(f.part_k, f.part_c, n_seg, r1, lab, f.comp_k, gate);
     KPOP_LAUNCH_CHECK();
     forest_comp_edge_kernel<<<dim3(rows_grid), dim3(256), 0, st>>>(f.part_k, f.part_c, r1, lab, f.comp_k, f.comp_e, gate);
@@ -475,11 +441,8 @@ extern "C" int kpop_spanning_forest(kpop_refset *rs, double max_distance, uint32
 extern "C" int kpop_distance_spanning_forest(const double *m, uint32_t rows, uint32_t n_dims, const double *metric, int kind, double p, int normalize,
                                              double max_distance, uint32_t *n_edges, uint32_t *edge_i, uint32_t *edge_j, double *edge_dist,
                                              uint32_t *labels) {
-  kpop_refset *rs = nullptr;
-  KPOP_TRY(kpop_refset_create(m, rows, n_dims, metric, kind, p, normalize, 0, &rs));
-  const int rc = kpop_spanning_forest(rs, max_distance, n_edges, edge_i, edge_j, edge_dist, labels);
-  const int rc_free = kpop_refset_free(rs);
-  return rc ? rc : rc_free;
+  return with_temporary_refset(m, rows, n_dims, metric, kind, p, normalize,
+                               [&](kpop_refset *rs) { return kpop_spanning_forest(rs, max_distance, n_edges, edge_i, edge_j, edge_dist, labels); });
 }
 
 // host arithmetic alone: the union-find of the labels, the larger root under the smaller, over the edges within T

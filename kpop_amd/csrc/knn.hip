@@ -466,11 +466,9 @@ template <bool LEAVE_OUT>
 static int knn_passes_of_kind(int kind, const double *a, uint32_t r1, const double *b, uint32_t r2, uint32_t n_dims, const double *metric, double p, uint32_t k,
                               const uint32_t *group_of, uint32_t first_row, const uint32_t *class_of, uint32_t n_classes, const KnnWork &w, uint32_t *n_seg,
                               hipStream_t st) {
-  switch (kind) {
-    case KPOP_EUCLIDEAN: return knn_passes_of<KPOP_EUCLIDEAN, LEAVE_OUT>(a, r1, b, r2, n_dims, metric, p, k, group_of, first_row, class_of, n_classes, w, n_seg, st);
-    case KPOP_COSINE: return knn_passes_of<KPOP_COSINE, LEAVE_OUT>(a, r1, b, r2, n_dims, metric, p, k, group_of, first_row, class_of, n_classes, w, n_seg, st);
-    default: return knn_passes_of<KPOP_MINKOWSKI, LEAVE_OUT>(a, r1, b, r2, n_dims, metric, p, k, group_of, first_row, class_of, n_classes, w, n_seg, st);
-  }
+  return by_kind(kind, [&](auto K) {
+    return knn_passes_of<decltype(K)::value, LEAVE_OUT>(a, r1, b, r2, n_dims, metric, p, k, group_of, first_row, class_of, n_classes, w, n_seg, st);
+  });
 }
 
 // (knn_lists.h) the three passes as knn_dev launches them, and with rows left out: for knn_validate.hip
@@ -501,10 +499,9 @@ static int knn_dev(kpop_refset *rs, const uint32_t *d_class_of, uint32_t n_class
   } else {
     KPOP_HIP(hipMemsetAsync(reinterpret_cast<char *>(d_work) + w.tables_off, 0, w.tables_bytes, st));
     KPOP_HIP(hipMemsetAsync(w.tie_first, 0xFF, (uint64_t)r2 * n_classes * 4, st));
-    const double *a = rs->rows, *b = d_m2;
-    if (rs->normalize) {  // the set's quotients from its copy, the query rows' from the norms' pass: prepare_operands' (distance.hip)
-      KPOP_TRY(rs->prepared(st));
-      KPOP_TRY(rs->divided(st, &a));
+    const double *a, *b = d_m2;
+    KPOP_TRY(refset_chain_rows(rs, st, &a));
+    if (rs->normalize) {  // the query rows' quotients from the norms' pass: prepare_operands' (distance.hip)
       KPOP_TRY(refset_query_norms(rs, d_m2, r2, w.n2, w.b, st));
       b = w.b;
     }
@@ -575,9 +572,6 @@ extern "C" int kpop_knn_vote(kpop_refset *rs, const uint32_t *class_of, uint32_t
 extern "C" int kpop_distance_knn_vote(const double *m1, uint32_t r1, const uint32_t *class_of, uint32_t n_classes, const double *m2, uint32_t r2, uint32_t n_dims,
                                       const double *metric, int kind, double p, int normalize, uint32_t k, uint32_t *out_class, uint32_t *out_votes,
                                       uint32_t *out_n, double *out_first_dist) {
-  kpop_refset *rs = nullptr;
-  KPOP_TRY(kpop_refset_create(m1, r1, n_dims, metric, kind, p, normalize, 0, &rs));
-  const int rc = kpop_knn_vote(rs, class_of, n_classes, m2, r2, k, out_class, out_votes, out_n, out_first_dist);
-  const int rc_free = kpop_refset_free(rs);
-  return rc ? rc : rc_free;
+  return with_temporary_refset(m1, r1, n_dims, metric, kind, p, normalize,
+                               [&](kpop_refset *rs) { return kpop_knn_vote(rs, class_of, n_classes, m2, r2, k, out_class, out_votes, out_n, out_first_dist); });
 }

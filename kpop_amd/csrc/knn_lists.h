@@ -5,6 +5,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "refset_call.h"
 #include "space_ops.h"
 
 namespace kpop {
@@ -114,32 +115,26 @@ static uint32_t knn_max_segments(uint32_t r2, uint32_t strip_rows) {
 }
 
 static KnnWork knn_carve(void *work, uint32_t r2, uint32_t k, uint32_t n_classes, uint32_t n_dims, bool normalize) {
-  char *base = reinterpret_cast<char *>(work);
-  uint64_t off = 0;
-  auto take = [&](uint64_t bytes) {
-    char *q = base + off;
-    off += (bytes + 255) & ~255ull;
-    return q;
-  };
+  Carver c(work);
   const uint64_t n = r2, lists = n * k, segs = knn_max_segments(r2, knn_strip_rows(k));
   KnnWork w;
-  w.n2 = reinterpret_cast<double *>(take(normalize ? n * 8 : 0));
-  w.b = reinterpret_cast<double *>(take(normalize ? n * n_dims * 8 : 0));
-  w.seg_key = reinterpret_cast<uint64_t *>(take(lists * 8 * segs));
-  w.seg_idx = reinterpret_cast<uint32_t *>(take(lists * 4 * segs));
-  w.seg_n = reinterpret_cast<uint32_t *>(take(n * 4 * segs));
-  w.seg_drop = reinterpret_cast<uint32_t *>(take(n * 4 * segs));
-  w.m_key = reinterpret_cast<uint64_t *>(take(lists * 8));
-  w.m_idx = reinterpret_cast<uint32_t *>(take(lists * 4));
-  w.m_tau = reinterpret_cast<uint64_t *>(take(n * 8));
-  w.m_n = reinterpret_cast<uint32_t *>(take(n * 4));
-  w.m_flag = reinterpret_cast<uint32_t *>(take(n * 4));
-  w.tables_off = off;
-  w.tie_total = reinterpret_cast<uint32_t *>(take(n * 4));
-  w.tie_count = reinterpret_cast<uint32_t *>(take(n * n_classes * 4));
-  w.tables_bytes = off - w.tables_off;  // (zeroes)
-  w.tie_first = reinterpret_cast<uint32_t *>(take(n * n_classes * 4));  // (ones)
-  w.bytes = off + 256;
+  w.n2 = c.take<double>(normalize ? n * 8 : 0);
+  w.b = c.take<double>(normalize ? n * n_dims * 8 : 0);
+  w.seg_key = c.take<uint64_t>(lists * 8 * segs);
+  w.seg_idx = c.take<uint32_t>(lists * 4 * segs);
+  w.seg_n = c.take<uint32_t>(n * 4 * segs);
+  w.seg_drop = c.take<uint32_t>(n * 4 * segs);
+  w.m_key = c.take<uint64_t>(lists * 8);
+  w.m_idx = c.take<uint32_t>(lists * 4);
+  w.m_tau = c.take<uint64_t>(n * 8);
+  w.m_n = c.take<uint32_t>(n * 4);
+  w.m_flag = c.take<uint32_t>(n * 4);
+  w.tables_off = c.off;
+  w.tie_total = c.take<uint32_t>(n * 4);
+  w.tie_count = c.take<uint32_t>(n * n_classes * 4);
+  w.tables_bytes = c.off - w.tables_off;  // (zeroes)
+  w.tie_first = c.take<uint32_t>(n * n_classes * 4);  // (ones)
+  w.bytes = c.off + 256;
   return w;
 }
 

@@ -272,10 +272,9 @@ static int vote_ks_dev(kpop_refset *rs, const uint32_t *d_class_of, uint32_t n_c
   } else {
     KPOP_HIP(hipMemsetAsync(reinterpret_cast<char *>(d_work) + w.tables_off, 0, w.tables_bytes, st));
     KPOP_HIP(hipMemsetAsync(w.tie_first, 0xFF, (uint64_t)r2 * n_classes * 4, st));
-    const double *a = rs->rows, *b = d_m2;
-    if (rs->normalize) {  // the set's quotients from its copy, the query rows' from the norms' pass: knn_dev's
-      KPOP_TRY(rs->prepared(st));
-      KPOP_TRY(rs->divided(st, &a));
+    const double *a, *b = d_m2;
+    KPOP_TRY(refset_chain_rows(rs, st, &a));
+    if (rs->normalize) {  // the query rows' quotients from the norms' pass: knn_dev's
       KPOP_TRY(refset_query_norms(rs, d_m2, r2, w.n2, w.b, st));
       b = w.b;
     }
@@ -305,11 +304,8 @@ static int validate_dev(kpop_refset *rs, const uint32_t *d_class_of, uint32_t n_
   const KnnWork w = knn_carve(d_work, n_rows, K, n_classes, D, false);
   KPOP_HIP(hipMemsetAsync(reinterpret_cast<char *>(d_work) + w.tables_off, 0, w.tables_bytes, st));
   KPOP_HIP(hipMemsetAsync(w.tie_first, 0xFF, (uint64_t)n_rows * n_classes * 4, st));
-  const double *a = rs->rows;
-  if (rs->normalize) {  // both operands the set's divided copy: clusters.hip's
-    KPOP_TRY(rs->prepared(st));
-    KPOP_TRY(rs->divided(st, &a));
-  }
+  const double *a;  // both operands
+  KPOP_TRY(refset_chain_rows(rs, st, &a));
   uint32_t n_seg = 0;
   KPOP_TRY(knn_run_leave_out_passes(rs->kind, a, r1, first_row, n_rows, D, rs->metric, rs->p, K, d_group_of, d_class_of, n_classes, w, &n_seg, st));
   knn_vote_ks_launch(w, n_seg, n_rows, K, d_class_of, n_classes, ks, d_out_class, d_out_votes, d_out_n, d_out_first_dist, st);
@@ -456,9 +452,7 @@ extern "C" int kpop_knn_validate(kpop_refset *rs, const uint32_t *class_of, uint
 extern "C" int kpop_distance_knn_validate(const double *m, uint32_t rows, uint32_t n_dims, const double *metric, int kind, double p, int normalize,
                                           const uint32_t *class_of, uint32_t n_classes, const uint32_t *group_of, const uint32_t *ks, uint32_t n_ks,
                                           uint32_t *out_class, uint32_t *out_votes, uint32_t *out_n, double *out_first_dist, uint64_t *out_correct) {
-  kpop_refset *rs = nullptr;
-  KPOP_TRY(kpop_refset_create(m, rows, n_dims, metric, kind, p, normalize, 0, &rs));
-  const int rc = kpop_knn_validate(rs, class_of, n_classes, group_of, ks, n_ks, out_class, out_votes, out_n, out_first_dist, out_correct);
-  const int rc_free = kpop_refset_free(rs);
-  return rc ? rc : rc_free;
+  return with_temporary_refset(m, rows, n_dims, metric, kind, p, normalize, [&](kpop_refset *rs) {
+    return kpop_knn_validate(rs, class_of, n_classes, group_of, ks, n_ks, out_class, out_votes, out_n, out_first_dist, out_correct);
+  });
 }

@@ -1,6 +1,6 @@
 // pair_tile.h -- the f64 pair tile of the vector pipe, once: the loop that every kernel computing the reference chain's distances
-// of a tile of pairs is built on (within.hip, clusters.hip, forest.hip, knn.hip, representatives.hip; distance_rowwise_kernel keeps
-// the form it was written in, see distance.hip).
+// of a tile of pairs is built on (within.hip, clusters.hip, forest.hip, knn.hip, representatives.hip, dbscan.hip;
+// distance_rowwise_kernel keeps the form it was written in, see distance.hip).  What the self-joins share around it: self_tile.h.
 //
 //   A workgroup of 256 threads owns columns i0 .. i1 (rows of the first operand) x rows j0 .. j1 (rows of the second); a thread
 //   4 columns x TY rows.  The chain of a pair (lib/Space.ml:192-200 with the adaptors of lib/Matrix.ml:243-250) is ONE thread's,
@@ -15,7 +15,8 @@
 //       stage.load(...);                       the next step's operands -- this tile's next dimensions, or the next tile's
 //                                              first -- issued before the arithmetic, landing behind it
 //       if (worker) pair_accumulate(...);
-//   The tile's choice, the barriers, the LDS arrays and the epilogue are the kernel's.
+//   The tile's choice, the barriers, the LDS arrays and the epilogue are the kernel's; a kernel that computes one tile takes the
+//   whole loop as pair_tile_distances.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -110,6 +111,32 @@ __device__ __forceinline__ void pair_accumulate(double (&acc)[TY][4], double (*A
         double diff = __dsub_rn(av[x], bv[y]);
         acc[y][x] = __dadd_rn(acc[y][x], component<KIND>(diff, mc, p));
       }
+  }
+}
+
+// the kernels that compute ONE tile: the distances of columns i0 .. i1 of a x rows j0 .. j1 of b, the steps above over all the
+// dimensions, then the scaling.  worker: the thread holds pairs (a literal `true` where the tile's shape says so costs nothing);
+// every thread stages and meets the barriers
+template <int KIND, int TY, int MAXW, int MAXTJ>
+__device__ __forceinline__ void pair_tile_distances(double (&acc)[TY][4], double (*As)[MAXW + 2], double (*Bs)[MAXTJ + 2], double *s_metric,
+                                                    const double *__restrict__ a, uint32_t i0, uint32_t i1, const double *__restrict__ b, uint32_t j0,
+                                                    uint32_t j1, uint32_t n_dims, const double *__restrict__ metric, double p, uint32_t ti, uint32_t tj,
+                                                    bool worker) {
+  pair_zero(acc);
+  PairStage<MAXW, MAXTJ> stage;
+  stage.load(a, i0, i1, b, j0, j1, n_dims, 0, n_dims);
+  for (uint32_t c0 = 0; c0 < n_dims; c0 += kPairDC) {
+    __syncthreads();
+    stage.store(As, Bs, s_metric, metric, c0, n_dims);
+    __syncthreads();
+    if (c0 + kPairDC < n_dims) stage.load(a, i0, i1, b, j0, j1, n_dims, c0 + kPairDC, n_dims);
+    if (worker) pair_accumulate<KIND>(acc, As, Bs, s_metric, ti, tj, min((uint32_t)kPairDC, n_dims - c0), p);
+  }
+  if (worker) {
+#pragma unroll
+    for (int yy = 0; yy < TY; ++yy)
+#pragma unroll
+      for (int x = 0; x < 4; ++x) acc[yy][x] = scale_distance<KIND>(acc[yy][x], p);
   }
 }
 

@@ -11,13 +11,13 @@
 // row indices ascending, and the device word n_reps.  A step over rows js .. je:
 //   representatives_cover_kernel    the step's rows against reps[0 .. n0), n0 read from the device word (the grid is fixed, the tile
 //                                   bounds come from the word, clamped to the capacity the workspace was sized for).
-//                                   forest_nearest_kernel's shape (forest.hip): a workgroup owns a strip of rows and a segment of
+//                                   A workgroup owns a strip of rows (the self-join's tile shapes, tri_tile.h) and a segment of
 //                                   the column tiles, every thread keeps the best (key, position in reps) of its rows, the lanes of a
-//                                   row reduce with shuffles, one store a row and segment.  The columns are gathered rows: the
+//                                   row reduce with shuffles (self_tile.h), one store a row and segment.  The columns are gathered rows: the
 //                                   indexed load of pair_tile.h -- no compacted copy of the representatives' rows is kept.
 //                                   Positions ascend with the row index, so (key, position) orders as (d, r)
 //   representatives_row_min_kernel  the least of a row's segments; key none: not covered
-//   representatives_hits_kernel     clusters_tile_kernel's arithmetic over the lower triangle of the step's rows against themselves,
+//   representatives_hits_kernel     a tile's distances and compare (self_tile.h) over the lower triangle of the step's rows against themselves,
 //                                   a row tile whose rows are all covered skipped: the bit matrix H[j][i], i < j, d(j, i) <= T
 //   representatives_resolve_kernel  the sequential part, one wavefront: the rows that are not covered, ascending; lane l holds bits
 //                                   32 l .. 32 l + 32 of the set chosen in this step, a row is chosen iff H[row] & chosen is empty --
@@ -33,10 +33,9 @@
 
 #include "common.h"
 #include "distance_routes.h"
-#include "pair_tile.h"
-#include "refset.h"
+#include "refset_call.h"
 #include "scan.h"
-#include "space_ops.h"
+#include "self_tile.h"
 
 namespace kpop {
 
@@ -55,24 +54,18 @@ struct RepWork {
 
 static RepWork representatives_carve(void *base, uint32_t r1) {
   const uint64_t n = std::max(r1, 1u);
-  char *c = reinterpret_cast<char *>(base);
-  uint64_t off = 0;
-  auto take = [&](uint64_t b) {
-    char *q = c + off;
-    off += (b + 255) & ~255ull;
-    return q;
-  };
+  Carver c(base);
   RepWork f;
-  f.words = reinterpret_cast<uint32_t *>(take(256));
-  f.chosen = reinterpret_cast<uint32_t *>(take(4 * kRepHWords));
-  f.reps = reinterpret_cast<uint32_t *>(take(n * 4));
-  f.part_k = reinterpret_cast<uint64_t *>(take((uint64_t)kRepMaxSeg * kRepStep * 8));
-  f.part_c = reinterpret_cast<uint32_t *>(take((uint64_t)kRepMaxSeg * kRepStep * 4));
-  f.best_k = reinterpret_cast<uint64_t *>(take((uint64_t)kRepStep * 8));
-  f.best_c = reinterpret_cast<uint32_t *>(take((uint64_t)kRepStep * 4));
-  f.H = reinterpret_cast<uint32_t *>(take((uint64_t)kRepStep * kRepHWords * 4));
-  f.sums = reinterpret_cast<uint64_t *>(take((scan_blocks(n) + 1) * 8));
-  f.bytes = off;
+  f.words = c.take<uint32_t>(256);
+  f.chosen = c.take<uint32_t>(4 * kRepHWords);
+  f.reps = c.take<uint32_t>(n * 4);
+  f.part_k = c.take<uint64_t>((uint64_t)kRepMaxSeg * kRepStep * 8);
+  f.part_c = c.take<uint32_t>((uint64_t)kRepMaxSeg * kRepStep * 4);
+  f.best_k = c.take<uint64_t>((uint64_t)kRepStep * 8);
+  f.best_c = c.take<uint32_t>((uint64_t)kRepStep * 4);
+  f.H = c.take<uint32_t>((uint64_t)kRepStep * kRepHWords * 4);
+  f.sums = c.take<uint64_t>((scan_blocks(n) + 1) * 8);
+  f.bytes = c.off;
   return f;
 }
 
@@ -110,7 +103,7 @@ __global__ __launch_bounds__(256) void representatives_alone_kernel(uint32_t kno
 // blockIdx.x: rows j0 .. j0 + TJ of the step js .. je, TJ = TY n_rg; segment blockIdx.y of gridDim.y: its share of the column tiles,
 // w positions of reps[lo .. hi) each -- lo = 0, hi = n_reps (newer = 0: the representatives before the step), or lo = the count
 // before the step's resolve, hi = n_reps (newer = 1: those the step chose, of which only the ones below a row are eligible to it).
-// A thread 4 columns x TY rows, the dimensions ascending in one thread, 16 at a time through LDS: forest_nearest_kernel's loop.
+// A thread 4 columns x TY rows, the dimensions ascending in one thread, 16 at a time through LDS: the many-tile step of pair_tile.h.
 template <int KIND, int TY>
 __global__ __launch_bounds__(256, 1) void representatives_cover_kernel(const double *__restrict__ a, uint32_t cap, uint32_t w, uint32_t n_dims,
                                                                        const double *__restrict__ metric, double p, double max_distance, uint32_t n_cg,
@@ -157,7 +150,7 @@ __global__ __launch_bounds__(256, 1) void representatives_cover_kernel(const dou
       if (more || t + 1 < t_end) stage.load_indexed(a, cap, reps, ni0, min(hi, ni0 + w), a, j0, j1, n_dims, more ? c0 + kPairDC : 0u, n_dims);
       if (worker) pair_accumulate<KIND>(acc, As, Bs, s_metric, ti, tj, min((uint32_t)kPairDC, n_dims - c0), p);
     }
-    // the epilogue: compare where clusters_tile_kernel compares (a NaN compares false: within nothing); a representative below the
+    // the epilogue: the scaled distance against the bound (a NaN compares false: within nothing); a representative below the
     // row only.  Positions ascend within the tile and from tile to tile, so that `below` alone keeps, among equal keys, the least
     if (worker) {
 #pragma unroll
@@ -176,26 +169,14 @@ __global__ __launch_bounds__(256, 1) void representatives_cover_kernel(const dou
         }
     }
   }
-  // the n_cg threads of a row are neighbouring lanes of one wavefront (n_cg divides 64, a row group starts at a multiple of it)
-  for (uint32_t o = n_cg >> 1; o > 0; o >>= 1) {
+  // the least (key, position) over a row's lanes
 #pragma unroll
-    for (int yy = 0; yy < TY; ++yy) {
-      const uint64_t ok = (uint64_t)__shfl_xor((unsigned long long)best_k[yy], (int)o, 64);
-      const uint32_t oc = (uint32_t)__shfl_xor((int)best_c[yy], (int)o, 64);
-      if (key_less(ok, oc, best_k[yy], best_c[yy])) {
-        best_k[yy] = ok;
-        best_c[yy] = oc;
-      }
-    }
-  }
-  if (worker && cg == 0) {
-#pragma unroll
-    for (int yy = 0; yy < TY; ++yy) {
-      const uint32_t j = j0 + tj + yy;
-      if (j < j1) {
-        part_k[(uint64_t)seg * kRepStep + (j - js)] = best_k[yy];
-        part_c[(uint64_t)seg * kRepStep + (j - js)] = best_c[yy];
-      }
+  for (int yy = 0; yy < TY; ++yy) {
+    const KeyAt best = reduce_row_lanes(KeyAt{best_k[yy], best_c[yy]}, n_cg, key_at_min);
+    const uint32_t j = j0 + tj + yy;
+    if (worker && cg == 0 && j < j1) {
+      part_k[(uint64_t)seg * kRepStep + (j - js)] = best.k;
+      part_c[(uint64_t)seg * kRepStep + (j - js)] = best.c;
     }
   }
 }
@@ -236,7 +217,7 @@ __global__ __launch_bounds__(256) void representatives_row_min_kernel(const uint
 
 // a: as above, both operands.  Tile blockIdx.x, blockIdx.y of the step's rows js .. je against themselves: w columns from
 // js + blockIdx.x w, TJ = TY n_rg rows from js + blockIdx.y TJ; the lower triangle only, and no row tile whose rows are all covered
-// (best_k has a key): nobody reads their rows of H.  A thread 4 columns x TY rows: clusters_tile_kernel's loop and compare.  H: a row
+// (best_k has a key): nobody reads their rows of H.  A thread 4 columns x TY rows: the tile of self_tile.h.  H: a row
 // kRepHWords words of 32 bits, bit i - js of row j - js set iff i < j and d(j, i) <= max_distance; a tile writes all the words
 // of its rows that it covers, zero bits included, so that H needs no clearing
 template <int KIND, int TY>
@@ -259,30 +240,13 @@ __global__ __launch_bounds__(256, 1) void representatives_hits_kernel(const doub
   const bool worker = rg < n_rg;
   const uint32_t ti = cg * 4, tj = (worker ? rg : 0) * TY;
   double acc[TY][4];
-  pair_zero(acc);
-  PairStage<kRepMaxW, kRepMaxTJ> stage;
-  stage.load(a, i0, i1, a, j0, j1, n_dims, 0, n_dims);
-  for (uint32_t c0 = 0; c0 < n_dims; c0 += kPairDC) {
-    __syncthreads();
-    stage.store(As, Bs, s_metric, metric, c0, n_dims);
-    __syncthreads();
-    if (c0 + kPairDC < n_dims) stage.load(a, i0, i1, a, j0, j1, n_dims, c0 + kPairDC, n_dims);
-    if (worker) pair_accumulate<KIND>(acc, As, Bs, s_metric, ti, tj, min((uint32_t)kPairDC, n_dims - c0), p);
-  }
-  // the epilogue: a thread's 4 columns are 4 bits of its row's word; the n_cg threads of a row are neighbouring lanes
+  pair_tile_distances<KIND, TY, kRepMaxW, kRepMaxTJ>(acc, As, Bs, s_metric, a, i0, i1, a, j0, j1, n_dims, metric, p, ti, tj, worker);
+  const uint32_t mask = worker ? self_hit_mask<TY>(acc, TriTile{blockIdx.x, blockIdx.y, i0, i1, j0, j1, true}, ti, tj, max_distance) : 0u;
+  // the epilogue: a thread's 4 columns are 4 bits of its row's word, OR-ed over the row's lanes
 #pragma unroll
   for (int yy = 0; yy < TY; ++yy) {
-    uint64_t bits = 0;
     const uint32_t j = j0 + tj + yy;
-    if (worker) {
-#pragma unroll
-      for (int x = 0; x < 4; ++x) {
-        const double d = scale_distance<KIND>(acc[yy][x], p);
-        const uint32_t i = i0 + ti + x;
-        if (j < j1 && i < i1 && i < j && d <= max_distance) bits |= 1ull << (ti + x);
-      }
-    }
-    for (uint32_t o = n_cg >> 1; o > 0; o >>= 1) bits |= (uint64_t)__shfl_xor((unsigned long long)bits, (int)o, 64);
+    const uint64_t bits = reduce_row_lanes((uint64_t)((mask >> (4 * yy)) & 0xFu) << ti, n_cg, [](uint64_t x, uint64_t y) { return x | y; });
     if (worker && cg == 0 && j < j1) {
       uint32_t *row = H + (uint64_t)(j - js) * kRepHWords + (i0 - js) / 32;
       row[0] = (uint32_t)bits;
@@ -336,30 +300,25 @@ __global__ __launch_bounds__(64) void representatives_resolve_kernel(const uint6
 template <int KIND>
 static int representatives_steps(const double *a, uint32_t r1, uint32_t n_dims, const double *metric, double p, double max_distance, uint32_t known_rows,
                                  const RepWork &f, uint32_t *rep_of, double *rep_dist, hipStream_t st) {
-  // clusters_tiles' two shapes (clusters.hip): 32 columns x 256 rows, a thread 4 x 8, for a long set; 64 x 64, a thread 4 x 4, below.
-  // (The choice moves no bit: a pair's chain is one thread's either way.)
-  const bool big = r1 >= 65536;
-  const uint32_t w = big ? 32 : 64, n_cg = w / 4, n_rg = 256 / n_cg, TJ = (big ? 8 : 4) * n_rg;
-  const uint32_t strips = kRepStep / TJ, n_seg = std::min<uint32_t>(kRepMaxSeg, 512 / strips);  // two workgroups a CU, as the registers admit
-  const dim3 cover_grid(strips, n_seg), hits_grid(kRepStep / w, kRepStep / TJ), rows_grid(kRepStep / 256);
+  const SelfShape sh = self_shape(r1);
+  const uint32_t strips = kRepStep / sh.TJ, n_seg = std::min<uint32_t>(kRepMaxSeg, 512 / strips);  // two workgroups a CU, as the registers admit
+  const dim3 cover_grid(strips, n_seg), hits_grid(kRepStep / sh.w, kRepStep / sh.TJ), rows_grid(kRepStep / 256);
   for (uint64_t s = known_rows; s < r1; s += kRepStep) {
     const uint32_t js = (uint32_t)s, je = (uint32_t)std::min<uint64_t>(r1, s + kRepStep);
     for (int last = 0; last < 2; ++last) {
-      if (big)
-        representatives_cover_kernel<KIND, 8><<<cover_grid, dim3(256), 0, st>>>(a, r1, w, n_dims, metric, p, max_distance, n_cg, n_rg, js, je, f.words, last, f.reps,
-                                                                              f.part_k, f.part_c);
-      else
-        representatives_cover_kernel<KIND, 4><<<cover_grid, dim3(256), 0, st>>>(a, r1, w, n_dims, metric, p, max_distance, n_cg, n_rg, js, je, f.words, last, f.reps,
-                                                                              f.part_k, f.part_c);
+      by_shape_rows(sh, [&](auto TY) {
+        representatives_cover_kernel<KIND, decltype(TY)::value><<<cover_grid, dim3(256), 0, st>>>(a, r1, sh.w, n_dims, metric, p, max_distance, sh.n_cg, sh.n_rg, js, je,
+                                                                                                 f.words, last, f.reps, f.part_k, f.part_c);
+      });
       KPOP_LAUNCH_CHECK();
       representatives_row_min_kernel<<<rows_grid, dim3(256), 0, st>>>(f.part_k, f.part_c, n_seg, js, je, r1, f.best_k, f.best_c, last, f.chosen, f.reps, rep_of,
                                                                       rep_dist);
       KPOP_LAUNCH_CHECK();
       if (last) break;
-      if (big)
-        representatives_hits_kernel<KIND, 8><<<hits_grid, dim3(256), 0, st>>>(a, w, n_dims, metric, p, max_distance, n_cg, n_rg, js, je, f.best_k, f.H);
-      else
-        representatives_hits_kernel<KIND, 4><<<hits_grid, dim3(256), 0, st>>>(a, w, n_dims, metric, p, max_distance, n_cg, n_rg, js, je, f.best_k, f.H);
+      by_shape_rows(sh, [&](auto TY) {
+        representatives_hits_kernel<KIND, decltype(TY)::value><<<hits_grid, dim3(256), 0, st>>>(a, sh.w, n_dims, metric, p, max_distance, sh.n_cg, sh.n_rg, js, je, f.best_k,
+                                                                                               f.H);
+      });
       KPOP_LAUNCH_CHECK();
       representatives_resolve_kernel<<<dim3(1), dim3(64), 0, st>>>(f.best_k, f.H, js, je, r1, f.words, f.reps, f.chosen);
       KPOP_LAUNCH_CHECK();
@@ -393,22 +352,11 @@ static int representatives_dev(kpop_refset *rs, double max_distance, uint32_t kn
       representatives_alone_kernel<<<dim3(std::min(div_up(r1 - known_rows, 256), 4096u)), dim3(256), 0, st>>>(known_rows, r1, d_rep_of, d_rep_dist, f.words);
       KPOP_LAUNCH_CHECK();
     } else {
-      const double *a = rs->rows;
-      if (rs->normalize) {
-        KPOP_TRY(rs->prepared(st));
-        KPOP_TRY(rs->divided(st, &a));
-      }
-      switch (rs->kind) {
-        case KPOP_EUCLIDEAN:
-          KPOP_TRY(representatives_steps<KPOP_EUCLIDEAN>(a, r1, rs->n_dims, rs->metric, rs->p, max_distance, known_rows, f, d_rep_of, d_rep_dist, st));
-          break;
-        case KPOP_COSINE:
-          KPOP_TRY(representatives_steps<KPOP_COSINE>(a, r1, rs->n_dims, rs->metric, rs->p, max_distance, known_rows, f, d_rep_of, d_rep_dist, st));
-          break;
-        default:
-          KPOP_TRY(representatives_steps<KPOP_MINKOWSKI>(a, r1, rs->n_dims, rs->metric, rs->p, max_distance, known_rows, f, d_rep_of, d_rep_dist, st));
-          break;
-      }
+      const double *a;
+      KPOP_TRY(refset_chain_rows(rs, st, &a));
+      KPOP_TRY(by_kind(rs->kind, [&](auto K) {
+        return representatives_steps<decltype(K)::value>(a, r1, rs->n_dims, rs->metric, rs->p, max_distance, known_rows, f, d_rep_of, d_rep_dist, st);
+      }));
     }
   }
   KPOP_HIP(hipMemcpyAsync(d_n_reps, f.words, 4, hipMemcpyDeviceToDevice, st));
@@ -440,10 +388,7 @@ extern "C" int kpop_representatives_within(kpop_refset *rs, double max_distance,
   if (!n_reps || (rs->r1 && !rep_of)) KPOP_FAIL(KPOP_ERR_INVALID, "%s: null argument", who);
   const uint32_t r1 = rs->r1;
   if (known_rows > r1) KPOP_FAIL(KPOP_ERR_INVALID, "%s: %u known rows in a set of %u", who, known_rows, r1);
-  // what an earlier call returned: an entry is no larger than its row and names a row that stands for itself
-  for (uint32_t i = 0; i < known_rows; ++i)
-    if (rep_of[i] > i || rep_of[rep_of[i]] != rep_of[i])
-      KPOP_FAIL(KPOP_ERR_INVALID, "%s: rep_of[%u] = %u is not an entry this call returns (rep_of[i] <= i, rep_of[rep_of[i]] == rep_of[i])", who, i, rep_of[i]);
+  KPOP_TRY(check_known_prefix(rep_of, known_rows, who, "rep_of", "an entry"));
   *n_reps = 0;
   if (r1 == 0) return KPOP_OK;
   hipStream_t st = nullptr;
@@ -466,9 +411,6 @@ extern "C" int kpop_representatives_within(kpop_refset *rs, double max_distance,
 
 extern "C" int kpop_distance_representatives(const double *m, uint32_t rows, uint32_t n_dims, const double *metric, int kind, double p, int normalize,
                                              double max_distance, uint32_t *rep_of, double *rep_dist, uint32_t *n_reps) {
-  kpop_refset *rs = nullptr;
-  KPOP_TRY(kpop_refset_create(m, rows, n_dims, metric, kind, p, normalize, 0, &rs));
-  const int rc = kpop_representatives_within(rs, max_distance, 0, rep_of, rep_dist, n_reps);
-  const int rc_free = kpop_refset_free(rs);
-  return rc ? rc : rc_free;
+  return with_temporary_refset(m, rows, n_dims, metric, kind, p, normalize,
+                               [&](kpop_refset *rs) { return kpop_representatives_within(rs, max_distance, 0, rep_of, rep_dist, n_reps); });
 }

@@ -1,5 +1,5 @@
-// union_find.h -- the lock-free union-find of clusters.hip and forest.hip: a forest in an array of parent words, parent[i] == i
-// a root.  The union hooks the LARGER root under the smaller with one compare-and-swap; finds halve the paths.  Only a root is
+// union_find.h -- the lock-free union-find of clusters.hip, dbscan.hip and forest.hip (and of a tile's forest in LDS, self_tile.h): a
+// forest in an array of parent words, parent[i] == i a root.  The union hooks the LARGER root under the smaller with one compare-and-swap; finds halve the paths.  Only a root is
 // ever hooked, and only under a smaller index: the forest stays acyclic, a row that has stopped being a root never becomes one
 // again, and the last root of a component is its smallest index whoever arrives first.  A failed compare-and-swap means somebody
 // else hooked that root: progress, and nothing waits on another workgroup.
@@ -35,6 +35,16 @@ __device__ __forceinline__ uint32_t uf_find_readonly(uint32_t *parent, uint32_t 
     if (q == x) return x;
     x = q;
   }
+}
+
+// after the unions, a launch of its own: the root of i, stored in i's word unless i is that root.  A root is a row whose word is its
+// own index: no store here changes that, and a word on somebody's path is that row's ancestor before the store and after it, so the
+// finds of the other threads of the launch (which store nothing but this) still end at the same roots
+template <int SCOPE>
+__device__ __forceinline__ uint32_t uf_settle(uint32_t *parent, uint32_t i) {
+  const uint32_t root = uf_find_readonly<SCOPE>(parent, i);
+  if (root != i) __hip_atomic_store(parent + i, root, __ATOMIC_RELAXED, SCOPE);
+  return root;
 }
 
 template <int SCOPE>

@@ -27,8 +27,8 @@
 #include "common.h"
 #include "distance_routes.h"
 #include "pair_tile.h"
+#include "refset_call.h"
 #include "scan.h"
-#include "space_ops.h"
 
 namespace kpop {
 
@@ -55,6 +55,7 @@ __global__ __launch_bounds__(256, 1) void within_tile_kernel(const double *__res
   const bool worker = rg < n_rg;
   const uint32_t ti = cg * 4, tj = (worker ? rg : 0) * TY;
   s_cnt[threadIdx.x] = 0;  // (kWMaxTJ == blockDim.x; the loop's barriers come before anybody adds)
+  // (the loop of pair_tile_distances, written out: built on it the kernel assembles to other arithmetic, profiles/self_tile_refactor.md)
   double acc[TY][4];
   pair_zero(acc);
   PairStage<kWMaxW, kWMaxTJ> stage;
@@ -235,32 +236,26 @@ struct WithinWork {
   uint64_t bytes;
 };
 static WithinWork within_carve(void *work, uint32_t r2, uint32_t n_dims, bool normalize, uint64_t capacity) {
-  char *base = reinterpret_cast<char *>(work);
-  uint64_t off = 0;
-  auto take = [&](uint64_t bytes) {
-    char *q = base + off;
-    off += (bytes + 255) & ~255ull;
-    return q;
-  };
+  Carver c(work);
   WithinWork w;
-  w.n2 = reinterpret_cast<double *>(take(normalize ? (uint64_t)r2 * 8 : 0));
-  w.b = reinterpret_cast<double *>(take(normalize ? (uint64_t)r2 * n_dims * 8 : 0));
-  w.cursor = reinterpret_cast<unsigned long long *>(take(256));
-  w.pool_d = reinterpret_cast<double *>(take(capacity * 8));
-  w.tmp_d = reinterpret_cast<double *>(take(capacity * 8));
-  w.pool_i = reinterpret_cast<uint32_t *>(take(capacity * 4));
-  w.pool_r = reinterpret_cast<uint32_t *>(take(capacity * 4));
-  w.pool_k = reinterpret_cast<uint32_t *>(take(capacity * 4));
-  w.tmp_i = reinterpret_cast<uint32_t *>(take(capacity * 4));
-  w.bytes = off + 256;
+  w.n2 = c.take<double>(normalize ? (uint64_t)r2 * 8 : 0);
+  w.b = c.take<double>(normalize ? (uint64_t)r2 * n_dims * 8 : 0);
+  w.cursor = c.take<unsigned long long>(256);
+  w.pool_d = c.take<double>(capacity * 8);
+  w.tmp_d = c.take<double>(capacity * 8);
+  w.pool_i = c.take<uint32_t>(capacity * 4);
+  w.pool_r = c.take<uint32_t>(capacity * 4);
+  w.pool_k = c.take<uint32_t>(capacity * 4);
+  w.tmp_i = c.take<uint32_t>(capacity * 4);
+  w.bytes = c.off + 256;
   return w;
 }
 
 template <int KIND>
 static int within_tiles(const double *a, uint32_t r1, const double *b, uint32_t r2, uint32_t n_dims, const double *metric, double p, double max_distance,
                         unsigned long long *counts, uint64_t capacity, const WithinWork &w, hipStream_t st) {
-  // the tiles of rowwise_block (distance.hip): 32 columns x 256 rows against a very long set, so that it is read from HBM once per 256
-  // query rows; balanced column tiles of 64..127 otherwise.  (The choice moves no bit: a pair's chain is one thread's either way.)
+  // the tiles of rowwise_block (distance.hip): against a very long set the long-set shape of the self-joins (self_shape, tri_tile.h),
+  // 32 columns x 256 rows; balanced column tiles of 64..127 otherwise, a choice of this file's own.  (It moves no bit.)
   if (r1 >= 65536 && r2 <= 4096) {
     within_tile_kernel<KIND, 8><<<dim3(div_up(r1, 32), div_up(r2, 256)), dim3(256), 0, st>>>(a, 32, r1, b, r2, n_dims, metric, p, max_distance, 8, 32, 0, counts, capacity,
                                                                                               w.cursor, w.pool_d, w.pool_i, w.pool_r, w.pool_k);
@@ -294,19 +289,14 @@ static int within_dev(kpop_refset *rs, const double *d_m2, uint32_t r2, double m
   const uint32_t D = rs->n_dims;
   const WithinWork w = within_carve(d_work, r2, D, rs->normalize != 0, capacity);
   KPOP_HIP(hipMemsetAsync(w.cursor, 0, 256, st));
-  const double *a = rs->rows, *b = d_m2;
-  if (rs->normalize) {  // the set's quotients from its copy, the query rows' from the norms' pass: prepare_operands' (distance.hip)
-    KPOP_TRY(rs->prepared(st));
-    KPOP_TRY(rs->divided(st, &a));
+  const double *a, *b = d_m2;
+  KPOP_TRY(refset_chain_rows(rs, st, &a));
+  if (rs->normalize) {  // the query rows' quotients from the norms' pass: prepare_operands' (distance.hip)
     KPOP_TRY(refset_query_norms(rs, d_m2, r2, w.n2, w.b, st));
     b = w.b;
   }
   unsigned long long *counts = reinterpret_cast<unsigned long long *>(d_out_offsets);
-  switch (rs->kind) {
-    case KPOP_EUCLIDEAN: KPOP_TRY(within_tiles<KPOP_EUCLIDEAN>(a, rs->r1, b, r2, D, rs->metric, rs->p, max_distance, counts, capacity, w, st)); break;
-    case KPOP_COSINE: KPOP_TRY(within_tiles<KPOP_COSINE>(a, rs->r1, b, r2, D, rs->metric, rs->p, max_distance, counts, capacity, w, st)); break;
-    default: KPOP_TRY(within_tiles<KPOP_MINKOWSKI>(a, rs->r1, b, r2, D, rs->metric, rs->p, max_distance, counts, capacity, w, st)); break;
-  }
+  KPOP_TRY(by_kind(rs->kind, [&](auto K) { return within_tiles<decltype(K)::value>(a, rs->r1, b, r2, D, rs->metric, rs->p, max_distance, counts, capacity, w, st); }));
   scan_block_sums_kernel<0><<<dim3(1), dim3(1024), 0, st>>>(d_out_offsets, r2);  // counts -> offsets in place, the total to [r2]
   KPOP_LAUNCH_CHECK();
   if (capacity == 0) return KPOP_OK;
@@ -377,9 +367,6 @@ extern "C" int kpop_neighbours_within(kpop_refset *rs, const double *m2, uint32_
 
 extern "C" int kpop_distance_within(const double *m1, uint32_t r1, const double *m2, uint32_t r2, uint32_t n_dims, const double *metric, int kind, double p,
                                     int normalize, double max_distance, uint64_t capacity, uint64_t *out_offsets, uint32_t *out_idx, double *out_dist) {
-  kpop_refset *rs = nullptr;
-  KPOP_TRY(kpop_refset_create(m1, r1, n_dims, metric, kind, p, normalize, 0, &rs));
-  const int rc = kpop_neighbours_within(rs, m2, r2, max_distance, capacity, out_offsets, out_idx, out_dist);
-  const int rc_free = kpop_refset_free(rs);
-  return rc ? rc : rc_free;
+  return with_temporary_refset(m1, r1, n_dims, metric, kind, p, normalize,
+                               [&](kpop_refset *rs) { return kpop_neighbours_within(rs, m2, r2, max_distance, capacity, out_offsets, out_idx, out_dist); });
 }
