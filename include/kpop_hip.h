@@ -912,6 +912,73 @@ int kpop_distance_dbscan(const double *m, uint32_t rows, uint32_t n_dims, const 
                          int normalize, double eps, uint32_t min_pts, uint32_t *labels, uint32_t *core_of,
                          uint32_t *degree, uint32_t *counts);
 
+/* ------------------------------------------------- mutual-reachability tree of a resident set (DBSCAN at every radius)
+ * kpop_dbscan wants eps up front; this is its partner, as kpop_spanning_forest is kpop_clusters_within's: one forest for a
+ * given min_pts, every eps by a cut -- the first stage of HDBSCAN*.  Distance, graph and NaN are the three blocks' above:
+ * d(j, i) is the reference chain's distance (lib/Space.ml:182-205 with the adaptors of lib/Matrix.ml:243-250) -- the bits
+ * kpop_refset_distance_rowwise writes under kpop_tune("distance_mfma", 0) when the set's own rows are the query --
+ * symmetric bit for bit, the pair i == j never examined; no kpop_tune setting is read.
+ * CORE DISTANCE, min_pts in 1 .. 129: core_dist[i] = +0 for min_pts = 1 (a row with a NaN in it too: its degree is 1);
+ * otherwise the (min_pts - 1)-th element of the multiset { d(i, j) : j != i, d a number } (+inf is a number) in ascending
+ * order, -0 taken as +0, a zero written as +0; the quiet NaN 0x7FF8000000000000 when the multiset has fewer elements
+ * (min_pts > r1, a row with a NaN in it, a set full of them).  For every eps that is a number: core_dist[i] <= eps iff
+ * kpop_dbscan's degree[i] >= min_pts.  min_pts = 0: KPOP_ERR_INVALID; min_pts > 129: KPOP_ERR_UNSUPPORTED.
+ * MUTUAL REACHABILITY: mr(i, j) = max(d(i, j), core_dist[i], core_dist[j]), compared as doubles, a zero as +0.  An edge
+ * i < j exists iff all three values are numbers and mr <= max_distance (+inf: every edge whose mr is a number, +inf
+ * included; negative: none; NaN: KPOP_ERR_INVALID).  Edges are ordered by (mr, i, j) ascending -- a strict total order,
+ * so the minimum spanning forest is UNIQUE, defined without reference to an algorithm, the same bits on every run, however
+ * often weights tie (every edge out of row i within core_dist[i] weighs at least that).  *n_edges; edge_i[e] < edge_j[e]
+ * with edge_dist[e] = mr, listed in that order, room r1 - 1 entries each (none for r1 <= 1); core_dist[r1] (may be
+ * NULL); labels[r1] (may be NULL): the smallest row index of each component of the forest.  r1 = 0: KPOP_OK and
+ * *n_edges = 0.  With min_pts = 1 the result is kpop_spanning_forest(rs, max_distance)'s, array for array.  A forest
+ * capped at T is the prefix of the uncapped one up to the last edge with mr <= T.
+ * THE CUT IS DBSCAN*: for any T <= max_distance, after uniting the ends of the edges with edge_dist <= T, a row with
+ * core_dist[i] <= T -- a core row of kpop_dbscan(T, min_pts) -- has exactly kpop_dbscan's label, the smallest core row
+ * index of its cluster, and every other row is a component of its own: border rows are NOT attached (DBSCAN*, the variant
+ * HDBSCAN is built on).  THERE IS NO known_rows, for kpop_dbscan's reason: a new row can lower old rows' core distances.
+ * Neither the r1 x r1 matrix nor a neighbour list longer than min_pts - 1 a row is formed.  The set's limits, slot and
+ * thread ownership hold as for every call on a set.  Semantics: INTEGRATION.md 6j; timings: profiles/reachability.md.  */
+/* (lib/Space.ml:182-205; lib/Matrix.ml:243-250, the order of lib/Matrix.ml:641-650 without the row itself.)  Host array
+   core_dist[r1].  Synchronises.                                                                                        */
+int kpop_core_distances(kpop_refset *rs, uint32_t min_pts, double *core_dist);
+/* bytes of d_work for kpop_dev_core_distances (lib/Space.ml:182-205 over the set against itself, see the block above), for
+   the set's r1 at the time of the call: the neighbour lists of one SLAB of 16,384 query rows (the last slab: what is left;
+   the larger of the two), a row (12 k + 8) bytes a column segment (1 or 2 for a full slab) plus 12 k + 16, k = min_pts - 1
+   -- 49 MiB at k = 128 however long the set; 256 for min_pts = 1 and min_pts > r1, which need no list; 0 for a min_pts
+   the call refuses                                                                                                     */
+uint64_t kpop_dev_core_distances_workspace_bytes(const kpop_refset *rs, uint32_t min_pts);
+/* (lib/Space.ml:182-205; lib/Matrix.ml:243-250.)  Enqueues only, reads nothing back, allocates nothing.  d_core_dist[r1].  */
+int kpop_dev_core_distances(kpop_refset *rs, uint32_t min_pts, void *d_work, double *d_core_dist, void *stream);
+/* (lib/Space.ml:182-205; lib/Matrix.ml:243-250.)  Host arrays.  Synchronises.                                           */
+int kpop_reachability_tree(kpop_refset *rs, uint32_t min_pts, double max_distance, uint32_t *n_edges, uint32_t *edge_i,
+                           uint32_t *edge_j, double *edge_dist, double *core_dist, uint32_t *labels);
+/* bytes of d_work for kpop_dev_reachability_tree (lib/Space.ml:182-205 over the set against itself, see the block above),
+   for the set's r1 at the time of the call: 8 bytes a row for the core distances, then the larger of
+   kpop_dev_core_distances_workspace_bytes and kpop_dev_spanning_forest_workspace_bytes (one after the other in one place) */
+uint64_t kpop_dev_reachability_tree_workspace_bytes(const kpop_refset *rs, uint32_t min_pts);
+/* (lib/Space.ml:182-205; lib/Matrix.ml:243-250.)  Enqueues only: the lists' two passes a slab, then ceil(log2 r1) rounds,
+   each of which returns at once when the round before added no edge; nothing is read back, nothing allocated.
+   d_n_edges[1], d_edge_i / d_edge_j / d_edge_dist[r1 - 1] (the first *d_n_edges written), d_core_dist[r1] or NULL,
+   d_labels[r1] or NULL.                                                                                                */
+int kpop_dev_reachability_tree(kpop_refset *rs, uint32_t min_pts, double max_distance, void *d_work, uint32_t *d_n_edges,
+                               uint32_t *d_edge_i, uint32_t *d_edge_j, double *d_edge_dist, double *d_core_dist,
+                               uint32_t *d_labels, void *stream);
+/* unprepared convenience (lib/Matrix.ml:191-266 for the distances, m against itself): a temporary set over m, then
+   kpop_reachability_tree                                                                                               */
+int kpop_distance_reachability_tree(const double *m, uint32_t rows, uint32_t n_dims, const double *metric, int kind,
+                                    double p, int normalize, uint32_t min_pts, double max_distance, uint32_t *n_edges,
+                                    uint32_t *edge_i, uint32_t *edge_j, double *edge_dist, double *core_dist,
+                                    uint32_t *labels);
+/* pure host arithmetic, no GPU and no kpop_init: ANY list of edges i < j < r1 cut at T -- the edges with edge_dist <= T
+   united (a NaN joins nothing), a row with core_dist[i] <= T given the smallest row index of its component, every other
+   row KPOP_NOISE.  counts[0]: the components that hold such a row; counts[1]: those rows; counts[2]: the noise rows.  Over
+   a forest of kpop_reachability_tree and T <= its max_distance: on every core row the label of kpop_dbscan(T, min_pts) over
+   the reference chain's distances (lib/Space.ml:182-205; lib/Matrix.ml:243-250), counts[0] and counts[1] its counts[0] and
+   counts[1]; its border rows are noise here.  KPOP_ERR_INVALID for a NaN T, a null array and an edge that is not
+   i < j < r1.                                                                                                          */
+int kpop_reachability_cut(uint32_t r1, uint32_t n_edges, const uint32_t *edge_i, const uint32_t *edge_j,
+                          const double *edge_dist, const double *core_dist, double T, uint32_t *labels, uint32_t *counts);
+
 /* ------------------------------------------------- k-mer database (KPopCountDB)
  * the operations of lib/KMerDB.ml that touch every count.  A database is the reference's
  * `storage: I32BAVector.t array` (lib/KMerDB.ml:54-63): n_cols spectra ("columns"), each a vector of n_rows int32

@@ -203,6 +203,16 @@ SIGNATURES = {
     "kpop_dev_dbscan_workspace_bytes": (C.c_uint64, [vp]),
     "kpop_dev_dbscan": (C.c_int, [vp, C.c_double, C.c_uint32, vp, vp, vp, vp, vp, vp]),
     "kpop_distance_dbscan": (C.c_int, [f64p, C.c_uint32, C.c_uint32, f64p, C.c_int, C.c_double, C.c_int, C.c_double, C.c_uint32, u32p, u32p, u32p, u32p]),
+    # the mutual-reachability tree: core distances, the forest under max(d, core_i, core_j), its cut (reachability.hip)
+    "kpop_core_distances": (C.c_int, [vp, C.c_uint32, f64p]),
+    "kpop_dev_core_distances_workspace_bytes": (C.c_uint64, [vp, C.c_uint32]),
+    "kpop_dev_core_distances": (C.c_int, [vp, C.c_uint32, vp, vp, vp]),
+    "kpop_reachability_tree": (C.c_int, [vp, C.c_uint32, C.c_double, u32p, u32p, u32p, f64p, f64p, u32p]),
+    "kpop_dev_reachability_tree_workspace_bytes": (C.c_uint64, [vp, C.c_uint32]),
+    "kpop_dev_reachability_tree": (C.c_int, [vp, C.c_uint32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "kpop_distance_reachability_tree": (C.c_int, [f64p, C.c_uint32, C.c_uint32, f64p, C.c_int, C.c_double, C.c_int, C.c_uint32, C.c_double, u32p, u32p, u32p,
+                                                  f64p, f64p, u32p]),
+    "kpop_reachability_cut": (C.c_int, [C.c_uint32, C.c_uint32, u32p, u32p, f64p, f64p, C.c_double, u32p, u32p]),
 }
 
 

@@ -901,6 +901,35 @@ class RefSet:
         n = int(n.value)
         return ei[:n], ej[:n], ed[:n], labels[:r1]
 
+    def core_distances(self, min_pts):
+        """Every row's core distance -> f64 [r1]: +0 for min_pts = 1, otherwise the distance to its (min_pts - 1)-th nearest OTHER row
+        (NaN distances are not counted, +inf is), NaN where a row has fewer.  core_distances(min_pts) <= eps iff dbscan(eps, min_pts)'s
+        degree >= min_pts.  min_pts in 1 .. 129 (kpop_core_distances, include/kpop_hip.h)."""
+        r1 = self.info()["r1"]
+        core = np.zeros(max(r1, 1), dtype=np.float64)
+        check(_lib.load().kpop_core_distances(self._h, _min_pts(min_pts), _p(core, C.c_double)))
+        return core[:r1]
+
+    def reachability_forest(self, min_pts, max_distance=float("inf")):
+        """The mutual-reachability forest of the set: DBSCAN at every radius -> (edge_i u32, edge_j u32, edge_dist f64, core_dist f64 [r1],
+        labels u32 [r1]).  An edge i < j weighs max(d(i, j), core_dist[i], core_dist[j]) and exists iff the three are numbers and the
+        weight is within max_distance; the result is the minimum spanning forest under the strict order (weight, i, j): unique, the same
+        bits on every run, the edges listed ascending; labels the smallest row index of each component.  min_pts = 1 gives
+        spanning_forest(max_distance).  reachability_cut of the edges at any T <= max_distance gives dbscan(T, min_pts)'s labels on the
+        core rows, every other row alone (DBSCAN*: border rows are not attached).  No earlier result is a valid start after append
+        (kpop_reachability_tree, include/kpop_hip.h)."""
+        r1 = self.info()["r1"]
+        room = max(r1 - 1, 1)
+        ei, ej = np.zeros(room, dtype=np.uint32), np.zeros(room, dtype=np.uint32)
+        ed = np.zeros(room, dtype=np.float64)
+        core = np.zeros(max(r1, 1), dtype=np.float64)
+        labels = np.zeros(max(r1, 1), dtype=np.uint32)
+        n = C.c_uint32()
+        check(_lib.load().kpop_reachability_tree(self._h, _min_pts(min_pts), float(max_distance), C.byref(n), _p(ei, C.c_uint32), _p(ej, C.c_uint32),
+                                                 _p(ed, C.c_double), _p(core, C.c_double), _p(labels, C.c_uint32)))
+        n = int(n.value)
+        return ei[:n], ej[:n], ed[:n], core[:r1], labels[:r1]
+
     def knn_vote(self, m2, class_of, k=5, n_classes=None):
         """The k-NN classifier of the reference's README on the device -> (cls u32, votes u32, n u32, first f64), one entry a row of m2.
         class_of: a class in [0, n_classes) for every row of the set (n_classes=None: the largest class + 1).  A row's list is its k
@@ -1392,3 +1421,68 @@ def forest_cut(r1, edge_i, edge_j, edge_dist, T):
     check(_lib.load().kpop_forest_cut(r1, n_edges, _p(_nz(ei, np.uint32), C.c_uint32), _p(_nz(ej, np.uint32), C.c_uint32),
                                       _p(_nz(ed, np.float64), C.c_double), float(T), _p(labels, C.c_uint32), C.byref(n)))
     return labels[:r1], int(n.value)
+
+
+def dev_core_distances_workspace_bytes(rs, min_pts):
+    """the size of d_work for dev_core_distances, for the set's r1 at the time of the call: the lists of one slab of rows"""
+    return int(_lib.load().kpop_dev_core_distances_workspace_bytes(rs.handle, _min_pts(min_pts)))
+
+
+def dev_core_distances(rs, min_pts, d_work, d_core_dist, stream=0):
+    """enqueue only: d_core_dist[r1] (f64)"""
+    check(_lib.load().kpop_dev_core_distances(rs.handle, _min_pts(min_pts), d_work, d_core_dist, stream))
+
+
+def dev_reachability_forest_workspace_bytes(rs, min_pts):
+    """the size of d_work for dev_reachability_forest, for the set's r1 at the time of the call"""
+    return int(_lib.load().kpop_dev_reachability_tree_workspace_bytes(rs.handle, _min_pts(min_pts)))
+
+
+def dev_reachability_forest(rs, min_pts, max_distance, d_work, d_n_edges, d_edge_i, d_edge_j, d_edge_dist, d_core_dist=None, d_labels=None, stream=0):
+    """enqueue only: d_n_edges[1] (u32), d_edge_i / d_edge_j (u32) and d_edge_dist (f64) of r1 - 1 entries each, the first
+    *d_n_edges written; d_core_dist[r1] (f64) or None; d_labels[r1] (u32) or None"""
+    check(_lib.load().kpop_dev_reachability_tree(rs.handle, _min_pts(min_pts), float(max_distance), d_work, d_n_edges, d_edge_i, d_edge_j, d_edge_dist,
+                                                 d_core_dist, d_labels, stream))
+
+
+def distance_reachability_forest(m, metric, kind=EUCLIDEAN, p=2.0, normalize=True, min_pts=1, max_distance=float("inf")):
+    """RefSet(m, ...).reachability_forest(min_pts, max_distance) without keeping the set: one call of kpop_distance_reachability_tree
+    -> (edge_i, edge_j, edge_dist, core_dist, labels)"""
+    m, metric = _c(m, np.float64), _c(metric, np.float64)
+    if m.ndim != 2 or m.shape[1] != len(metric):
+        raise ValueError("Incompatible_geometries")
+    rows = m.shape[0]
+    room = max(rows - 1, 1)
+    ei, ej = np.zeros(room, dtype=np.uint32), np.zeros(room, dtype=np.uint32)
+    ed = np.zeros(room, dtype=np.float64)
+    core = np.zeros(max(rows, 1), dtype=np.float64)
+    labels = np.zeros(max(rows, 1), dtype=np.uint32)
+    n = C.c_uint32()
+    check(_lib.load().kpop_distance_reachability_tree(_p(_nz(m, np.float64), C.c_double), rows, len(metric), _p(_nz(metric, np.float64), C.c_double),
+                                                      int(kind), float(p), 1 if normalize else 0, _min_pts(min_pts), float(max_distance), C.byref(n),
+                                                      _p(ei, C.c_uint32), _p(ej, C.c_uint32), _p(ed, C.c_double), _p(core, C.c_double),
+                                                      _p(labels, C.c_uint32)))
+    n = int(n.value)
+    return ei[:n], ej[:n], ed[:n], core[:rows], labels[:rows]
+
+
+def reachability_cut(r1, edge_i, edge_j, edge_dist, core_dist, T):
+    """A list of edges cut at T (the edges with edge_dist <= T united) -> (labels u32 [r1], counts u32 [3]): a row with core_dist <= T gets
+    the smallest row index of its component, every other row NOISE; counts: the components with such a row, those rows, the noise rows.
+    Host arithmetic alone: no GPU, no init.  Over a reachability_forest and T <= its max_distance: RefSet.dbscan(T, min_pts)'s labels on
+    every core row and its counts[0], counts[1]; its border rows are noise here (kpop_reachability_cut, include/kpop_hip.h)."""
+    ei = np.ascontiguousarray(edge_i, dtype=np.uint32)
+    ej = np.ascontiguousarray(edge_j, dtype=np.uint32)
+    ed = np.ascontiguousarray(edge_dist, dtype=np.float64)
+    core = np.ascontiguousarray(core_dist, dtype=np.float64)
+    if not (ei.ndim == ej.ndim == ed.ndim == 1 and len(ei) == len(ej) == len(ed)):
+        raise ValueError("edge_i, edge_j and edge_dist: three lists of one length")
+    r1, n_edges = int(r1), len(ei)
+    if core.shape != (r1,):
+        raise ValueError("core_dist: a core distance for each of the %d rows" % r1)
+    labels = np.zeros(max(r1, 1), dtype=np.uint32)
+    counts = np.zeros(3, dtype=np.uint32)
+    check(_lib.load().kpop_reachability_cut(r1, n_edges, _p(_nz(ei, np.uint32), C.c_uint32), _p(_nz(ej, np.uint32), C.c_uint32),
+                                            _p(_nz(ed, np.float64), C.c_double), _p(_nz(core, np.float64), C.c_double), float(T), _p(labels, C.c_uint32),
+                                            _p(counts, C.c_uint32)))
+    return labels[:r1], counts

@@ -32,10 +32,21 @@
 // radix sorts (radix_sort.h), the pair first, the distance's key second.
 // The tile loop is pair_tile.h's, the shapes and the lanes' reduction self_tile.h's, the union union_find.h's, the distance's key
 // space_ops.h's.
+//
+// The rounds under another weight.  forest_nearest_kernel takes what an edge weighs as a policy: ForestDistanceWeight, the distance
+// (an empty struct that compiles away: the kernel above), or ForestReachWeight, max(d, core_i, core_j) over per-row core distances --
+// the mutual-reachability forest of reachability.hip, which calls forest_dev through forest_rounds.h.  Nothing else of a round knows
+// what a key stands for, and the two claims the rounds rest on hold for any symmetric weight wt(r, c) that is a function of the
+// unordered pair alone (both checked again for the second policy):
+//   * for a fixed row r the edges {r, c} order by (wt, c): the order is (wt, min, max), and (min(r, c), max(r, c)) ascends with c
+//     whichever side of r the columns lie on (every c < r gives (c, r), below every (r, c') with c' > r) -- no property of wt is used;
+//   * a tile whose rows and columns all carry one label is skipped because it holds no pair of two components, whatever a pair weighs.
+// Weights tie far more often there (every edge out of row i within core_i weighs at least core_i); the strict order makes that harmless.
 #include <algorithm>
 
 #include "common.h"
 #include "distance_routes.h"
+#include "forest_rounds.h"
 #include "radix_sort.h"
 #include "refset_call.h"
 #include "self_tile.h"
@@ -79,16 +90,44 @@ __global__ __launch_bounds__(256) void forest_tile_labels_kernel(const uint32_t 
   }
 }
 
+// What an edge weighs.  The single-linkage tree: the distance -- every call folds away.  The mutual-reachability forest
+// (reachability.hip): max(d, core_i, core_j), core the rows' core distances; a thread holds its rows' for the launch and the tile's
+// four columns' for the tile.  weight(yy, x, d): the weight of the pair of the thread's yy-th row and x-th column, a NaN when it is
+// no edge -- tested value by value, because fmax drops a NaN operand instead of handing it on
+struct ForestDistanceWeight {
+  __device__ __forceinline__ void rows(const double *, uint32_t, uint32_t) {}
+  __device__ __forceinline__ void columns(const double *, uint32_t, uint32_t) {}
+  __device__ __forceinline__ double weight(int, int, double d) const { return d; }
+};
+template <int TY>
+struct ForestReachWeight {
+  double own[TY], col[4];
+  __device__ __forceinline__ void rows(const double *core, uint32_t jfirst, uint32_t j1) {
+#pragma unroll
+    for (int yy = 0; yy < TY; ++yy) own[yy] = jfirst + yy < j1 ? core[jfirst + yy] : 0.0;
+  }
+  __device__ __forceinline__ void columns(const double *core, uint32_t ifirst, uint32_t i1) {
+#pragma unroll
+    for (int x = 0; x < 4; ++x) col[x] = ifirst + x < i1 ? core[ifirst + x] : 0.0;
+  }
+  __device__ __forceinline__ double weight(int yy, int x, double d) const {
+    if (d != d || own[yy] != own[yy] || col[x] != col[x]) return __longlong_as_double(0x7FF8000000000000ll);
+    return fmax(fmax(d, col[x]), own[yy]);
+  }
+};
+
 // a: the set's rows as the chain reads them (divided by their norms when the set normalises), both operands.  Strip blockIdx.x:
 // rows j0 .. j0 + TJ, TJ = TY n_rg = kf w; segment blockIdx.y: the column tiles (w rows of the set each) t_begin .. t_end.  A thread
 // 4 columns x TY rows, the dimensions ascending in one thread, 16 at a time through LDS (pair_tile.h).  The next step's
 // operands -- the tile's next 16 dimensions, or the first of the next tile that is not skipped -- are loaded under the arithmetic.
-template <int KIND, int TY>
+// core: the rows' core distances, read by ForestReachWeight alone
+template <int KIND, int TY, class Weight>
 __global__ __launch_bounds__(256, 1) void forest_nearest_kernel(const double *__restrict__ a, uint32_t w, uint32_t r1, uint32_t n_dims,
                                                                 const double *__restrict__ metric, double p, double max_distance, uint32_t n_cg,
                                                                 uint32_t n_rg, uint32_t kf, uint32_t n_ct, uint32_t tiles_per_seg,
                                                                 const uint32_t *__restrict__ lab, const uint32_t *__restrict__ tile_lab,
-                                                                uint64_t *__restrict__ part_k, uint32_t *__restrict__ part_c, const uint32_t *gate) {
+                                                                uint64_t *__restrict__ part_k, uint32_t *__restrict__ part_c, const uint32_t *gate,
+                                                                const double *__restrict__ core) {
   FOREST_GATE();
   __shared__ __attribute__((aligned(16))) double As[kPairDC][kFMaxW + 2];
   __shared__ __attribute__((aligned(16))) double Bs[kPairDC][kFMaxTJ + 2];
@@ -116,6 +155,8 @@ __global__ __launch_bounds__(256, 1) void forest_nearest_kernel(const double *__
     best_k[yy] = kFNone;
     best_c[yy] = 0u;
   }
+  Weight wt;
+  wt.rows(core, j0 + tj, j1);
   PairStage<kFMaxW, kFMaxTJ> stage;
   uint32_t t = next_tile(t_begin);
   if (t < t_end) stage.load(a, t * w, min(r1, t * w + w), a, j0, j1, n_dims, 0, n_dims);
@@ -125,6 +166,7 @@ __global__ __launch_bounds__(256, 1) void forest_nearest_kernel(const double *__
     uint32_t li[4];
 #pragma unroll
     for (int x = 0; x < 4; ++x) li[x] = (i0 + ti + x < i1) ? lab[i0 + ti + x] : 0u;
+    wt.columns(core, i0 + ti, i1);
     double acc[TY][4];
     pair_zero(acc);
     for (uint32_t c0 = 0; c0 < n_dims; c0 += kPairDC) {
@@ -136,7 +178,7 @@ __global__ __launch_bounds__(256, 1) void forest_nearest_kernel(const double *__
       if (more || t_next < t_end) stage.load(a, ni0, min(r1, ni0 + w), a, j0, j1, n_dims, more ? c0 + kPairDC : 0u, n_dims);
       if (worker) pair_accumulate<KIND>(acc, As, Bs, s_metric, ti, tj, min((uint32_t)kPairDC, n_dims - c0), p);
     }
-    // the epilogue: the scaled distance against the bound (a NaN compares false: no edge), a row of another component only
+    // the epilogue: the pair's weight against the bound (a NaN compares false: no edge), a row of another component only
     // (which the row itself never is); columns ascend within the tile and from tile to tile, so that `below` alone keeps, among
     // equal keys, the least column
     if (worker) {
@@ -144,7 +186,7 @@ __global__ __launch_bounds__(256, 1) void forest_nearest_kernel(const double *__
       for (int yy = 0; yy < TY; ++yy)
 #pragma unroll
         for (int x = 0; x < 4; ++x) {
-          const double d = scale_distance<KIND>(acc[yy][x], p);
+          const double d = wt.weight(yy, x, scale_distance<KIND>(acc[yy][x], p));
           const uint32_t i = i0 + ti + x, j = j0 + tj + yy;
           if (j < j1 && i < i1 && li[x] != lj[yy] && d <= max_distance) {
             const uint64_t key = distance_key(d);
@@ -302,9 +344,10 @@ static ForestWork forest_carve(void *base, uint32_t r1) {
   return f;
 }
 
+// core set: the mutual-reachability weight over those core distances; not set: the distance
 template <int KIND>
-static int forest_nearest(const double *a, uint32_t r1, uint32_t n_dims, const double *metric, double p, double max_distance, const ForestWork &f,
-                          uint32_t *lab, uint32_t *n_seg_out, const uint32_t *gate, hipStream_t st) {
+static int forest_nearest(const double *a, uint32_t r1, uint32_t n_dims, const double *metric, double p, double max_distance, const double *core,
+                          const ForestWork &f, uint32_t *lab, uint32_t *n_seg_out, const uint32_t *gate, hipStream_t st) {
   const SelfShape s = self_shape(r1);
   const uint32_t w = s.w, n_ct = div_up(r1, w), strips = div_up(r1, s.TJ);
   // the columns in a few segments when the strips alone do not fill the chip twice over
@@ -317,8 +360,13 @@ static int forest_nearest(const double *a, uint32_t r1, uint32_t n_dims, const d
   if (strips > 0x7FFFFFFFu) KPOP_FAIL(KPOP_ERR_UNSUPPORTED, "kpop_dev_spanning_forest: %u rows", r1);
   const dim3 grid(strips, n_seg);
   by_shape_rows(s, [&](auto TY) {
-    forest_nearest_kernel<KIND, decltype(TY)::value><<<grid, dim3(256), 0, st>>>(a, w, r1, n_dims, metric, p, max_distance, s.n_cg, s.n_rg, s.kf, n_ct, tiles_per_seg, lab,
-                                                                                f.tile_lab, f.part_k, f.part_c, gate);
+    constexpr int ty = decltype(TY)::value;
+    if (core)
+      forest_nearest_kernel<KIND, ty, ForestReachWeight<ty>><<<grid, dim3(256), 0, st>>>(a, w, r1, n_dims, metric, p, max_distance, s.n_cg, s.n_rg, s.kf, n_ct,
+                                                                                        tiles_per_seg, lab, f.tile_lab, f.part_k, f.part_c, gate, core);
+    else
+      forest_nearest_kernel<KIND, ty, ForestDistanceWeight><<<grid, dim3(256), 0, st>>>(a, w, r1, n_dims, metric, p, max_distance, s.n_cg, s.n_rg, s.kf, n_ct,
+                                                                                       tiles_per_seg, lab, f.tile_lab, f.part_k, f.part_c, gate, nullptr);
   });
   KPOP_LAUNCH_CHECK();
   return 0;
@@ -331,9 +379,10 @@ static uint32_t forest_rounds(uint32_t r1) {  // ceil(log2 r1)
 }
 
 // the body of both entry points.  host_reads: after a round, wait for the word that says what it added and stop at zero;
-// otherwise enqueues only
-static int forest_dev(kpop_refset *rs, double max_distance, void *d_work, uint32_t *d_n_edges, uint32_t *d_edge_i, uint32_t *d_edge_j, double *d_edge_dist,
-                      uint32_t *d_labels, hipStream_t st, bool host_reads, const char *who) {
+// otherwise enqueues only.  d_core set: the edges weigh max(d, core_i, core_j) over those r1 core distances (forest_rounds.h: for
+// reachability.hip)
+int forest_dev(kpop_refset *rs, const double *d_core, double max_distance, void *d_work, uint32_t *d_n_edges, uint32_t *d_edge_i, uint32_t *d_edge_j,
+                      double *d_edge_dist, uint32_t *d_labels, hipStream_t st, bool host_reads, const char *who) {
   if (max_distance != max_distance) KPOP_FAIL(KPOP_ERR_INVALID, "%s: the distance is not a number", who);
   if (!d_n_edges) KPOP_FAIL(KPOP_ERR_INVALID, "%s: null count", who);
   KPOP_HIP(hipMemsetAsync(d_n_edges, 0, 4, st));
@@ -353,7 +402,7 @@ static int forest_dev(kpop_refset *rs, double max_distance, void *d_work, uint32
   for (uint32_t k = 0; k < rounds; ++k) {
     const uint32_t *gate = k ? f.words + (k - 1) : nullptr;
     uint32_t n_seg = 1;
-    KPOP_TRY(by_kind(rs->kind, [&](auto K) { return forest_nearest<decltype(K)::value>(a, r1, rs->n_dims, rs->metric, rs->p, max_distance, f, lab, &n_seg, gate, st); }));
+    KPOP_TRY(by_kind(rs->kind, [&](auto K) { return forest_nearest<decltype(K)::value>(a, r1, rs->n_dims, rs->metric, rs->p, max_distance, d_core, f, lab, &n_seg, gate, st); }));
     forest_row_min_kernel<<<dim3(rows_grid), dim3(256), 0, st>>>(f.part_k, f.part_c, n_seg, r1, lab, f.comp_k, gate);
     KPOP_LAUNCH_CHECK();
     forest_comp_edge_kernel<<<dim3(rows_grid), dim3(256), 0, st>>>(f.part_k, f.part_c, r1, lab, f.comp_k, f.comp_e, gate);
@@ -386,6 +435,8 @@ static int forest_dev(kpop_refset *rs, double max_distance, void *d_work, uint32
   return KPOP_OK;
 }
 
+uint64_t forest_workspace_bytes(uint32_t r1) { return forest_carve(nullptr, r1).bytes; }
+
 }  // namespace kpop
 
 using namespace kpop;
@@ -400,7 +451,7 @@ extern "C" int kpop_dev_spanning_forest(kpop_refset *rs, double max_distance, vo
   const char *who = "kpop_dev_spanning_forest";
   KPOP_TRY(refset_check_handle(rs, who));
   if (!d_work) KPOP_FAIL(KPOP_ERR_INVALID, "%s: null workspace", who);
-  return forest_dev(rs, max_distance, d_work, d_n_edges, d_edge_i, d_edge_j, d_edge_dist, d_labels, as_stream(stream), false, who);
+  return forest_dev(rs, nullptr, max_distance, d_work, d_n_edges, d_edge_i, d_edge_j, d_edge_dist, d_labels, as_stream(stream), false, who);
 }
 
 extern "C" int kpop_spanning_forest(kpop_refset *rs, double max_distance, uint32_t *n_edges, uint32_t *edge_i, uint32_t *edge_j, double *edge_dist,
@@ -422,7 +473,7 @@ extern "C" int kpop_spanning_forest(kpop_refset *rs, double max_distance, uint32
   KPOP_TRY(dj.alloc(m * 4));
   KPOP_TRY(dd.alloc(m * 8));
   KPOP_TRY(dl.alloc((uint64_t)r1 * 4));
-  KPOP_TRY(forest_dev(rs, max_distance, work.p, dn.as<uint32_t>(), di.as<uint32_t>(), dj.as<uint32_t>(), dd.as<double>(), dl.as<uint32_t>(), st, true, who));
+  KPOP_TRY(forest_dev(rs, nullptr, max_distance, work.p, dn.as<uint32_t>(), di.as<uint32_t>(), dj.as<uint32_t>(), dd.as<double>(), dl.as<uint32_t>(), st, true, who));
   uint32_t n = 0;
   KPOP_HIP(hipMemcpyAsync(&n, dn.p, 4, hipMemcpyDeviceToHost, st));
   KPOP_HIP(hipStreamSynchronize(st));

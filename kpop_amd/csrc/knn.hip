@@ -429,11 +429,12 @@ __global__ __launch_bounds__(64) void knn_vote_kernel(const uint64_t *__restrict
 }
 
 // the three passes over the pairs.  LEAVE_OUT: the query rows are rows first_row .. first_row + r2 of the set a, without the rows that
-// group_of leaves out of each list (knn_validate.hip); otherwise the rows of b, and group_of and first_row are not read
+// group_of leaves out of each list (knn_validate.hip); otherwise the rows of b, and group_of and first_row are not read.  ties false:
+// the first two alone -- the merged lists and their last keys, for a caller that wants the k-th key and not the k-th key's members
 template <int KIND, int TY, int W, bool LEAVE_OUT>
 static int knn_passes(const double *a, uint32_t r1, const double *b, uint32_t r2, uint32_t n_dims, const double *metric, double p, uint32_t k,
                       const uint32_t *group_of, uint32_t first_row, const uint32_t *class_of, uint32_t n_classes, const KnnWork &w, uint32_t *n_seg_out,
-                      hipStream_t st) {
+                      bool ties, hipStream_t st) {
   using Who = std::conditional_t<LEAVE_OUT, KnnvLeftOut<TY>, KnnNobodyLeftOut>;
   constexpr uint32_t TJ = KnnShape<TY, W>::TJ;
   const uint32_t n_ct = div_up(r1, W), strips = div_up(r2, TJ);
@@ -446,6 +447,7 @@ static int knn_passes(const double *a, uint32_t r1, const double *b, uint32_t r2
   KPOP_LAUNCH_CHECK();
   knn_merge_kernel<<<dim3(std::min(r2, 1u << 20)), dim3(64), 0, st>>>(w.seg_key, w.seg_idx, w.seg_n, w.seg_drop, n_seg, r2, k, w.m_key, w.m_idx, w.m_n, w.m_tau, w.m_flag);
   KPOP_LAUNCH_CHECK();
+  if (!ties) return 0;
   knn_ties_kernel<KIND, TY, W, Who><<<grid, dim3(256), 0, st>>>(a, r1, b, r2, n_dims, metric, p, n_ct, tiles_per_seg, group_of, first_row, class_of, n_classes, w.m_tau,
                                                                 w.m_flag, w.tie_total, w.tie_count, w.tie_first);
   KPOP_LAUNCH_CHECK();
@@ -455,31 +457,37 @@ static int knn_passes(const double *a, uint32_t r1, const double *b, uint32_t r2
 template <int KIND, bool LEAVE_OUT>
 static int knn_passes_of(const double *a, uint32_t r1, const double *b, uint32_t r2, uint32_t n_dims, const double *metric, double p, uint32_t k,
                          const uint32_t *group_of, uint32_t first_row, const uint32_t *class_of, uint32_t n_classes, const KnnWork &w, uint32_t *n_seg,
-                         hipStream_t st) {
+                         bool ties, hipStream_t st) {
   const uint32_t TJ = knn_strip_rows(k);
-  if (TJ == 64) return knn_passes<KIND, 4, 64, LEAVE_OUT>(a, r1, b, r2, n_dims, metric, p, k, group_of, first_row, class_of, n_classes, w, n_seg, st);
-  if (TJ == 32) return knn_passes<KIND, 2, 64, LEAVE_OUT>(a, r1, b, r2, n_dims, metric, p, k, group_of, first_row, class_of, n_classes, w, n_seg, st);
-  return knn_passes<KIND, 1, 64, LEAVE_OUT>(a, r1, b, r2, n_dims, metric, p, k, group_of, first_row, class_of, n_classes, w, n_seg, st);
+  if (TJ == 64) return knn_passes<KIND, 4, 64, LEAVE_OUT>(a, r1, b, r2, n_dims, metric, p, k, group_of, first_row, class_of, n_classes, w, n_seg, ties, st);
+  if (TJ == 32) return knn_passes<KIND, 2, 64, LEAVE_OUT>(a, r1, b, r2, n_dims, metric, p, k, group_of, first_row, class_of, n_classes, w, n_seg, ties, st);
+  return knn_passes<KIND, 1, 64, LEAVE_OUT>(a, r1, b, r2, n_dims, metric, p, k, group_of, first_row, class_of, n_classes, w, n_seg, ties, st);
 }
 
 template <bool LEAVE_OUT>
 static int knn_passes_of_kind(int kind, const double *a, uint32_t r1, const double *b, uint32_t r2, uint32_t n_dims, const double *metric, double p, uint32_t k,
                               const uint32_t *group_of, uint32_t first_row, const uint32_t *class_of, uint32_t n_classes, const KnnWork &w, uint32_t *n_seg,
-                              hipStream_t st) {
+                              bool ties, hipStream_t st) {
   return by_kind(kind, [&](auto K) {
-    return knn_passes_of<decltype(K)::value, LEAVE_OUT>(a, r1, b, r2, n_dims, metric, p, k, group_of, first_row, class_of, n_classes, w, n_seg, st);
+    return knn_passes_of<decltype(K)::value, LEAVE_OUT>(a, r1, b, r2, n_dims, metric, p, k, group_of, first_row, class_of, n_classes, w, n_seg, ties, st);
   });
 }
 
 // (knn_lists.h) the three passes as knn_dev launches them, and with rows left out: for knn_validate.hip
 int knn_run_passes(int kind, const double *a, uint32_t r1, const double *b, uint32_t r2, uint32_t n_dims, const double *metric, double p, uint32_t k,
                    const uint32_t *class_of, uint32_t n_classes, const KnnWork &w, uint32_t *n_seg, hipStream_t st) {
-  return knn_passes_of_kind<false>(kind, a, r1, b, r2, n_dims, metric, p, k, nullptr, 0, class_of, n_classes, w, n_seg, st);
+  return knn_passes_of_kind<false>(kind, a, r1, b, r2, n_dims, metric, p, k, nullptr, 0, class_of, n_classes, w, n_seg, true, st);
 }
 int knn_run_leave_out_passes(int kind, const double *a, uint32_t r1, uint32_t first_row, uint32_t n_rows, uint32_t n_dims, const double *metric, double p,
                              uint32_t k, const uint32_t *group_of, const uint32_t *class_of, uint32_t n_classes, const KnnWork &w, uint32_t *n_seg,
                              hipStream_t st) {
-  return knn_passes_of_kind<true>(kind, a, r1, a + (uint64_t)first_row * n_dims, n_rows, n_dims, metric, p, k, group_of, first_row, class_of, n_classes, w, n_seg, st);
+  return knn_passes_of_kind<true>(kind, a, r1, a + (uint64_t)first_row * n_dims, n_rows, n_dims, metric, p, k, group_of, first_row, class_of, n_classes, w, n_seg, true, st);
+}
+// (knn_lists.h) the leave-self-out lists alone: knn_nearest_kernel with every row left out of its own list, then knn_merge_kernel.
+// w.m_n, w.m_tau hold every row's length and last key; no class array is read and no tie table written (reachability.hip)
+int knn_run_leave_self_out_lists(int kind, const double *a, uint32_t r1, uint32_t first_row, uint32_t n_rows, uint32_t n_dims, const double *metric, double p,
+                                 uint32_t k, const KnnWork &w, uint32_t *n_seg, hipStream_t st) {
+  return knn_passes_of_kind<true>(kind, a, r1, a + (uint64_t)first_row * n_dims, n_rows, n_dims, metric, p, k, nullptr, first_row, nullptr, 0, w, n_seg, false, st);
 }
 
 // the body of both entry points: enqueues only

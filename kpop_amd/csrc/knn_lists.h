@@ -138,7 +138,7 @@ static KnnWork knn_carve(void *work, uint32_t r2, uint32_t k, uint32_t n_classes
   return w;
 }
 
-static int knn_check_sizes(uint32_t k, uint32_t n_classes, const char *who) {
+static inline int knn_check_sizes(uint32_t k, uint32_t n_classes, const char *who) {
   if (k == 0) KPOP_FAIL(KPOP_ERR_INVALID, "%s: k = 0", who);
   if (k > (uint32_t)kKMaxK) KPOP_FAIL(KPOP_ERR_UNSUPPORTED, "%s: k = %u (at most %d)", who, k, kKMaxK);
   if (n_classes == 0) KPOP_FAIL(KPOP_ERR_INVALID, "%s: no classes", who);
@@ -154,5 +154,9 @@ int knn_run_passes(int kind, const double *a, uint32_t r1, const double *b, uint
 int knn_run_leave_out_passes(int kind, const double *a, uint32_t r1, uint32_t first_row, uint32_t n_rows, uint32_t n_dims, const double *metric, double p,
                              uint32_t k, const uint32_t *group_of, const uint32_t *class_of, uint32_t n_classes, const KnnWork &w, uint32_t *n_seg,
                              hipStream_t st);
+// the first two of them alone, every row left out of its own list: w.m_n, w.m_tau are each row's length and last (k-th) key.  No
+// class array, no tie table: the tie pass settles WHICH rows share the k-th key, never its value (reachability.hip's core distances)
+int knn_run_leave_self_out_lists(int kind, const double *a, uint32_t r1, uint32_t first_row, uint32_t n_rows, uint32_t n_dims, const double *metric, double p,
+                                 uint32_t k, const KnnWork &w, uint32_t *n_seg, hipStream_t st);
 
 }  // namespace kpop
