@@ -979,6 +979,68 @@ int kpop_distance_reachability_tree(const double *m, uint32_t rows, uint32_t n_d
 int kpop_reachability_cut(uint32_t r1, uint32_t n_edges, const uint32_t *edge_i, const uint32_t *edge_j,
                           const double *edge_dist, const double *core_dist, double T, uint32_t *labels, uint32_t *counts);
 
+/* ------------------------------------------------- silhouette and medoids of a labelled resident set, in one pass
+ * The calls above PRODUCE row labels; this one judges a labelling without ground truth (Rousseeuw 1987) and names one real
+ * row per class.  class_of[r1]: a class in [0, n_classes), or KPOP_NO_CLASS for a row that is LEFT OUT -- it is in no sum
+ * and nothing is computed for it (KPOP_NOISE == KPOP_NO_CLASS: kpop_dbscan's noise rows leave themselves out).  d(j, i) is
+ * the reference chain's distance (lib/Space.ml:182-205 with the adaptors of lib/Matrix.ml:243-250) -- the bits
+ * kpop_refset_distance_rowwise writes under kpop_tune("distance_mfma", 0) when the set's own rows are the query; the pair
+ * i == j is never examined; no kpop_tune setting is read.  With n_c the rows of class c, for a row j of class c:
+ *   own_mean[j]     the sum of d(j, i) over the rows i != j of c, divided by n_c - 1; +0 when n_c == 1
+ *   other_mean[j], other_class[j]   over the classes c' != c with n_c' > 0, the least (sum of d(j, i) over c') / n_c' and
+ *                   that class; ties go to the smaller class number, a NaN mean is never the least; no such class (or
+ *                   every such mean a NaN): the quiet NaN 0x7FF8000000000000 and KPOP_NO_CLASS
+ *   silhouette[j]   (other_mean - own_mean) / max(own_mean, other_mean) as IEEE arithmetic gives it (a NaN operand, 0/0
+ *                   and inf/inf give NaN), a zero written as +0; +0 when n_c == 1 (Rousseeuw's convention)
+ * A row left out gets NaN, NaN, KPOP_NO_CLASS, NaN.  A NaN distance is not skipped: it poisons the sums it is in; the way
+ * to keep a row with a NaN in it out is to leave it out.  For a class c: class_rows[c] = n_c; medoid[c] the member least
+ * under (own_mean with -0 taken as +0, row index) among the members whose own_mean is a number, medoid_mean[c] that row's
+ * own_mean, bits kept; an empty class, or one with no such member: KPOP_NO_CLASS and NaN.
+ * THE SUMS are f64 sums in an order that is a fixed function of r1, n_dims and the members' row indices: no floating-point
+ * atomic, nothing that depends on timing.  (a) The same bits on every run.  (b) The bits of own_mean, other_mean,
+ * silhouette and medoid_mean do not change when the classes are renumbered; other_class and medoid move with the
+ * renumbering.  (c) A sum has at most r1 non-negative terms: it lies within r1 2^-53 relative of the exact sum, and is
+ * exact wherever all terms and partial sums are representable.
+ * ERRORS: n_classes == 0: KPOP_ERR_INVALID; n_classes > 65,535: KPOP_ERR_UNSUPPORTED (kpop_knn_vote's limit); r1 = 0:
+ * KPOP_OK.  Every output pointer may be NULL.  THERE IS NO known_rows: a new row changes every mean; after
+ * kpop_refset_append the call is made again in full.  THE COST is the full rectangle, r1^2 pairs, twice
+ * kpop_clusters_within's triangle: the symmetric half is not exploited (column-side sums that stay deterministic would need
+ * a table of partial sums per tile).  Neither the r1 x r1 matrix nor an r1 x n_classes table is formed.  The set's limits,
+ * slot and thread ownership hold as for every call on a set.  MEASURED (profiles/silhouette.md; 100,000 rows in 1,000
+ * classes, beside kpop_dev_clusters_within at 0.3 in the same process): 156 ms against 49.7 at 64 dimensions, a ratio of
+ * 3.14; 3.80 s against 1.07 at 1,635 dimensions, 3.55 -- by pair count 2; a column tile holds one class, and classes of
+ * 38 to 204 rows fill 86.5 % of their tiles.  Semantics: INTEGRATION.md 6k. */
+/* (lib/Space.ml:182-205; lib/Matrix.ml:243-250.)  Host arrays: class_of[r1]; own_mean, other_mean, other_class,
+   silhouette [r1]; class_rows, medoid, medoid_mean [n_classes].  A class_of[i] >= n_classes that is not KPOP_NO_CLASS is
+   KPOP_ERR_INVALID.  Synchronises.                                                                                     */
+int kpop_silhouette(kpop_refset *rs, const uint32_t *class_of, uint32_t n_classes, double *own_mean, double *other_mean,
+                    uint32_t *other_class, double *silhouette, uint32_t *class_rows, uint32_t *medoid,
+                    double *medoid_mean);
+/* bytes of d_work for kpop_dev_silhouette (lib/Space.ml:182-205 over the set against itself, see the block above), for the
+   set's r1 at the time of the call: the rows grouped by class (the sort's keys and indices, its scratch), a row's own
+   mean and 12 bytes for each of up to 16 column segments, the column tiles (16 bytes each, at most r1 / w + n_classes + 1
+   of them) and 32 bytes a class -- O(r1 + n_classes), 10.6 MB for 100,000 rows in 1,000 classes; no copy of rows; 0 for
+   an n_classes the call refuses                                                                                        */
+uint64_t kpop_dev_silhouette_workspace_bytes(const kpop_refset *rs, uint32_t n_classes);
+/* (lib/Space.ml:182-205; lib/Matrix.ml:243-250.)  Enqueues only, reads nothing back, allocates nothing.  d_class_of[r1] is
+   TRUSTED and guarded: an entry >= n_classes counts as left out.  The outputs as above, on the device, each or NULL.    */
+int kpop_dev_silhouette(kpop_refset *rs, const uint32_t *d_class_of, uint32_t n_classes, void *d_work, double *d_own_mean,
+                        double *d_other_mean, uint32_t *d_other_class, double *d_silhouette, uint32_t *d_class_rows,
+                        uint32_t *d_medoid, double *d_medoid_mean, void *stream);
+/* unprepared convenience (lib/Matrix.ml:191-266 over lib/Space.ml:182-205 for the distances, m against itself): a
+   temporary set over m, then kpop_silhouette                                                                           */
+int kpop_distance_silhouette(const double *m, uint32_t rows, uint32_t n_dims, const double *metric, int kind, double p,
+                             int normalize, const uint32_t *class_of, uint32_t n_classes, double *own_mean,
+                             double *other_mean, uint32_t *other_class, double *silhouette, uint32_t *class_rows,
+                             uint32_t *medoid, double *medoid_mean);
+/* pure host arithmetic, no GPU and no kpop_init: the mean silhouette (of kpop_silhouette over the reference chain's
+   distances, lib/Space.ml:182-205, or any other) of each class, class_mean[n_classes], and of all the rows that are not
+   left out, *overall_mean; both summed in ascending row order, which is the contract; an empty class, and no row at all,
+   give NaN.  KPOP_ERR_INVALID for a null pointer, n_classes == 0 and a class_of[i] >= n_classes that is not
+   KPOP_NO_CLASS; n_classes > 65,535: KPOP_ERR_UNSUPPORTED.                                                              */
+int kpop_silhouette_summary(uint32_t r1, const uint32_t *class_of, uint32_t n_classes, const double *silhouette,
+                            double *class_mean, double *overall_mean);
+
 /* ------------------------------------------------- k-mer database (KPopCountDB)
  * the operations of lib/KMerDB.ml that touch every count.  A database is the reference's
  * `storage: I32BAVector.t array` (lib/KMerDB.ml:54-63): n_cols spectra ("columns"), each a vector of n_rows int32

@@ -17,7 +17,8 @@ from .api import (check, COSINE, DNA_DS, DNA_SS, PROTEIN, EUCLIDEAN, METRIC_FLAT
                   dev_knn_vote_ks, dev_knn_validate_workspace_bytes, dev_knn_validate, distance_knn_validate, confusion_matrix,
                   dev_representatives_within_workspace_bytes, dev_representatives_within, distance_representatives, NOISE,
                   dev_dbscan_workspace_bytes, dev_dbscan, distance_dbscan, dev_core_distances_workspace_bytes, dev_core_distances,
-                  dev_reachability_forest_workspace_bytes, dev_reachability_forest, distance_reachability_forest, reachability_cut)
+                  dev_reachability_forest_workspace_bytes, dev_reachability_forest, distance_reachability_forest, reachability_cut,
+                  Silhouette, dev_silhouette_workspace_bytes, dev_silhouette, distance_silhouette, silhouette_summary, dense_labels)
 
 __all__ = ["init", "device_count", "count_reads", "Twister", "ca", "metric_compute", "distance_rowwise",
            "distance_summary", "embeddings", "splits_gaps", "summarize_distances", "parse_distance", "KPopError", "DNA_DS", "DNA_SS", "PROTEIN", "EUCLIDEAN", "COSINE",
@@ -32,4 +33,5 @@ __all__ = ["init", "device_count", "count_reads", "Twister", "ca", "metric_compu
            "dev_knn_validate_workspace_bytes", "dev_knn_validate", "distance_knn_validate", "confusion_matrix",
            "dev_representatives_within_workspace_bytes", "dev_representatives_within", "distance_representatives", "NOISE",
            "dev_dbscan_workspace_bytes", "dev_dbscan", "distance_dbscan", "dev_core_distances_workspace_bytes", "dev_core_distances",
-           "dev_reachability_forest_workspace_bytes", "dev_reachability_forest", "distance_reachability_forest", "reachability_cut"]
+           "dev_reachability_forest_workspace_bytes", "dev_reachability_forest", "distance_reachability_forest", "reachability_cut",
+           "Silhouette", "dev_silhouette_workspace_bytes", "dev_silhouette", "distance_silhouette", "silhouette_summary", "dense_labels"]

@@ -213,6 +213,13 @@ SIGNATURES = {
     "kpop_distance_reachability_tree": (C.c_int, [f64p, C.c_uint32, C.c_uint32, f64p, C.c_int, C.c_double, C.c_int, C.c_uint32, C.c_double, u32p, u32p, u32p,
                                                   f64p, f64p, u32p]),
     "kpop_reachability_cut": (C.c_int, [C.c_uint32, C.c_uint32, u32p, u32p, f64p, f64p, C.c_double, u32p, u32p]),
+    # the silhouette and the medoids of a labelled set (silhouette.hip)
+    "kpop_silhouette": (C.c_int, [vp, u32p, C.c_uint32, f64p, f64p, u32p, f64p, u32p, u32p, f64p]),
+    "kpop_dev_silhouette_workspace_bytes": (C.c_uint64, [vp, C.c_uint32]),
+    "kpop_dev_silhouette": (C.c_int, [vp, vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "kpop_distance_silhouette": (C.c_int, [f64p, C.c_uint32, C.c_uint32, f64p, C.c_int, C.c_double, C.c_int, u32p, C.c_uint32, f64p, f64p, u32p, f64p, u32p,
+                                           u32p, f64p]),
+    "kpop_silhouette_summary": (C.c_int, [C.c_uint32, u32p, C.c_uint32, f64p, f64p, f64p]),
 }
 
 

@@ -10,6 +10,7 @@ Names follow the reference (PaoloRibeca/KPop):
 Everything here is plumbing (numpy <-> pointers); the arithmetic runs in the
 HIP kernels of libkpop_hip.so.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -885,6 +886,21 @@ class RefSet:
                                       _p(counts, C.c_uint32)))
         return labels[:r1], core_of[:r1], degree[:r1], counts
 
+    def silhouette(self, class_of, n_classes=None):
+        """The silhouette and the medoids of the set under a labelling -> Silhouette(own_mean f64 [r1], other_mean f64 [r1], other_class
+        u32 [r1], silhouette f64 [r1], class_rows u32 [n_classes], medoid u32 [n_classes], medoid_mean f64 [n_classes]).  class_of[i] is a
+        class in [0, n_classes) or NO_CLASS (== NOISE): the row is left out of every sum and gets NaN, NaN, NO_CLASS, NaN.  own_mean: the
+        mean distance to the other rows of the row's class (+0 alone); other_mean, other_class: the least mean distance to another class
+        and that class (ties to the smaller class); silhouette: (other - own) / max(own, other), +0 for a row alone in its class; medoid:
+        the member of a class with the least own_mean (ties to the smaller row), medoid_mean that mean.  The same bits on every run and
+        under any renumbering of the classes.  n_classes None: one more than the largest class.  No earlier result is a valid start:
+        after append the call is made again in full (kpop_silhouette, include/kpop_hip.h)."""
+        r1 = self.info()["r1"]
+        class_of, n_classes = _left_out_classes(class_of, r1, n_classes)
+        res = _silhouette_result(r1, n_classes)
+        check(_lib.load().kpop_silhouette(self._h, _p(_nz(class_of, np.uint32), C.c_uint32), n_classes, *_silhouette_pointers(res)))
+        return _silhouette_cut(res, r1, n_classes)
+
     def spanning_forest(self, max_distance=float("inf")):
         """The single-linkage tree of the set: the minimum spanning forest of the graph that joins rows i < j iff d(j, i) <= max_distance,
         under the order (d, i, j) -> (edge_i u32, edge_j u32, edge_dist f64, labels u32 [r1]).  The order is strict, so the forest is
@@ -1486,3 +1502,93 @@ def reachability_cut(r1, edge_i, edge_j, edge_dist, core_dist, T):
                                             _p(_nz(ed, np.float64), C.c_double), _p(_nz(core, np.float64), C.c_double), float(T), _p(labels, C.c_uint32),
                                             _p(counts, C.c_uint32)))
     return labels[:r1], counts
+
+
+Silhouette = collections.namedtuple("Silhouette", "own_mean other_mean other_class silhouette class_rows medoid medoid_mean")
+
+
+def _left_out_classes(class_of, r1, n_classes):
+    """_classes where NO_CLASS leaves a row out: it does not count towards the number of classes"""
+    class_of = np.asarray(class_of)
+    if class_of.ndim != 1 or len(class_of) != r1:
+        raise ValueError("class_of: one class, or NO_CLASS, for each of the set's %d rows" % r1)
+    if len(class_of) and (class_of.min() < 0 or class_of.max() > 0xFFFFFFFF):
+        raise ValueError("class_of: classes are uint32")
+    class_of = _c(class_of, np.uint32)
+    if n_classes is None:
+        kept = class_of[class_of != NO_CLASS]
+        n_classes = int(kept.max()) + 1 if len(kept) else 1
+    n_classes = int(n_classes)
+    if not 0 <= n_classes <= 0xFFFFFFFF:
+        raise ValueError("n_classes: a count of classes")
+    return class_of, n_classes
+
+
+def _silhouette_result(r1, n_classes):
+    rows, classes = max(r1, 1), max(min(n_classes, 65536), 1)  # (the library refuses more classes before it writes)
+    return Silhouette(np.zeros(rows, dtype=np.float64), np.zeros(rows, dtype=np.float64), np.zeros(rows, dtype=np.uint32), np.zeros(rows, dtype=np.float64),
+                      np.zeros(classes, dtype=np.uint32), np.zeros(classes, dtype=np.uint32), np.zeros(classes, dtype=np.float64))
+
+
+def _silhouette_pointers(res):
+    return [_p(x, C.c_double if x.dtype == np.float64 else C.c_uint32) for x in res]
+
+
+def _silhouette_cut(res, r1, n_classes):
+    return Silhouette(*[x[:r1] for x in res[:4]], *[x[:n_classes] for x in res[4:]])
+
+
+def dev_silhouette_workspace_bytes(rs, n_classes):
+    """the size of d_work for dev_silhouette, for the set's r1 at the time of the call; 0 for an n_classes the call refuses"""
+    return int(_lib.load().kpop_dev_silhouette_workspace_bytes(rs.handle, int(n_classes)))
+
+
+def dev_silhouette(rs, d_class_of, n_classes, d_work, d_own_mean=None, d_other_mean=None, d_other_class=None, d_silhouette=None, d_class_rows=None,
+                   d_medoid=None, d_medoid_mean=None, stream=0):
+    """enqueue only: d_own_mean / d_other_mean / d_silhouette (f64 [r1]), d_other_class (u32 [r1]), d_class_rows / d_medoid (u32 [n_classes]),
+    d_medoid_mean (f64 [n_classes]) as RefSet.silhouette returns them, each or None; d_class_of (u32, one a row of the set) is trusted:
+    an entry that is no class counts as left out"""
+    check(_lib.load().kpop_dev_silhouette(rs.handle, d_class_of, int(n_classes), d_work, d_own_mean, d_other_mean, d_other_class, d_silhouette, d_class_rows,
+                                          d_medoid, d_medoid_mean, stream))
+
+
+def distance_silhouette(m, metric, class_of, kind=EUCLIDEAN, p=2.0, normalize=True, n_classes=None):
+    """RefSet(m, ...).silhouette(class_of, n_classes) without keeping the set: one call of kpop_distance_silhouette -> Silhouette"""
+    m, metric = _c(m, np.float64), _c(metric, np.float64)
+    if m.ndim != 2 or m.shape[1] != len(metric):
+        raise ValueError("Incompatible_geometries")  # lib/Matrix.ml:193-194
+    rows = m.shape[0]
+    class_of, n_classes = _left_out_classes(class_of, rows, n_classes)
+    res = _silhouette_result(rows, n_classes)
+    check(_lib.load().kpop_distance_silhouette(_p(_nz(m, np.float64), C.c_double), rows, len(metric), _p(_nz(metric, np.float64), C.c_double), int(kind),
+                                               float(p), 1 if normalize else 0, _p(_nz(class_of, np.uint32), C.c_uint32), n_classes, *_silhouette_pointers(res)))
+    return _silhouette_cut(res, rows, n_classes)
+
+
+def silhouette_summary(class_of, silhouette, n_classes=None):
+    """The mean silhouette of each class and of all the rows that are not left out -> (class_mean f64 [n_classes], overall_mean), both summed
+    in ascending row order; an empty class gives NaN.  Host arithmetic alone: no GPU, no init (kpop_silhouette_summary, include/kpop_hip.h)."""
+    silhouette = _c(silhouette, np.float64)
+    if silhouette.ndim != 1:
+        raise ValueError("silhouette: one value a row")
+    class_of, n_classes = _left_out_classes(class_of, len(silhouette), n_classes)
+    class_mean = np.zeros(max(min(n_classes, 65536), 1), dtype=np.float64)
+    overall = C.c_double()
+    check(_lib.load().kpop_silhouette_summary(len(silhouette), _p(_nz(class_of, np.uint32), C.c_uint32), n_classes, _p(_nz(silhouette, np.float64), C.c_double),
+                                              _p(class_mean, C.c_double), C.byref(overall)))
+    return class_mean[:n_classes], float(overall.value)
+
+
+def dense_labels(labels):
+    """The labels that the clustering calls return (the smallest row index of a component, or NOISE) as classes 0 .. n - 1 in ascending
+    label order -> (class_of u32 [r1], n_classes, label_of_class u32 [n_classes]); NOISE becomes NO_CLASS.  What clusters, forest_cut,
+    dbscan and reachability_cut give goes through this into RefSet.silhouette."""
+    labels = np.asarray(labels)
+    if labels.ndim != 1 or (len(labels) and (labels.min() < 0 or labels.max() > 0xFFFFFFFF)):
+        raise ValueError("labels: one uint32 a row")
+    labels = _c(labels, np.uint32)
+    kept = labels != NOISE
+    label_of_class, inverse = np.unique(labels[kept], return_inverse=True)
+    class_of = np.full(len(labels), NO_CLASS, dtype=np.uint32)
+    class_of[kept] = inverse.astype(np.uint32)
+    return class_of, len(label_of_class), label_of_class.astype(np.uint32)
