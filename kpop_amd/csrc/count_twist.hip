@@ -11,9 +11,15 @@
 // rows of n_dims f64 -- with lane d owning dimension d, every row is one
 // fully coalesced 512-byte load (n_dims = 64) and no cross-lane reduction is
 // ever needed.  The kernel is HBM-bound on that gather.
+//
+// Where things are: what a call of kpop_dev_count_twist does is decided in count_twist_plan.h (plan_count_twist: plain host code,
+// with the constants the decision reads and the layout of the workspace); the kernels are here and in tile_pipe.h; the host half of
+// this file launches what the plan says -- one dispatcher per template axis (by_R, by_key_width, by_flag), a short function a step.
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
+#include "count_twist_plan.h"
 #include "kmer.h"
 #include "lookback.h"
 #include "read_hash.h"
@@ -21,11 +27,13 @@
 #include "sort_count.h"
 #include "twister.h"
 #include "wave_sort.h"
+#include "tile_pipe.h"  // count_twist_tile_pipe_kernel: the tile route's scheme as a producer / consumer pipeline
 
 namespace kpop {
 
-constexpr int kWavesPerBlock = 4;
-constexpr int kGatherUnroll = 8;   // row loads in flight per wave in the streaming kernels
+static_assert(kPlanScanTile == kScanTile && kPlanLookGroup == kLookGroup, "count_twist_plan.h sizes the scans' and the look-back's words");
+
+constexpr int kGatherUnroll = 8;  // row loads in flight per wave in the streaming kernels
 constexpr int kGatherPad = 16;     // LDS padding: the deepest gather unroll
 constexpr uint64_t kCsrSegLines = 8192;  // a spectrum's sums are formed per stretch of this many lines and the stretches added in order, whichever kernel
 constexpr uint32_t kFewSpectra = 8192;  // up to this many spectra (a wave each: one round of the chip) twist_csr_kernel keeps 32 row loads in flight per wave; with more, eight and more resident waves do better (20,000 x 139 lines: 0.194 -> 0.161 ms, 32,768 x 139: 0.311 -> 0.247 -- the threshold was 32,768)
@@ -566,12 +574,38 @@ __global__ __launch_bounds__(256) void twist_csr_seg_combine_kernel(const double
   }
 }
 
+// one launch of twist_csr_kernel: UU loads in flight, KK lines kept in registers; the blocks of 64 dimensions a lane sums per pass by
+// the twister's width
+template <typename V>
+struct TwistCsrArgs {
+  const TwisterView &tv;
+  const uint64_t *hash;
+  const V *value;
+  const uint64_t *offsets;
+  uint32_t n;
+  int normalize;
+  double *out;
+  hipStream_t st;
+};
+template <typename V, int UU, int KK>
+static void launch_twist_csr_width(const TwistCsrArgs<V> &a) {
+  const dim3 grid(div_up(a.n, kWavesPerBlock)), block(64 * kWavesPerBlock);
+  if (a.tv.n_dims <= 64) twist_csr_kernel<V, UU, KK, false, 1><<<grid, block, 0, a.st>>>(a.tv, a.hash, a.value, a.offsets, a.n, a.normalize, a.out);
+  else if (a.tv.n_dims <= 128) twist_csr_kernel<V, UU, KK, false, 2><<<grid, block, 0, a.st>>>(a.tv, a.hash, a.value, a.offsets, a.n, a.normalize, a.out);
+  else if (a.tv.n_dims <= 192) twist_csr_kernel<V, UU, KK, false, 3><<<grid, block, 0, a.st>>>(a.tv, a.hash, a.value, a.offsets, a.n, a.normalize, a.out);
+  else twist_csr_kernel<V, UU, KK, false, 4><<<grid, block, 0, a.st>>>(a.tv, a.hash, a.value, a.offsets, a.n, a.normalize, a.out);
+}
+template <typename V, int KK>
+static void launch_twist_csr_keep(const TwistCsrArgs<V> &a) {
+  if (a.n <= kFewSpectra) launch_twist_csr_width<V, 32, KK>(a);
+  else launch_twist_csr_width<V, kGatherUnroll, KK>(a);
+}
+
 // launch by the longest spectrum of the batch: <= 512 lines keeps pass 1's columns in registers
 template <typename V>
 static int launch_twist_csr(const TwisterView &tv, const uint64_t *hash, const V *value, const uint64_t *offsets, uint32_t n,
                             uint64_t max_lines, int normalize, double *out, hipStream_t st) {
-  const dim3 grid(div_up(n, kWavesPerBlock)), block(64 * kWavesPerBlock);
-  const bool few = n <= kFewSpectra;
+  const dim3 block(64 * kWavesPerBlock);
   // A few very long spectra: segments, so that the whole chip works on them (see the kernel).  An empty segment adds +0.0.
   if (max_lines >= 16384 && n <= 2048 && !(ctx().tune_dbg & (1 << 28))) {
     const uint32_t n_seg = (uint32_t)div_up(max_lines, kCsrSegLines);  // (stretches of a fixed length: see the kernel)
@@ -595,26 +629,12 @@ static int launch_twist_csr(const TwisterView &tv, const uint64_t *hash, const V
       return 0;
     }
   }
-  // (UU loads in flight, KK lines kept in registers; the blocks of 64 dimensions a lane sums per pass by the twister's width)
-#define KPOP_CSR(UU, KK)                                                                                                          \
-  do {                                                                                                                            \
-    if (tv.n_dims <= 64) twist_csr_kernel<V, UU, KK, false, 1><<<grid, block, 0, st>>>(tv, hash, value, offsets, n, normalize, out);        \
-    else if (tv.n_dims <= 128) twist_csr_kernel<V, UU, KK, false, 2><<<grid, block, 0, st>>>(tv, hash, value, offsets, n, normalize, out);  \
-    else if (tv.n_dims <= 192) twist_csr_kernel<V, UU, KK, false, 3><<<grid, block, 0, st>>>(tv, hash, value, offsets, n, normalize, out);  \
-    else twist_csr_kernel<V, UU, KK, false, 4><<<grid, block, 0, st>>>(tv, hash, value, offsets, n, normalize, out);                        \
-  } while (0)
-  if (max_lines == 0 || max_lines > 512) {
-    if (few) KPOP_CSR(32, 0); else KPOP_CSR(kGatherUnroll, 0);
-  } else if (max_lines <= 64) {
-    if (few) KPOP_CSR(32, 1); else KPOP_CSR(kGatherUnroll, 1);
-  } else if (max_lines <= 128) {
-    if (few) KPOP_CSR(32, 2); else KPOP_CSR(kGatherUnroll, 2);
-  } else if (max_lines <= 256) {
-    if (few) KPOP_CSR(32, 4); else KPOP_CSR(kGatherUnroll, 4);
-  } else {
-    if (few) KPOP_CSR(32, 8); else KPOP_CSR(kGatherUnroll, 8);
-  }
-#undef KPOP_CSR
+  const TwistCsrArgs<V> a{tv, hash, value, offsets, n, normalize, out, st};
+  if (max_lines == 0 || max_lines > 512) launch_twist_csr_keep<V, 0>(a);
+  else if (max_lines <= 64) launch_twist_csr_keep<V, 1>(a);
+  else if (max_lines <= 128) launch_twist_csr_keep<V, 2>(a);
+  else if (max_lines <= 256) launch_twist_csr_keep<V, 4>(a);
+  else launch_twist_csr_keep<V, 8>(a);
   KPOP_LAUNCH_CHECK();
   return 0;
 }
@@ -632,15 +652,7 @@ static int launch_twist_csr(const TwisterView &tv, const uint64_t *hash, const V
 // up to rounding.  Segment partials are combined in segment order by a second
 // kernel, so results are bitwise reproducible.
 // ---------------------------------------------------------------------------
-constexpr uint32_t kWaveMaxWindows = 512;  // 64 lanes x R=8: the per-read kernels' limit
-constexpr uint32_t kSegWindows = 16384;    // upper bound of a segment
-// Row-load policy, kpop_tune("nt", 2) = automatic (measured: profiles/r02_b_realistic_inputs.txt).
-// Non-temporal loads keep once-read rows from displacing the name -> row index, which is worth 0-6 % when reads are
-// uniformly random over a table many times the 256 MB Infinity Cache -- and costs 6-35 % whenever rows ARE re-read:
-// tables up to ~1 GB even under uniform access (the cache holds a useful share of them), reads drawn from a few
-// genomes, assemblies of one organism.  So: reads kernel non-temporal only above 2 GiB of rows; genome kernel never
-// (a batch of assemblies is one species more often than not, and there plain loads are 1.5x faster).
-constexpr uint64_t kStreamingRowBytes = 2ull << 30;
+// (kWaveMaxWindows, kSegWindows and the row-load policy: count_twist_plan.h)
 
 // nseg[r] = the segments of sequence r (0: the one-wavefront-per-read kernel's), and the list of the sequences that have
 // any (wave-aggregated append: the order of the list is not the batch's, and nothing depends on it).  The streaming kernel
@@ -824,12 +836,7 @@ __global__ __launch_bounds__(256) void count_twist_stream_kernel(
 // rows in window order: equal to the streaming kernel's up to rounding (<= 2e-15 relative measured), like the rest of the
 // "dense" routes.  lib/Twister.ml:146-188.
 // ---------------------------------------------------------------------------
-using f64x4 = __attribute__((ext_vector_type(4))) double;
-constexpr uint32_t kTileProbeG = 64, kTileS = 512, kTileH = 2048;  // sequences of a probed group; windows of a stretch; slots of the set's table
-constexpr uint32_t tile_set_rows(int g) { return g == 64 ? 1024u : 896u; }  // rows the numbering has room for (X rows are padded by 2: 16 rows on 16 banks)
-constexpr uint32_t kTileSetCap = 768;    // rows in the set beyond which the seeds after the first add no more
-constexpr uint32_t kTileStageW = 136;    // dwords of a sequence's staged stretch: 3 + 512 + 14 bytes and the thirteenth dword of the last thread
-constexpr uint32_t kTileMinSeqs = 16;    // sequences with segments in a batch below which the tile kernel does not try
+// (the tile routes' constants: count_twist_plan.h; f64x4 and the phase clocks: tile_pipe.h)
 
 // the sequences of more than kWaveMaxWindows windows, in batch order (an exclusive scan's compaction), each one's place in that list
 struct LoadLongW {
@@ -955,14 +962,6 @@ __global__ __launch_bounds__(256) void tile_group_probe_kernel(const uint8_t *__
     grel[g] = n_long < kTileMinSeqs ? 0u : rel;
   }
 }
-
-// phase clocks of count_twist_tile_kernel (kpop_tune("dbg", 16 << 24) only: s_memtime ticks of every block's thread 0, summed
-// over blocks and chunks; read and cleared by kpop_debug_counters)
-__device__ unsigned long long g_tile_stamps[16];
-
-}  // namespace kpop
-#include "tile_pipe.h"  // count_twist_tile_pipe_kernel: the same scheme as a producer / consumer pipeline (up to 64 dimensions)
-namespace kpop {
 
 // G sequences a chunk: 64 (one block of 1,024 threads a CU, 152 KB of LDS) or 32 (512 threads, 78 KB: TWO blocks a CU, one in
 // its matrix phase while the other waits for bases and index words)
@@ -1624,55 +1623,48 @@ __global__ void synth_reads_kernel(uint64_t seed, uint64_t n_reads, uint32_t rea
 }
 
 // ---------------------------------------------------------------------------
-// dispatch helpers
+// dispatch: one function per template axis (by_kind in distance_routes.h is the model).  A call site nests the axes whose
+// every combination it launches, and names the rest: the code object holds those instantiations and no others.
 // ---------------------------------------------------------------------------
-static int pick_R(uint32_t max_windows) {
-  if (max_windows <= 64) return 1;
-  if (max_windows <= 128) return 2;
-  if (max_windows <= 256) return 4;
-  if (max_windows <= 512) return 8;
-  return 0;
-}
-
-// bytes of device scratch count_wave needs: the ticket counter and one look-back word per block
-// ... and, for the two-level look-back, a word and an arrival counter per group of 64 blocks (lookback.h)
-static inline uint64_t count_wave_max_blocks(uint32_t n) { return (uint64_t)div_up(n, 2 * kWavesPerBlock) + 1; }
-static inline uint64_t count_wave_scratch_bytes(uint32_t n) {
-  const uint64_t blocks = count_wave_max_blocks(n), groups = blocks / kLookGroup + 2;
-  return 64 + blocks * 8 + groups * 8 + ((groups * 4 + 63) & ~63ull);
-}
-
-template <typename H, int SB>
-static int launch_count_wave_sb(int R, const uint8_t *bases, const uint64_t *offsets, uint32_t n, int k, int content, void *scratch,
-                                uint64_t *oh, uint32_t *oc, uint64_t *oo, hipStream_t st) {
-  dim3 block(64 * kWavesPerBlock);
-  const auto grid = [&](int rw) { return dim3(div_up(n, (uint32_t)rw * kWavesPerBlock)); };
-  uint32_t *ticket = reinterpret_cast<uint32_t *>(scratch);
-  uint64_t *state = reinterpret_cast<uint64_t *>(reinterpret_cast<char *>(scratch) + 64);
-  uint64_t *gstate = state + count_wave_max_blocks(n);
-  uint32_t *garr = reinterpret_cast<uint32_t *>(gstate + count_wave_max_blocks(n) / kLookGroup + 2);
-  KPOP_HIP(hipMemsetAsync(scratch, 0, count_wave_scratch_bytes(n), st));
+template <class F>
+static int by_R(int R, const char *who, F &&f) {
   switch (R) {
-    case 1: count_wave_kernel<1, H, SB><<<grid(reads_per_wave<1>()), block, 0, st>>>(bases, offsets, n, k, content, ticket, state, gstate, garr, oh, oc, oo, ctx().tune_dbg); break;
-    case 2: count_wave_kernel<2, H, SB><<<grid(reads_per_wave<2>()), block, 0, st>>>(bases, offsets, n, k, content, ticket, state, gstate, garr, oh, oc, oo, ctx().tune_dbg); break;
-    case 4: count_wave_kernel<4, H, SB><<<grid(reads_per_wave<4>()), block, 0, st>>>(bases, offsets, n, k, content, ticket, state, gstate, garr, oh, oc, oo, ctx().tune_dbg); break;
-    case 8: count_wave_kernel<8, H, SB><<<grid(reads_per_wave<8>()), block, 0, st>>>(bases, offsets, n, k, content, ticket, state, gstate, garr, oh, oc, oo, ctx().tune_dbg); break;
-    default: KPOP_FAIL(KPOP_ERR_INVALID, "launch_count_wave: R=%d", R);
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    default: KPOP_FAIL(KPOP_ERR_INVALID, "%s: R=%d", who, R);
   }
-  KPOP_LAUNCH_CHECK();
-  return 0;
+}
+// keys are 32-bit while the hash (2 bits per base, 5 per residue) leaves the all-ones sentinel free: <= 30 bits
+template <class F>
+static int by_key_width(bool wide, F &&f) {
+  return wide ? f(uint64_t{}) : f(uint32_t{});
+}
+template <class F>
+static int by_flag(bool on, F &&f) {
+  return on ? f(std::true_type{}) : f(std::false_type{});
 }
 
-// keys are 32-bit while the hash (2 bits per base, 5 per residue) leaves the all-ones sentinel free: <= 30 bits.
-// oh / oc need one entry per window (the worst case); oo gets n + 1 offsets.
+// oh / oc need one entry per window (the worst case); oo gets n + 1 offsets; scratch: count_wave_scratch_bytes(n), 64-byte aligned
 static int launch_count_wave(int R, const uint8_t *bases, const uint64_t *offsets, uint32_t n, int k, int content, void *scratch,
                              uint64_t *oh, uint32_t *oc, uint64_t *oo, hipStream_t st) {
-  const bool narrow = hash_bits(k, content) <= 30;
-  if (content == KPOP_PROTEIN)
-    return narrow ? launch_count_wave_sb<uint32_t, 5>(R, bases, offsets, n, k, content, scratch, oh, oc, oo, st)
-                  : launch_count_wave_sb<uint64_t, 5>(R, bases, offsets, n, k, content, scratch, oh, oc, oo, st);
-  return narrow ? launch_count_wave_sb<uint32_t, 2>(R, bases, offsets, n, k, content, scratch, oh, oc, oo, st)
-                : launch_count_wave_sb<uint64_t, 2>(R, bases, offsets, n, k, content, scratch, oh, oc, oo, st);
+  const CountWaveScratch s = carve_count_wave(scratch, n);
+  const int dbg = ctx().tune_dbg;
+  KPOP_HIP(hipMemsetAsync(scratch, 0, s.bytes, st));
+  KPOP_TRY(by_R(R, "launch_count_wave", [&](auto r) {
+    return by_key_width(hash_bits(k, content) > 30, [&](auto h) {
+      using H = decltype(h);
+      const dim3 grid(div_up(n, (uint32_t)reads_per_wave<decltype(r)::value>() * kWavesPerBlock)), block(64 * kWavesPerBlock);
+      if (content == KPOP_PROTEIN)
+        count_wave_kernel<decltype(r)::value, H, 5><<<grid, block, 0, st>>>(bases, offsets, n, k, content, s.ticket, s.state, s.gstate, s.garr, oh, oc, oo, dbg);
+      else
+        count_wave_kernel<decltype(r)::value, H, 2><<<grid, block, 0, st>>>(bases, offsets, n, k, content, s.ticket, s.state, s.gstate, s.garr, oh, oc, oo, dbg);
+      return 0;
+    });
+  }));
+  KPOP_LAUNCH_CHECK();
+  return 0;
 }
 
 // k range and content of the counting entry points (bin/KPopCount.ml:113: <= 30 for DNA, <= 12 for protein)
@@ -1684,102 +1676,264 @@ static int check_count_args(int k, int content, const char *who) {
   return 0;
 }
 
-template <typename H, int U, bool NT>
-static int launch_count_twist_wave_v(int R, const TwisterView &tv, const uint8_t *bases, const uint64_t *offsets,
-                                     const uint32_t *ids, uint32_t n, int content, int normalize, double *out,
-                                     hipStream_t st) {
-  dim3 grid(div_up(n, kWavesPerBlock)), block(64 * kWavesPerBlock);
-  switch (R) {
-    case 1: count_twist_wave_kernel<1, H, U, NT><<<grid, block, (size_t)ctx().tune_ldspad, st>>>(tv, bases, offsets, ids, n, content, normalize, out); break;
-    case 2: count_twist_wave_kernel<2, H, U, NT><<<grid, block, (size_t)ctx().tune_ldspad, st>>>(tv, bases, offsets, ids, n, content, normalize, out); break;
-    case 4: count_twist_wave_kernel<4, H, U, NT><<<grid, block, (size_t)ctx().tune_ldspad, st>>>(tv, bases, offsets, ids, n, content, normalize, out); break;
-    case 8: count_twist_wave_kernel<8, H, U, NT><<<grid, block, (size_t)ctx().tune_ldspad, st>>>(tv, bases, offsets, ids, n, content, normalize, out); break;
-    default: KPOP_FAIL(KPOP_ERR_INVALID, "launch_count_twist_wave: R=%d", R);
-  }
-  KPOP_LAUNCH_CHECK();
-  return 0;
-}
-
-// protein (bin/KPopCount.ml:246-248): five bits a residue, keys of 32 bits up to k = 6 and of 64 beyond
-template <typename H>
-static int launch_count_twist_wave_protein(int R, const TwisterView &tv, const uint8_t *bases, const uint64_t *offsets, const uint32_t *ids, uint32_t n,
-                                           int normalize, double *out, hipStream_t st) {
-  dim3 grid(div_up(n, kWavesPerBlock)), block(64 * kWavesPerBlock);
-#define KPOP_WPR(RR) count_twist_wave_kernel<RR, H, 8, false, false, 5><<<grid, block, (size_t)ctx().tune_ldspad, st>>>(tv, bases, offsets, ids, n, KPOP_PROTEIN, normalize, out)
-  switch (R) {
-    case 1: KPOP_WPR(1); break;
-    case 2: KPOP_WPR(2); break;
-    case 4: KPOP_WPR(4); break;
-    case 8: KPOP_WPR(8); break;
-    default: KPOP_FAIL(KPOP_ERR_INVALID, "launch_count_twist_wave: R=%d", R);
-  }
-#undef KPOP_WPR
-  KPOP_LAUNCH_CHECK();
-  return 0;
-}
-
-template <typename H>
-static int launch_count_twist_wave(int R, TwisterView tv, const uint8_t *bases, const uint64_t *offsets,
-                                   const uint32_t *ids, uint32_t n, int content, int normalize, double *out,
-                                   hipStream_t st) {
-  if (content == KPOP_PROTEIN)  // (its own key width: H is the caller's choice for DNA)
-    return hash_bits(tv.hk, content) <= 30 ? launch_count_twist_wave_protein<uint32_t>(R, tv, bases, offsets, ids, n, normalize, out, st)
-                                           : launch_count_twist_wave_protein<uint64_t>(R, tv, bases, offsets, ids, n, normalize, out, st);
+// what plan_count_twist reads, from the twister, the call and the calling thread's context
+static CountTwistInput plan_input(const kpop_twister *tw, const TwisterView &tv, uint32_t n_reads, uint64_t n_bases, uint32_t max_len, int content) {
   const Context &c = ctx();
-  const bool nt = c.tune_nt == 1 || (c.tune_nt == 2 && (uint64_t)tv.n_rows * tv.d_pad * 8 > kStreamingRowBytes);
-  if (c.tune_unroll == 16)
-    return nt ? launch_count_twist_wave_v<H, 16, true>(R, tv, bases, offsets, ids, n, content, normalize, out, st)
-              : launch_count_twist_wave_v<H, 16, false>(R, tv, bases, offsets, ids, n, content, normalize, out, st);
-  return nt ? launch_count_twist_wave_v<H, 8, true>(R, tv, bases, offsets, ids, n, content, normalize, out, st)
-            : launch_count_twist_wave_v<H, 8, false>(R, tv, bases, offsets, ids, n, content, normalize, out, st);
-}
-
-
-// the pipelined tile kernel (tile_pipe.h) takes this twister: a rank-select index of words (k <= 14), a row's number in 29 bits (it
-// shares a word with three bits of tag in the residual lists) and a row's offset in 128-byte units in 32 (beyond 64 dimensions)
-static bool tile_route_pipe(const kpop_twister *tw) {
-  return tw->d_rsel && (tw->hk ? tw->hk : tw->k) <= 15 && ctx().tune_tilepipe != 0 && tw->n_rows <= (1ull << 29) && (uint64_t)tw->n_rows * (tw->d_pad / 16) < 0xFFFFFFFFull;
-}
-// ... in its three-stage form (tile_pipe.h, WIDE: the columns unit by unit): more than 64 dimensions (kpop_tune("tilewide", 1): at any number of them -- up to 64 the same bits as the other)
-static bool tile_route_wide(const kpop_twister *tw) { return tile_route_pipe(tw) && (tw->n_dims > 64 || ctx().tune_tilewide == 1); }
-// bytes of per-slot tables a call of the wide route may take: 4 GiB per 64 columns, a quarter of the device's memory at most (the
-// same for every call: how a batch is cut into sub-batches must not depend on what happens to be free)
-static uint64_t tile_workspace_cap(uint32_t d_pad) {
-  if (ctx().tune_tilecap_mb > 0) return (uint64_t)ctx().tune_tilecap_mb << 20;
-  uint64_t cap = (4ull << 30) * div_up(d_pad, 64u);
+  CountTwistInput in{};
+  in.k = tw->k, in.hk = tv.hk, in.n_rows = tw->n_rows, in.n_dims = tw->n_dims, in.d_pad = tw->d_pad, in.has_rsel = tw->d_rsel != nullptr;
+  in.n_reads = n_reads, in.n_bases = n_bases, in.max_len = max_len, in.protein = content == KPOP_PROTEIN;
+  in.tune_nt = c.tune_nt, in.tune_unroll = c.tune_unroll, in.tune_seg = c.tune_seg, in.tune_dense = c.tune_dense, in.tune_tileg = c.tune_tileg;
+  in.tune_tilepipe = c.tune_tilepipe, in.tune_tilewide = c.tune_tilewide, in.tune_tilecap_mb = c.tune_tilecap_mb, in.n_cus = c.n_cus;
   size_t free_b = 0, total_b = 0;
-  if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && total_b) cap = std::min<uint64_t>(cap, std::max<uint64_t>(4ull << 30, (uint64_t)total_b / 4));
-  return cap;
+  if (cap_reads_device_bytes(in) && hipMemGetInfo(&free_b, &total_b) == hipSuccess) in.device_bytes = total_b;
+  return in;
+}
+
+// the sequences of up to 512 windows of a batch, one wavefront each (the kernel skips longer ones).  DNA: keys by k, 8 or 16 row loads
+// in flight, either row-load policy; protein (bin/KPopCount.ml:246-248): five bits a residue, keys of 32 bits up to k = 6 and of 64 beyond
+static int launch_count_twist_reads(const CountTwistPlan &p, const TwisterView &tv, const uint8_t *bases, const uint64_t *offsets, uint32_t n, int content,
+                                    int normalize, double *out, hipStream_t st) {
+  const dim3 grid(div_up(n, kWavesPerBlock)), block(64 * kWavesPerBlock);
+  const size_t lds = (size_t)ctx().tune_ldspad;
+  const uint32_t *ids = nullptr;
+  KPOP_TRY(by_R(p.R, "launch_count_twist_wave", [&](auto r) {
+    return by_key_width(p.wide_keys, [&](auto h) {
+      using H = decltype(h);
+      if (content == KPOP_PROTEIN) {
+        count_twist_wave_kernel<decltype(r)::value, H, 8, false, false, 5><<<grid, block, lds, st>>>(tv, bases, offsets, ids, n, KPOP_PROTEIN, normalize, out);
+        return 0;
+      }
+      return by_flag(p.reads_unroll == 16, [&](auto u16) {
+        return by_flag(p.reads_nt, [&](auto nt) {
+          count_twist_wave_kernel<decltype(r)::value, H, decltype(u16)::value ? 16 : 8, decltype(nt)::value><<<grid, block, lds, st>>>(tv, bases, offsets, ids, n, content, normalize, out);
+          return 0;
+        });
+      });
+    });
+  }));
+  KPOP_LAUNCH_CHECK();
+  return 0;
 }
 
 // the same launch from the packed form of the batch (reads of up to 512 windows only: the caller has checked)
-template <typename H>
-static int launch_count_twist_wave_packed(int R, TwisterView tv, const uint32_t *codes, const uint32_t *invalid, const uint64_t *offsets, uint32_t n, int content,
-                                          int normalize, double *out, hipStream_t st) {
-  const Context &c = ctx();
-  const bool nt = c.tune_nt == 1 || (c.tune_nt == 2 && (uint64_t)tv.n_rows * tv.d_pad * 8 > kStreamingRowBytes);
-  dim3 grid(div_up(n, kWavesPerBlock)), block(64 * kWavesPerBlock);
+static int launch_count_twist_reads_packed(const CountTwistPlan &p, const TwisterView &tv, const uint32_t *codes, const uint32_t *invalid, const uint64_t *offsets,
+                                           uint32_t n, int content, int normalize, double *out, hipStream_t st) {
+  const dim3 grid(div_up(n, kWavesPerBlock)), block(64 * kWavesPerBlock);
+  const size_t lds = (size_t)ctx().tune_ldspad;
   const uint8_t *b = reinterpret_cast<const uint8_t *>(codes);
-#define KPOP_WP(RR, NTV) count_twist_wave_kernel<RR, H, 8, NTV, true><<<grid, block, (size_t)c.tune_ldspad, st>>>(tv, b, offsets, nullptr, n, content, normalize, out, invalid)
-  switch (R) {
-    case 1: if (nt) KPOP_WP(1, true); else KPOP_WP(1, false); break;
-    case 2: if (nt) KPOP_WP(2, true); else KPOP_WP(2, false); break;
-    case 4: if (nt) KPOP_WP(4, true); else KPOP_WP(4, false); break;
-    case 8: if (nt) KPOP_WP(8, true); else KPOP_WP(8, false); break;
-    default: KPOP_FAIL(KPOP_ERR_INVALID, "launch_count_twist_wave_packed: R=%d", R);
-  }
-#undef KPOP_WP
+  KPOP_TRY(by_R(p.R, "launch_count_twist_wave_packed", [&](auto r) {
+    return by_key_width(p.wide_keys, [&](auto h) {
+      return by_flag(p.reads_nt, [&](auto nt) {
+        count_twist_wave_kernel<decltype(r)::value, decltype(h), 8, decltype(nt)::value, true><<<grid, block, lds, st>>>(tv, b, offsets, nullptr, n, content, normalize, out, invalid);
+        return 0;
+      });
+    });
+  }));
   KPOP_LAUNCH_CHECK();
   return 0;
 }
 
-static int check_offsets(const uint64_t *offsets, uint32_t n, uint64_t *max_len) {
-  uint64_t m = 0;
-  for (uint32_t r = 0; r < n; ++r) {
-    if (offsets[r + 1] < offsets[r]) KPOP_FAIL(KPOP_ERR_INVALID, "offsets are not non-decreasing at read %u", r);
-    m = std::max(m, offsets[r + 1] - offsets[r]);
+// ---------------------------------------------------------------------------
+// the long part of kpop_dev_count_twist, a step a function: the call, its plan and its workspace (count_twist_plan.h)
+// ---------------------------------------------------------------------------
+struct CountTwistCall {
+  TwisterView tv;
+  const uint8_t *bases;
+  const uint64_t *offsets;
+  uint32_t n_reads;
+  int content, normalize;
+  double *out;
+  hipStream_t st;
+};
+
+// the long sequences in batch order, groups of 64 of them probed for being one organism -- before the segments are laid out
+static int probe_long_groups(const CountTwistCall &c, const CountTwistPlan &p, const CountTwistWorkspace &w) {
+  KPOP_TRY(exclusive_scan(LoadLongW{c.offsets, c.tv.hk}, StoreLong{w.olong, w.lpos}, c.n_reads, w.sums2, c.st));
+  tile_group_probe_kernel<<<dim3(p.max_groups), dim3(256), 0, c.st>>>(c.bases, c.offsets, c.tv.hk, c.content, w.olong, w.n_olong, w.gmax, w.grel);
+  KPOP_LAUNCH_CHECK();
+  return 0;
+}
+
+// the segment table: how many segments a sequence has, where its slots begin, and the list of the sequences that have any
+static int lay_out_segments(const CountTwistCall &c, const CountTwistPlan &p, const CountTwistWorkspace &w) {
+  segment_count_kernel<<<dim3(div_up(c.n_reads, 256)), dim3(256), 0, c.st>>>(c.offsets, c.n_reads, c.tv.hk, p.seg_windows, w.nseg, w.long_ids, w.n_long, w.lpos, w.grel,
+                                                                             w.segw);
+  KPOP_LAUNCH_CHECK();
+  return exclusive_scan(LoadU32{w.nseg}, StoreU64{w.seg_off}, c.n_reads, w.sums, c.st);
+}
+
+constexpr size_t tile_round4_lds(int g) { return (size_t)kTileH * 8 + tile_set_rows(g) * 4 + (size_t)g * (tile_set_rows(g) + 2) * 2; }
+
+// round 4's kernel, phases one after the other (kpop_tune("tilepipe", 0)); beyond 64 dimensions the residual rows in a launch of their own
+static int launch_tile_round4(const CountTwistCall &c, const CountTwistPlan &p, const CountTwistWorkspace &w) {
+  const Context &cx = ctx();
+  static PerSlotOnce once;
+  if (!once()) {
+    KPOP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&count_twist_tile_kernel<uint32_t, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_round4_lds(64)));
+    KPOP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&count_twist_tile_kernel<uint32_t, 32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_round4_lds(32)));
+    once() = true;
   }
-  *max_len = m;
+  const int g = p.tile_g, dbg = cx.tune_dbg >> 24;
+  const uint32_t blocks = (uint32_t)std::min<uint64_t>((uint64_t)div_up(p.max_long, g) * p.max_seg, (uint64_t)cx.n_cus * (g == 32 ? 2 : 1));
+  if (g == 64)
+    count_twist_tile_kernel<uint32_t, 64><<<dim3(blocks), dim3(1024), tile_round4_lds(64), c.st>>>(c.tv, c.bases, c.offsets, c.content, w.nseg, w.seg_off, w.part, w.pcnt, w.olong, w.n_olong,
+                                                                                                  w.gmax, w.grel, p.max_seg, w.slot_done, w.res_rows, w.wave_lists, dbg);
+  else
+    count_twist_tile_kernel<uint32_t, 32><<<dim3(blocks), dim3(512), tile_round4_lds(32), c.st>>>(c.tv, c.bases, c.offsets, c.content, w.nseg, w.seg_off, w.part, w.pcnt, w.olong, w.n_olong,
+                                                                                                 w.gmax, w.grel, p.max_seg, w.slot_done, w.res_rows, w.wave_lists, dbg);
+  KPOP_LAUNCH_CHECK();
+  if (p.route != LongRoute::TileRound4Residual) return 0;  // (up to 64 dimensions the kernel has gathered the residual rows itself)
+  const dim3 rgrid(capped_grid((p.max_slots + 3) / 4));
+  KPOP_TRY(by_flag(p.stream_nt, [&](auto nt) {
+    tile_residual_kernel<decltype(nt)::value><<<rgrid, dim3(256), 0, c.st>>>(c.tv, w.slot_done, w.res_rows, w.part, w.seg_total);
+    return 0;
+  }));
+  KPOP_LAUNCH_CHECK();
+  return 0;
+}
+
+// the pipelined kernel (tile_pipe.h), in its three-stage form beyond 64 dimensions (WIDE; kpop_tune("tilewide", 1): at any number of
+// them -- up to 64 the same bits as the other).  The ablation switches have a build of the kernel of their own, so that the product's
+// loops carry no test of them.
+static int launch_tile_pipe(const CountTwistCall &c, const CountTwistPlan &p, const CountTwistWorkspace &w) {
+  const Context &cx = ctx();
+  static PerSlotOnce once;
+  if (!once()) {
+    KPOP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&count_twist_tile_pipe_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPipeLdsBytes));
+    KPOP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&count_twist_tile_pipe_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPipeLdsBytes));
+    KPOP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&count_twist_tile_pipe_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPipeLdsBytes));
+    KPOP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&count_twist_tile_pipe_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPipeLdsBytes));
+    once() = true;
+  }
+  const uint32_t blocks = (uint32_t)std::min<uint64_t>((uint64_t)div_up(p.max_long, kPipeG) * p.max_seg, (uint64_t)cx.n_cus);
+  const int tdbg = ((cx.tune_dbg >> 24) & 127) | ((cx.tune_pipeprio & 3) << 8) | ((cx.tune_pipeprio & 4) ? 128 : 0);  // (bit 7: read by nothing in tile_pipe.h any more)
+  KPOP_TRY(by_flag((tdbg & 15) != 0, [&](auto ablation) {
+    return by_flag(p.route == LongRoute::TilePipeWide, [&](auto wide) {
+      count_twist_tile_pipe_kernel<decltype(ablation)::value, decltype(wide)::value><<<dim3(blocks), dim3(1024), kPipeLdsBytes, c.st>>>(
+          c.tv, c.bases, c.offsets, c.content, w.nseg, w.seg_off, w.part, w.pcnt, w.olong, w.n_olong, w.gmax, w.grel, p.max_seg, w.slot_done, w.wave_lists, tdbg);
+      return 0;
+    });
+  }));
+  KPOP_LAUNCH_CHECK();
+  return 0;
+}
+
+// the (sequence, segment) pairs the tile kernel left, for the streaming kernel
+static int list_todo(const CountTwistCall &c, const CountTwistPlan &p, const CountTwistWorkspace &w) {
+  KPOP_HIP(hipMemsetAsync(w.n_todo, 0, (1 + kStreamMaxPasses) * 4, c.st));
+  tile_todo_kernel<<<dim3(std::min<uint32_t>(div_up(p.max_long, 256), 4096u)), dim3(256), 0, c.st>>>(w.nseg, w.seg_off, w.olong, w.n_olong, w.slot_done,
+                                                                                                      reinterpret_cast<uint2 *>(w.todo), w.n_todo);
+  KPOP_LAUNCH_CHECK();
+  return 0;
+}
+
+// The dimensions go in passes of up to 256 (four blocks of 64 a lane), 128 or 64 -- one LAUNCH per pass, so that a pass never
+// loads blocks it has no dimensions for (300 dimensions: 256 + 44; a run-time guard on the loads brought the per-window
+// branches back: 2.4 -> 5.2 ms at 64 dimensions).  Every launch hashes the windows again: once per 256 dimensions, not per 64.
+template <typename H, bool NT, int SB>
+static int launch_stream_passes(const CountTwistCall &c, const CountTwistPlan &p, const CountTwistWorkspace &w) {
+  // (with a to-do list the pairs all have work, and how many is on the device: a grid that fills the chip, striding)
+  const dim3 grid(p.tiles() ? (uint32_t)std::min<uint64_t>(p.max_slots, (uint64_t)ctx().n_cus * 8) : capped_grid((uint64_t)p.max_long * p.max_seg));  // (eight blocks of 256 are resident per CU)
+  const uint32_t *n_pairs = p.tiles() ? w.n_todo : w.n_long;
+  uint32_t *next = w.stream_next;  // a take-the-next counter per launch (none without a to-do list)
+  const auto pass = [&](auto ndb, uint32_t d0, uint32_t d1) {
+    count_twist_stream_kernel<H, NT, decltype(ndb)::value, SB><<<grid, dim3(256), 0, c.st>>>(c.tv, c.bases, c.offsets, c.content, w.nseg, w.seg_off, w.part, w.pcnt, w.long_ids, n_pairs, p.max_seg,
+                                                                                            p.seg_windows, reinterpret_cast<const uint2 *>(w.todo), w.segw, next, d0, d1);
+    if (next) ++next;
+  };
+  const uint32_t n_dims = c.tv.n_dims;
+  for (uint32_t pos = 0; pos < n_dims;) {
+    const uint32_t rem = n_dims - pos, take = std::min(rem, 256u);
+    if (rem > 128) pass(std::integral_constant<int, 4>{}, pos, pos + take);
+    else if (rem > 64) pass(std::integral_constant<int, 2>{}, pos, pos + take);
+    else pass(std::integral_constant<int, 1>{}, pos, pos + take);
+    pos += take;
+  }
+  KPOP_LAUNCH_CHECK();
+  return 0;
+}
+static int launch_stream(const CountTwistCall &c, const CountTwistPlan &p, const CountTwistWorkspace &w) {
+  return by_key_width(p.wide_keys, [&](auto h) {
+    using H = decltype(h);
+    if (c.content == KPOP_PROTEIN) return launch_stream_passes<H, false, 5>(c, p, w);
+    return by_flag(p.stream_nt, [&](auto nt) { return launch_stream_passes<H, decltype(nt)::value, 2>(c, p, w); });
+  });
+}
+
+// the sums of a sequence's segments, added in segment order
+static int combine_partials(const CountTwistCall &c, const CountTwistPlan &p, const CountTwistWorkspace &w) {
+  combine_partials_kernel<<<dim3(p.max_long), dim3(256), 0, c.st>>>(w.nseg, w.seg_off, w.part, w.pcnt, c.tv.n_dims, c.normalize, c.out, w.long_ids, w.n_long);
+  KPOP_LAUNCH_CHECK();
+  return 0;
+}
+
+namespace {
+
+// a host batch's offsets, checked: non-decreasing; the longest item, the first one's place and how many items there are in all
+struct HostOffsets {
+  uint32_t n = 0;
+  uint64_t max_len = 0, base0 = 0, n_items = 0;
+  DevBuf d_off;
+  int check(const uint64_t *offsets, uint32_t n_seqs) {
+    n = n_seqs;
+    for (uint32_t r = 0; r < n; ++r) {
+      if (offsets[r + 1] < offsets[r]) KPOP_FAIL(KPOP_ERR_INVALID, "offsets are not non-decreasing at read %u", r);
+      max_len = std::max(max_len, offsets[r + 1] - offsets[r]);
+    }
+    base0 = offsets[0];
+    n_items = offsets[n] - base0;
+    return 0;
+  }
+  // ... rebased to 0, with room on the device; a caller allocates everything it needs before it copies anything
+  int alloc(const uint64_t *offsets) {
+    rel.resize((size_t)n + 1);
+    for (uint32_t r = 0; r <= n; ++r) rel[r] = offsets[r] - base0;
+    return d_off.alloc((uint64_t)(n + 1) * 8);
+  }
+  int copy(hipStream_t st) {
+    KPOP_HIP(hipMemcpyAsync(d_off.p, rel.data(), (uint64_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
+    return 0;
+  }
+  std::vector<uint64_t> rel;  // (alive until the copy has been waited for: as long as this)
+};
+// ... and the bases they cut
+struct HostReads : HostOffsets {
+  DevBuf d_bases;
+  int alloc(const uint64_t *offsets) {
+    KPOP_TRY(d_bases.alloc(n_items));
+    return HostOffsets::alloc(offsets);
+  }
+  int copy(const uint8_t *bases, hipStream_t st) {
+    if (n_items) KPOP_HIP(hipMemcpyAsync(d_bases.p, bases + base0, n_items, hipMemcpyHostToDevice, st));
+    return HostOffsets::copy(st);
+  }
+};
+
+// the -L spectra of uploaded reads of up to 512 windows, left on the device as CSR: one entry per window is the worst case
+struct ReadSpectra {
+  DevBuf d_scr, d_oo, d_oh, d_oc;
+  int alloc(const HostReads &b, int k) {
+    uint64_t worst = 0;
+    for (uint32_t r = 0; r < b.n; ++r) worst += windows_of(b.rel[r + 1] - b.rel[r], k);
+    KPOP_TRY(d_scr.alloc(count_wave_scratch_bytes(b.n)));
+    KPOP_TRY(d_oo.alloc((uint64_t)(b.n + 1) * 8));
+    KPOP_TRY(d_oh.alloc(worst * 8));
+    return d_oc.alloc(worst * 4);
+  }
+  int count(const HostReads &b, int k, int content, hipStream_t st) {
+    return launch_count_wave(pick_R(windows_of(b.max_len, k)), b.d_bases.as<uint8_t>(), b.d_off.as<uint64_t>(), b.n, k, content, d_scr.p, d_oh.as<uint64_t>(),
+                             d_oc.as<uint32_t>(), d_oo.as<uint64_t>(), st);
+  }
+};
+
+}  // namespace
+
+// genomes through the sort path: f(first, count) for sub-batches whose (spectrum id | hash) keys fit 63 bits
+template <class F>
+static int by_key_sub_batches(uint32_t n_reads, int k, int content, F &&f) {
+  const int id_bits_max = 63 - hash_bits(k, content);
+  const uint64_t sub = id_bits_max >= 32 ? n_reads : std::max<uint64_t>(1, 1ull << id_bits_max);
+  for (uint64_t r0 = 0; r0 < n_reads; r0 += sub) KPOP_TRY(f(r0, (uint32_t)std::min<uint64_t>(sub, n_reads - r0)));
   return 0;
 }
 
@@ -1811,6 +1965,17 @@ extern "C" int kpop_dev_synth_reads(uint64_t seed, uint64_t n_reads, uint32_t re
   return KPOP_OK;
 }
 
+// a batch past the three-stage tile route's bound (count_twist_plan.h): m sequences a call, at most m x max_len bases each
+static int count_twist_in_sub_batches(const kpop_twister *tw, const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n_reads, uint64_t n_bases, uint32_t max_len,
+                                      int content, int normalize, double *d_out, void *stream, uint64_t m) {
+  for (uint64_t r0 = 0; r0 < n_reads; r0 += m) {
+    const uint32_t n = (uint32_t)std::min<uint64_t>(m, n_reads - r0);
+    KPOP_TRY(kpop_dev_count_twist(tw, d_bases, d_offsets + r0, n, std::min<uint64_t>(n_bases, (uint64_t)n * max_len), max_len, content, normalize,
+                                  d_out + r0 * tw->n_dims, stream));
+  }
+  return KPOP_OK;
+}
+
 extern "C" int kpop_dev_count_twist(const kpop_twister *tw, const uint8_t *d_bases, const uint64_t *d_offsets,
                                     uint32_t n_reads, uint64_t n_bases, uint32_t max_len, int content, int normalize,
                                     double *d_out, void *stream) {
@@ -1818,231 +1983,44 @@ extern "C" int kpop_dev_count_twist(const kpop_twister *tw, const uint8_t *d_bas
   if (!tw || !d_offsets || !d_out) KPOP_FAIL(KPOP_ERR_INVALID, "kpop_dev_count_twist: null argument");
   if (content != KPOP_DNA_DS && content != KPOP_DNA_SS && content != KPOP_PROTEIN)
     KPOP_FAIL(KPOP_ERR_INVALID, "kpop_dev_count_twist: Invalid_content(%d)", content);
-  const bool protein = content == KPOP_PROTEIN;  // five bits a residue (bin/KPopCount.ml:246-248): the wave and the streaming kernel, no tile route
   if (n_reads == 0) return KPOP_OK;
-  hipStream_t st = as_stream(stream);
-  const TwisterView tv = view_of(tw);
-  if (protein && (tv.hk > kMaxKProtein || hash_bits(tv.hk, content) > 2 * tw->k))
-    KPOP_FAIL(KPOP_ERR_INVALID, "kpop_dev_count_twist: protein k=%d (at most %d, and its %d-bit hashes must fit the %d bits the twister was loaded with)", tv.hk,
-              kMaxKProtein, hash_bits(tv.hk, content), 2 * tw->k);
-  const uint32_t max_windows = (max_len >= (uint32_t)tv.hk) ? max_len - tv.hk + 1 : 0;
-  // Assemblies through more than 64 dimensions whose partial rows pass the tile route's bound (below) go through in SUB-BATCHES of
-  // sequences, m of them at most m x max_len bases, each a call of its own.
-  if (!protein && max_windows > kWaveMaxWindows && tile_route_wide(tw) && ctx().tune_dense != 0 && !ctx().tune_seg && n_reads >= kTileMinSeqs) {
-    const uint64_t max_long0 = std::min<uint64_t>(n_reads, n_bases / kWaveMaxWindows + 1);
-    const uint64_t per_slot = (uint64_t)tw->n_dims * 8 + 4 + 4 + 8, cap = tile_workspace_cap(tw->d_pad);
-    if ((n_bases / kTileS + max_long0) * per_slot > cap) {
-      const uint64_t m = cap / (((uint64_t)max_len / kTileS + 2) * per_slot);
-      if (m >= 4096 && m < n_reads) {
-        for (uint64_t r0 = 0; r0 < n_reads; r0 += m) {
-          const uint32_t n = (uint32_t)std::min<uint64_t>(m, n_reads - r0);
-          KPOP_TRY(kpop_dev_count_twist(tw, d_bases, d_offsets + r0, n, std::min<uint64_t>(n_bases, (uint64_t)n * max_len), max_len, content, normalize,
-                                        d_out + r0 * tw->n_dims, stream));
-        }
-        return KPOP_OK;
-      }
-    }
-  }
-  // reads of up to 512 windows: one wavefront per read (the kernel skips longer reads)
-  const int R = pick_R(std::min(max_windows, kWaveMaxWindows));
-  const int flags = (normalize ? 1 : 0) | (max_windows > kWaveMaxWindows ? 2 : 0);  // bit 1: the streaming pass below takes the long ones
-  if (tv.hk <= 15)
-    KPOP_TRY(launch_count_twist_wave<uint32_t>(R, tv, d_bases, d_offsets, nullptr, n_reads, content, flags, d_out, st));
-  else
-    KPOP_TRY(launch_count_twist_wave<uint64_t>(R, tv, d_bases, d_offsets, nullptr, n_reads, content, flags, d_out, st));
-  if (max_windows <= kWaveMaxWindows) return KPOP_OK;
-  // longer sequences: segment table, streaming kernel, ordered combine.  Segment = the stretch of a sequence one block
-  // sums: its rows should sit in one XCD's L2 (4 MB) next to those of the neighbouring segment, see the kernel.
-  const Context &cx = ctx();
-  uint32_t seg_windows = cx.tune_seg ? (uint32_t)cx.tune_seg : std::max<uint32_t>(1024u, std::min<uint32_t>(kSegWindows, (uint32_t)((3ull << 19) / ((uint64_t)tw->d_pad * 8)) / 64 * 64));
-  // Batches of assemblies first go through count_twist_tile_kernel (the consensus rows of a stretch of 64 sequences gathered
-  // once and multiplied on the matrix cores, the private rows listed for tile_residual_kernel); what it leaves -- stretches
-  // that share little with their seeds, found from a sample -- is the streaming kernel's as before.  kpop_tune("dense", 0)
-  // opts out (the streaming kernel alone: the reference's order of additions within a segment).
-  bool tiles_wanted = !protein && cx.tune_dense != 0 && tv.rsel && n_reads >= kTileMinSeqs && tv.hk <= 15 && !cx.tune_seg;
-  const bool nt = cx.tune_nt == 1;
-  // (a sequence with segments has more than kWaveMaxWindows windows: at most this many of them)
-  const uint32_t max_long = (uint32_t)std::min<uint64_t>(n_reads, n_bases / kWaveMaxWindows + 1);
-  // The tile route cuts sequences into 512-window segments, so its per-slot tables are sized for n_bases / 512 slots whatever the
-  // probe later finds (BASELINE config 3, D = 64: 1.5 GB of partial rows against 0.28 GB; beyond 64 dimensions 2 KB of residual
-  // list a slot on top).  Where that would pass 4 GiB of workspace -- per stream -- the batch keeps the streaming kernel.
-  // Beyond 64 dimensions the pipelined kernel takes the columns unit by unit (tile_pipe.h, WIDE); its bound is 4 GiB per 64
-  // columns (BASELINE config 3 at 256 dimensions: 6.1 GB of partial rows; at the reference's 1,635, README.md:1029, 39 GB -- what 288 GB
-  // are for), and a batch beyond THAT goes through in sub-batches of sequences, each sized from max_len (below).
-  const bool pipe_able = tile_route_pipe(tw);
-  const bool wide = tile_route_wide(tw);
-  if (tiles_wanted) {
-    const uint64_t slots = n_bases / std::min(seg_windows, kTileS) + max_long;
-    const uint64_t per_slot = (uint64_t)tw->n_dims * 8 + 4 + 4 + 8 + (tw->n_dims > 64 && !wide ? (uint64_t)kTileS * 4 : 0);
-    const uint64_t cap = wide ? tile_workspace_cap(tw->d_pad) : (4ull << 30);
-    if (slots * per_slot > cap) tiles_wanted = false;  // (a batch that could go through in sub-batches has, above)
-  }
-  const bool tiles = tiles_wanted;
-  const uint32_t seg_least = tiles ? std::min(seg_windows, kTileS) : seg_windows;  // (the shortest segment any sequence is cut into)
-  const uint64_t max_slots = n_bases / seg_least + max_long;  // every such sequence adds at most W/seg + 1 segments
-  const uint64_t nb = scan_blocks(n_reads);
-  const uint32_t max_seg = div_up(max_windows, seg_least);
-  const uint32_t max_groups = div_up(max_long, kTileProbeG);
-  const int tile_g = cx.tune_tileg == 64 ? 64 : 32;  // sequences a chunk of the tile kernel (kpop_tune("tileg"))
-  const uint64_t bytes_nseg = ((uint64_t)n_reads * 4 + 63) & ~63ull, bytes_off = ((uint64_t)(n_reads + 1) * 8 + 63) & ~63ull,
-                 bytes_sums = ((nb + 1) * 8 + 63) & ~63ull, bytes_cnt = (max_slots * 4 + 63) & ~63ull,
-                 bytes_part = (max_slots * tw->n_dims * 8 + 63) & ~63ull, bytes_done = tiles ? ((max_slots * 4 + 63) & ~63ull) : 0,
-                 bytes_long = ((uint64_t)n_reads * 4 + 64 + 63) & ~63ull,
-                 bytes_olong = tiles ? (((uint64_t)max_long * 4 + 63) & ~63ull) : 0, bytes_gmax = tiles ? (((uint64_t)max_groups * 4 + 63) & ~63ull) : 0,
-                 bytes_res = tiles && tw->n_dims > 64 && !wide ? max_slots * kTileS * 4 : 0, bytes_todo = tiles ? ((max_slots * 8 + 1024 + 63) & ~63ull) : 0,
-                 bytes_perread = tiles ? bytes_nseg : 0;
-  // up to 64 dimensions: the pipelined kernel (tile_pipe.h; kpop_tune("tilepipe", 0): round 4's kernel, phases one after the other)
-  // (kpop_tune("tilepipe", 0): round 4's kernel, phases one after the other, the residual rows in a launch of their own beyond 64 dimensions)
-  const bool pipe = tiles && pipe_able;  // (a row's number shares a word with three bits of tag in the residual lists; beyond 64 dimensions a row's offset in 128-byte units is a word)
-  const uint64_t bytes_wlists = !tiles ? 0 : pipe ? (uint64_t)cx.n_cus * (wide ? 3 : 2) * 8 * kPipeListCap * 4 : (uint64_t)cx.n_cus * 16 * 4 * kTileS * 4;
+  const CountTwistCall c{view_of(tw), d_bases, d_offsets, n_reads, content, normalize, d_out, as_stream(stream)};
+  if (content == KPOP_PROTEIN && (c.tv.hk > kMaxKProtein || hash_bits(c.tv.hk, content) > 2 * tw->k))
+    KPOP_FAIL(KPOP_ERR_INVALID, "kpop_dev_count_twist: protein k=%d (at most %d, and its %d-bit hashes must fit the %d bits the twister was loaded with)", c.tv.hk,
+              kMaxKProtein, hash_bits(c.tv.hk, content), 2 * tw->k);
+  const CountTwistInput in = plan_input(tw, c.tv, n_reads, n_bases, max_len, content);
+  const CountTwistPlan p = plan_count_twist(in);
+  if (p.sub_batch_seqs) return count_twist_in_sub_batches(tw, d_bases, d_offsets, n_reads, n_bases, max_len, content, normalize, d_out, stream, p.sub_batch_seqs);
+  // (bit 1 of the flags: the long part below takes the sequences of more than 512 windows)
+  KPOP_TRY(launch_count_twist_reads(p, c.tv, d_bases, d_offsets, n_reads, content, (normalize ? 1 : 0) | (p.has_long ? 2 : 0), d_out, c.st));
+  if (!p.has_long) return KPOP_OK;
+  if (p.refused)
+    KPOP_FAIL(KPOP_ERR_UNSUPPORTED, "kpop_dev_count_twist: %u dimensions (at most 65,280 with the tile route on; kpop_tune(\"dense\", 0) lifts that)", tw->n_dims);
+  // longer sequences: segment table, tile kernel where the plan says so, streaming kernel, ordered combine
   void *ws = nullptr;
-  KPOP_TRY(ctx().ws_for(st).ensure(bytes_nseg + bytes_off + 2 * bytes_sums + bytes_cnt + bytes_part + bytes_done + bytes_long + bytes_olong + 2 * bytes_gmax +
-                                       bytes_res + bytes_todo + 2 * bytes_perread + bytes_wlists, &ws));
-  char *wp = reinterpret_cast<char *>(ws);
-  auto carve = [&](uint64_t bytes) {
-    char *p = wp;
-    wp += bytes;
-    return p;
-  };
-  uint32_t *nseg = reinterpret_cast<uint32_t *>(carve(bytes_nseg));
-  uint64_t *seg_off = reinterpret_cast<uint64_t *>(carve(bytes_off));
-  uint64_t *sums = reinterpret_cast<uint64_t *>(carve(bytes_sums));
-  uint64_t *sums2 = reinterpret_cast<uint64_t *>(carve(bytes_sums));
-  uint32_t *pcnt = reinterpret_cast<uint32_t *>(carve(bytes_cnt));
-  double *part = reinterpret_cast<double *>(carve(bytes_part));
-  uint32_t *slot_done = tiles ? reinterpret_cast<uint32_t *>(carve(bytes_done)) : nullptr;
-  uint32_t *n_long = reinterpret_cast<uint32_t *>(carve(bytes_long));
-  uint32_t *long_ids = n_long + 16;
-  uint32_t *olong = reinterpret_cast<uint32_t *>(carve(bytes_olong));
-  uint32_t *gmax = reinterpret_cast<uint32_t *>(carve(bytes_gmax));
-  uint32_t *grel = reinterpret_cast<uint32_t *>(carve(bytes_gmax));
-  uint32_t *res_rows = reinterpret_cast<uint32_t *>(carve(bytes_res));
-  uint32_t *n_todo = reinterpret_cast<uint32_t *>(carve(bytes_todo));
-  uint2 *todo = tiles ? reinterpret_cast<uint2 *>(n_todo + 256) : nullptr;  // ([0] the list's length, [1..255] a take-the-next counter per streaming launch)
-  uint32_t *lpos = tiles ? reinterpret_cast<uint32_t *>(carve(bytes_perread)) : nullptr;
-  uint32_t *segw = tiles ? reinterpret_cast<uint32_t *>(carve(bytes_perread)) : nullptr;
-  uint32_t *wave_lists = reinterpret_cast<uint32_t *>(carve(bytes_wlists));
-  KPOP_HIP(hipMemsetAsync(n_long, 0, 64, st));
-  if (tiles) {
-    // the long sequences in batch order, groups of 64 of them probed for being one organism -- before the segments are laid out
-    KPOP_TRY(exclusive_scan(LoadLongW{d_offsets, tv.hk}, StoreLong{olong, lpos}, n_reads, sums2, st));
-    tile_group_probe_kernel<<<dim3(max_groups), dim3(256), 0, st>>>(d_bases, d_offsets, tv.hk, content, olong, sums2 + nb, gmax, grel);
-    KPOP_LAUNCH_CHECK();
+  KPOP_TRY(ctx().ws_for(c.st).ensure(carve_count_twist(nullptr, in, p).bytes, &ws));
+  const CountTwistWorkspace w = carve_count_twist(ws, in, p);
+  KPOP_HIP(hipMemsetAsync(w.n_long, 0, 64, c.st));
+  if (p.tiles()) KPOP_TRY(probe_long_groups(c, p, w));
+  KPOP_TRY(lay_out_segments(c, p, w));
+  if (p.tiles()) {
+    KPOP_HIP(hipMemsetAsync(w.slot_done, 0, w.slot_done_bytes, c.st));
+    KPOP_TRY(p.pipe() ? launch_tile_pipe(c, p, w) : launch_tile_round4(c, p, w));
+    KPOP_TRY(list_todo(c, p, w));
   }
-  segment_count_kernel<<<dim3(div_up(n_reads, 256)), dim3(256), 0, st>>>(d_offsets, n_reads, tv.hk, seg_windows, nseg, long_ids, n_long, lpos, grel, segw);
-  KPOP_LAUNCH_CHECK();
-  KPOP_TRY(exclusive_scan(LoadU32{nseg}, StoreU64{seg_off}, n_reads, sums, st));
-  if (tiles) {
-    KPOP_HIP(hipMemsetAsync(slot_done, 0, bytes_done, st));
-    const size_t lds = (size_t)kTileH * 8 + tile_set_rows(tile_g) * 4 + (size_t)tile_g * (tile_set_rows(tile_g) + 2) * 2;
-    static PerSlotOnce once;
-    if (!once()) {
-      KPOP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&count_twist_tile_kernel<uint32_t, 64>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)((size_t)kTileH * 8 + tile_set_rows(64) * 4 + (size_t)64 * (tile_set_rows(64) + 2) * 2)));
-      KPOP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&count_twist_tile_kernel<uint32_t, 32>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)((size_t)kTileH * 8 + tile_set_rows(32) * 4 + (size_t)32 * (tile_set_rows(32) + 2) * 2)));
-      once() = true;
-    }
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>((uint64_t)div_up(max_long, tile_g) * max_seg, (uint64_t)cx.n_cus * (tile_g == 32 ? 2 : 1));
-    if (pipe) {
-      static PerSlotOnce once_pipe;
-      if (!once_pipe()) {
-        KPOP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&count_twist_tile_pipe_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPipeLdsBytes));
-        KPOP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&count_twist_tile_pipe_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPipeLdsBytes));
-        KPOP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&count_twist_tile_pipe_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPipeLdsBytes));
-        KPOP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&count_twist_tile_pipe_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPipeLdsBytes));
-        once_pipe() = true;
-      }
-      const uint32_t pblocks = (uint32_t)std::min<uint64_t>((uint64_t)div_up(max_long, kPipeG) * max_seg, (uint64_t)cx.n_cus);
-      const int tdbg = ((ctx().tune_dbg >> 24) & 127) | ((ctx().tune_pipeprio & 3) << 8) | ((ctx().tune_pipeprio & 4) ? 128 : 0);  // (bit 7: read by nothing in tile_pipe.h any more)
-#define KPOP_PIPE(A, W) count_twist_tile_pipe_kernel<A, W><<<dim3(pblocks), dim3(1024), kPipeLdsBytes, st>>>(tv, d_bases, d_offsets, content, nseg, seg_off, part, pcnt, olong, sums2 + nb, gmax, grel, max_seg, slot_done, wave_lists, tdbg)
-      // (the ablation switches: a build of the kernel of their own, so that the product's loops carry no test of them;
-      //  kpop_tune("tilewide", 1): the three-stage kernel at any number of dimensions -- at up to 64 the same bits as the other)
-      const bool wide_k = wide;
-      if (tdbg & 15) {
-        if (wide_k) KPOP_PIPE(true, true); else KPOP_PIPE(true, false);
-      } else {
-        if (wide_k) KPOP_PIPE(false, true); else KPOP_PIPE(false, false);
-      }
-#undef KPOP_PIPE
-    } else if (tile_g == 64)
-      count_twist_tile_kernel<uint32_t, 64><<<dim3(blocks), dim3(1024), lds, st>>>(tv, d_bases, d_offsets, content, nseg, seg_off, part, pcnt, olong, sums2 + nb,
-                                                                                  gmax, grel, max_seg, slot_done, res_rows, wave_lists, ctx().tune_dbg >> 24);
-    else
-      count_twist_tile_kernel<uint32_t, 32><<<dim3(blocks), dim3(512), lds, st>>>(tv, d_bases, d_offsets, content, nseg, seg_off, part, pcnt, olong, sums2 + nb,
-                                                                                 gmax, grel, max_seg, slot_done, res_rows, wave_lists, ctx().tune_dbg >> 24);
-    KPOP_LAUNCH_CHECK();
-    if (tw->n_dims > 64 && !pipe) {  // (the pipelined kernel -- and round 4's up to 64 dimensions -- has gathered the residual rows itself)
-      const dim3 rgrid(capped_grid((max_slots + 3) / 4));
-      if (nt)
-        tile_residual_kernel<true><<<rgrid, dim3(256), 0, st>>>(tv, slot_done, res_rows, part, sums + nb);
-      else
-        tile_residual_kernel<false><<<rgrid, dim3(256), 0, st>>>(tv, slot_done, res_rows, part, sums + nb);
-      KPOP_LAUNCH_CHECK();
-    }
-    KPOP_HIP(hipMemsetAsync(n_todo, 0, 1024, st));
-    tile_todo_kernel<<<dim3(std::min<uint32_t>(div_up(max_long, 256), 4096u)), dim3(256), 0, st>>>(nseg, seg_off, olong, sums2 + nb, slot_done, todo, n_todo);
-    KPOP_LAUNCH_CHECK();
-  }
-  // (with a to-do list the pairs all have work, and how many is on the device: a grid that fills the chip, striding)
-  dim3 grid(tiles ? (uint32_t)std::min<uint64_t>(max_slots, (uint64_t)cx.n_cus * 8) : capped_grid((uint64_t)max_long * max_seg));  // (eight blocks of 256 are resident per CU)
-  // The dimensions go in passes of up to 256 (four blocks of 64 a lane), 128 or 64 -- one LAUNCH per pass, so that a pass never
-  // loads blocks it has no dimensions for (300 dimensions: 256 + 44; a run-time guard on the loads brought the per-window
-  // branches back: 2.4 -> 5.2 ms at 64 dimensions).  Every launch hashes the windows again: once per 256 dimensions, not per 64.
-#define KPOP_STREAM_B(H, NT, B, D0, D1) count_twist_stream_kernel<H, NT, B, KPOP_STREAM_SB><<<grid, dim3(256), 0, st>>>(tv, d_bases, d_offsets, content, nseg, seg_off, part, pcnt, long_ids, tiles ? n_todo : n_long, max_seg, seg_windows, todo, segw, tiles ? n_todo + 1 + launch_no++ : nullptr, D0, D1)
-  int launch_no = 0;  // (a take-the-next counter per launch)
-  if (tiles && tw->n_dims > 255u * 256u) KPOP_FAIL(KPOP_ERR_UNSUPPORTED, "kpop_dev_count_twist: %u dimensions (at most 65,280 with the tile route on; kpop_tune(\"dense\", 0) lifts that)", tw->n_dims);
-#define KPOP_STREAM(H, NT)                                                        \
-  do {                                                                            \
-    for (uint32_t pos = 0; pos < tw->n_dims;) {                                    \
-      const uint32_t rem = tw->n_dims - pos;                                      \
-      if (rem > 128) {                                                            \
-        const uint32_t take = std::min(rem, 256u);                                \
-        KPOP_STREAM_B(H, NT, 4, pos, pos + take);                                 \
-        pos += take;                                                              \
-      } else if (rem > 64) {                                                      \
-        KPOP_STREAM_B(H, NT, 2, pos, pos + rem);                                  \
-        pos += rem;                                                               \
-      } else {                                                                    \
-        KPOP_STREAM_B(H, NT, 1, pos, pos + rem);                                  \
-        pos += rem;                                                               \
-      }                                                                           \
-    }                                                                             \
-  } while (0)
-#define KPOP_STREAM_SB 2
-  if (content == KPOP_PROTEIN) {
-#undef KPOP_STREAM_SB
-#define KPOP_STREAM_SB 5
-    if (hash_bits(tv.hk, content) <= 30) KPOP_STREAM(uint32_t, false); else KPOP_STREAM(uint64_t, false);
-#undef KPOP_STREAM_SB
-#define KPOP_STREAM_SB 2
-  } else if (tv.hk <= 15) {
-    if (nt) KPOP_STREAM(uint32_t, true); else KPOP_STREAM(uint32_t, false);
-  } else {
-    if (nt) KPOP_STREAM(uint64_t, true); else KPOP_STREAM(uint64_t, false);
-  }
-#undef KPOP_STREAM_SB
-#undef KPOP_STREAM
-#undef KPOP_STREAM_B
-  KPOP_LAUNCH_CHECK();
-  combine_partials_kernel<<<dim3(max_long), dim3(256), 0, st>>>(nseg, seg_off, part, pcnt, tw->n_dims, normalize, d_out, long_ids, n_long);
-  KPOP_LAUNCH_CHECK();
-  return KPOP_OK;
+  KPOP_TRY(launch_stream(c, p, w));
+  return combine_partials(c, p, w);
 }
 
 // packed.hip's fast way: a batch whose reads ALL fit the one-wavefront-per-read kernel is twisted straight from its packed words (no
-// bytes are ever made); returns 1 when it did, 0 when the batch holds longer sequences (the caller spreads the bases and takes the usual way)
+// bytes are ever made); *done = 1 when it did, 0 when the batch holds longer sequences (the caller spreads the bases and takes the usual way)
 int count_twist_wave_from_packed(const kpop_twister *tw, const uint32_t *d_codes, const uint32_t *d_invalid, const uint64_t *d_offsets, uint32_t n_reads,
                                  uint32_t max_len, int content, int normalize, double *d_out, hipStream_t st, int *done) {
   const TwisterView tv = view_of(tw);
-  const uint32_t max_windows = (max_len >= (uint32_t)tv.hk) ? max_len - tv.hk + 1 : 0;
+  const CountTwistPlan p = plan_count_twist(plan_input(tw, tv, n_reads, 0, max_len, content));  // (the batch's bases: read for the long part alone)
   *done = 0;
-  if (max_windows > kWaveMaxWindows || (content != KPOP_DNA_DS && content != KPOP_DNA_SS)) return KPOP_OK;
-  const int R = pick_R(max_windows);
-  if (tv.hk <= 15)
-    KPOP_TRY(launch_count_twist_wave_packed<uint32_t>(R, tv, d_codes, d_invalid, d_offsets, n_reads, content, normalize ? 1 : 0, d_out, st));
-  else
-    KPOP_TRY(launch_count_twist_wave_packed<uint64_t>(R, tv, d_codes, d_invalid, d_offsets, n_reads, content, normalize ? 1 : 0, d_out, st));
+  if (p.has_long || (content != KPOP_DNA_DS && content != KPOP_DNA_SS)) return KPOP_OK;
+  KPOP_TRY(launch_count_twist_reads_packed(p, tv, d_codes, d_invalid, d_offsets, n_reads, content, normalize ? 1 : 0, d_out, st));
   *done = 1;
   return KPOP_OK;
 }
@@ -2061,8 +2039,7 @@ extern "C" int kpop_dev_count_reads(const uint8_t *d_bases, const uint64_t *d_of
   if (!d_offsets || !d_scratch || !d_out_hash || !d_out_count || !d_out_offsets)
     KPOP_FAIL(KPOP_ERR_INVALID, "kpop_dev_count_reads: null argument");
   KPOP_TRY(check_count_args(k, content, "kpop_dev_count_reads"));
-  const uint32_t max_windows = (max_len >= (uint32_t)k) ? max_len - k + 1 : 0;
-  if (max_windows > kWaveMaxWindows)
+  if (windows_of(max_len, k) > kWaveMaxWindows)
     KPOP_FAIL(KPOP_ERR_UNSUPPORTED, "kpop_dev_count_reads: reads of more than %u windows go through kpop_count_reads", kWaveMaxWindows);
   hipStream_t st = as_stream(stream);
   if (n_reads == 0) {
@@ -2070,7 +2047,7 @@ extern "C" int kpop_dev_count_reads(const uint8_t *d_bases, const uint64_t *d_of
     return KPOP_OK;
   }
   void *scratch = reinterpret_cast<void *>((reinterpret_cast<uintptr_t>(d_scratch) + 63) & ~(uintptr_t)63);
-  return launch_count_wave(pick_R(max_windows), d_bases, d_offsets, n_reads, k, content, scratch, d_out_hash, d_out_count,
+  return launch_count_wave(pick_R(windows_of(max_len, k)), d_bases, d_offsets, n_reads, k, content, scratch, d_out_hash, d_out_count,
                            d_out_offsets, st);
 }
 
@@ -2099,62 +2076,43 @@ extern "C" int kpop_count_reads(const uint8_t *bases, const uint64_t *offsets, u
   KPOP_TRY(check_count_args(k, content, "kpop_count_reads"));
   if (per_read) out_offsets[0] = 0; else out_offsets[0] = out_offsets[1] = 0;
   if (n_reads == 0) return KPOP_OK;
-  uint64_t max_len = 0;
-  KPOP_TRY(check_offsets(offsets, n_reads, &max_len));
-  const uint64_t max_windows = (max_len >= (uint64_t)k) ? max_len - k + 1 : 0;
+  HostReads batch;
+  KPOP_TRY(batch.check(offsets, n_reads));
   if (!per_read) {  // -l: one spectrum for everything (bin/KPopCount.ml:60)
     uint64_t written = 0;
     return sorted_count_batch(bases, offsets, n_reads, k, content, 0, out_hash, out_count, out_offsets, out_capacity,
                               &written);
   }
-  if (max_windows > kWaveMaxWindows) {
-    // genomes: sort path, in sub-batches whose (spectrum id | hash) keys fit 63 bits
-    const int id_bits_max = 63 - hash_bits(k, content);
-    const uint64_t sub = id_bits_max >= 32 ? n_reads : std::max<uint64_t>(1, 1ull << id_bits_max);
+  if (windows_of(batch.max_len, k) > kWaveMaxWindows) {  // genomes: sort path
     uint64_t pos = 0;
     std::vector<uint64_t> loc;
-    for (uint64_t r0 = 0; r0 < n_reads; r0 += sub) {
-      const uint32_t nr = (uint32_t)std::min<uint64_t>(sub, n_reads - r0);
+    KPOP_TRY(by_key_sub_batches(n_reads, k, content, [&](uint64_t r0, uint32_t nr) -> int {
       loc.assign(nr + 1, 0);
       uint64_t written = 0;
       KPOP_TRY(sorted_count_batch(bases, offsets + r0, nr, k, content, 1, out_hash + pos, out_count + pos, loc.data(),
                                   out_capacity - pos, &written));
       for (uint32_t i = 0; i <= nr; ++i) out_offsets[r0 + i] = pos + loc[i];
       pos += written;
-    }
+      return 0;
+    }));
     out_offsets[n_reads] = pos;
     return KPOP_OK;
   }
-  const int R = pick_R((uint32_t)max_windows);
-  const uint64_t base0 = offsets[0], n_bases = offsets[n_reads] - base0;
   hipStream_t st = nullptr;
-  DevBuf d_bases, d_off, d_scr, d_oo, d_oh, d_oc;
-  uint64_t worst = 0;  // one entry per window
-  std::vector<uint64_t> rel(n_reads + 1);
-  for (uint32_t r = 0; r <= n_reads; ++r) rel[r] = offsets[r] - base0;
-  for (uint32_t r = 0; r < n_reads; ++r) {
-    const uint64_t len = rel[r + 1] - rel[r];
-    worst += len >= (uint64_t)k ? len - k + 1 : 0;
-  }
-  KPOP_TRY(d_bases.alloc(n_bases));
-  KPOP_TRY(d_off.alloc((uint64_t)(n_reads + 1) * 8));
-  KPOP_TRY(d_scr.alloc(count_wave_scratch_bytes(n_reads)));
-  KPOP_TRY(d_oo.alloc((uint64_t)(n_reads + 1) * 8));
-  KPOP_TRY(d_oh.alloc(worst * 8));
-  KPOP_TRY(d_oc.alloc(worst * 4));
-  if (n_bases) KPOP_HIP(hipMemcpyAsync(d_bases.p, bases + base0, n_bases, hipMemcpyHostToDevice, st));
-  KPOP_HIP(hipMemcpyAsync(d_off.p, rel.data(), (uint64_t)(n_reads + 1) * 8, hipMemcpyHostToDevice, st));
-  KPOP_TRY(launch_count_wave(R, d_bases.as<uint8_t>(), d_off.as<uint64_t>(), n_reads, k, content, d_scr.p, d_oh.as<uint64_t>(),
-                             d_oc.as<uint32_t>(), d_oo.as<uint64_t>(), st));
-  KPOP_HIP(hipMemcpyAsync(out_offsets, d_oo.p, (uint64_t)(n_reads + 1) * 8, hipMemcpyDeviceToHost, st));
+  ReadSpectra spectra;
+  KPOP_TRY(batch.alloc(offsets));
+  KPOP_TRY(spectra.alloc(batch, k));
+  KPOP_TRY(batch.copy(bases, st));
+  KPOP_TRY(spectra.count(batch, k, content, st));
+  KPOP_HIP(hipMemcpyAsync(out_offsets, spectra.d_oo.p, (uint64_t)(n_reads + 1) * 8, hipMemcpyDeviceToHost, st));
   KPOP_HIP(hipStreamSynchronize(st));
   const uint64_t total = out_offsets[n_reads];
   if (total > out_capacity)
     KPOP_FAIL(KPOP_ERR_CAPACITY, "kpop_count_reads: %llu distinct (read,k-mer) pairs, capacity %llu",
               (unsigned long long)total, (unsigned long long)out_capacity);
   if (total) {
-    KPOP_HIP(hipMemcpyAsync(out_hash, d_oh.p, total * 8, hipMemcpyDeviceToHost, st));
-    KPOP_HIP(hipMemcpyAsync(out_count, d_oc.p, total * 4, hipMemcpyDeviceToHost, st));
+    KPOP_HIP(hipMemcpyAsync(out_hash, spectra.d_oh.p, total * 8, hipMemcpyDeviceToHost, st));
+    KPOP_HIP(hipMemcpyAsync(out_count, spectra.d_oc.p, total * 4, hipMemcpyDeviceToHost, st));
   }
   KPOP_HIP(hipStreamSynchronize(st));
   return KPOP_OK;
@@ -2166,19 +2124,15 @@ extern "C" int kpop_count_twist(const kpop_twister *tw, const uint8_t *bases, co
   ArenaScope scratch;
   if (!tw || !offsets || (!out && n_reads)) KPOP_FAIL(KPOP_ERR_INVALID, "kpop_count_twist: null argument");
   if (n_reads == 0) return KPOP_OK;
-  uint64_t max_len = 0;
-  KPOP_TRY(check_offsets(offsets, n_reads, &max_len));
-  const uint64_t base0 = offsets[0], n_bases = offsets[n_reads] - base0;
+  HostReads batch;
+  KPOP_TRY(batch.check(offsets, n_reads));
+  const uint64_t n_bases = batch.n_items;
   hipStream_t st = nullptr;
-  DevBuf d_bases, d_off, d_out;
-  KPOP_TRY(d_bases.alloc(n_bases));
-  KPOP_TRY(d_off.alloc((uint64_t)(n_reads + 1) * 8));
+  DevBuf d_out;
+  KPOP_TRY(batch.alloc(offsets));
   KPOP_TRY(d_out.alloc((uint64_t)n_reads * tw->n_dims * 8));
-  std::vector<uint64_t> rel(n_reads + 1);
-  for (uint32_t r = 0; r <= n_reads; ++r) rel[r] = offsets[r] - base0;
-  if (n_bases) KPOP_HIP(hipMemcpyAsync(d_bases.p, bases + base0, n_bases, hipMemcpyHostToDevice, st));
-  KPOP_HIP(hipMemcpyAsync(d_off.p, rel.data(), (uint64_t)(n_reads + 1) * 8, hipMemcpyHostToDevice, st));
-  if (max_len > 0xFFFFFFFFull) KPOP_FAIL(KPOP_ERR_UNSUPPORTED, "kpop_count_twist: sequence longer than 2^32 bases");
+  KPOP_TRY(batch.copy(bases, st));
+  if (batch.max_len > 0xFFFFFFFFull) KPOP_FAIL(KPOP_ERR_UNSUPPORTED, "kpop_count_twist: sequence longer than 2^32 bases");
   // kpop_tune("dense", 2): batches of assemblies at small k (every sequence holds a fifth or more of the twister's k-mers on
   // average, the twister small enough for the dense image) go through the u32 image and the f64 matrix cores; results
   // agree with the sparse kernels to rounding
@@ -2187,11 +2141,11 @@ extern "C" int kpop_count_twist(const kpop_twister *tw, const uint8_t *bases, co
   if (dense_image) {
     DevBuf d_work;
     KPOP_TRY(d_work.alloc(kpop_dev_count_twist_dense_workspace_bytes(tw, n_reads)));
-    KPOP_TRY(kpop_dev_count_twist_dense(tw, d_bases.as<uint8_t>(), d_off.as<uint64_t>(), n_reads, content, normalize, d_work.p,
+    KPOP_TRY(kpop_dev_count_twist_dense(tw, batch.d_bases.as<uint8_t>(), batch.d_off.as<uint64_t>(), n_reads, content, normalize, d_work.p,
                                         d_out.as<double>(), st));
   } else
-  KPOP_TRY(kpop_dev_count_twist(tw, d_bases.as<uint8_t>(), d_off.as<uint64_t>(), n_reads, n_bases, (uint32_t)max_len,
-                                content, normalize, d_out.as<double>(), st));
+    KPOP_TRY(kpop_dev_count_twist(tw, batch.d_bases.as<uint8_t>(), batch.d_off.as<uint64_t>(), n_reads, n_bases, (uint32_t)batch.max_len,
+                                  content, normalize, d_out.as<double>(), st));
   KPOP_HIP(hipMemcpyAsync(out, d_out.p, (uint64_t)n_reads * tw->n_dims * 8, hipMemcpyDeviceToHost, st));
   KPOP_HIP(hipStreamSynchronize(st));
   return KPOP_OK;
@@ -2212,10 +2166,10 @@ extern "C" int kpop_spectra_twist(const kpop_twister *tw, const uint8_t *bases, 
   if (hash_bits(k, content) > 2 * tw->k)
     KPOP_FAIL(KPOP_ERR_INVALID, "kpop_spectra_twist: k=%d (%d-bit hashes) above the twister's k=%d (%d bits)", k, hash_bits(k, content), tw->k, 2 * tw->k);
   if (n_reads == 0) return KPOP_OK;
-  uint64_t max_len = 0;
-  KPOP_TRY(check_offsets(offsets, n_reads, &max_len));
-  if (max_len > 0xFFFFFFFFull) KPOP_FAIL(KPOP_ERR_UNSUPPORTED, "kpop_spectra_twist: sequence longer than 2^32 bases");
-  const uint64_t max_windows = (max_len >= (uint64_t)k) ? max_len - k + 1 : 0;
+  HostReads batch;
+  KPOP_TRY(batch.check(offsets, n_reads));
+  if (batch.max_len > 0xFFFFFFFFull) KPOP_FAIL(KPOP_ERR_UNSUPPORTED, "kpop_spectra_twist: sequence longer than 2^32 bases");
+  const uint64_t max_windows = windows_of(batch.max_len, k);
   hipStream_t st = nullptr;
   kpop_twister view = *tw;  // same device arrays, the caller's counting k
   view.hk = k;
@@ -2224,50 +2178,30 @@ extern "C" int kpop_spectra_twist(const kpop_twister *tw, const uint8_t *bases, 
   DevBuf d_out;
   KPOP_TRY(d_out.alloc(out_bytes));
   if (max_windows <= kWaveMaxWindows) {
-    const uint64_t base0 = offsets[0], n_bases = offsets[n_reads] - base0;
-    DevBuf d_bases, d_off;
-    KPOP_TRY(d_bases.alloc(n_bases));
-    KPOP_TRY(d_off.alloc((uint64_t)(n_reads + 1) * 8));
-    std::vector<uint64_t> rel(n_reads + 1);
-    for (uint32_t r = 0; r <= n_reads; ++r) rel[r] = offsets[r] - base0;
-    if (n_bases) KPOP_HIP(hipMemcpyAsync(d_bases.p, bases + base0, n_bases, hipMemcpyHostToDevice, st));
-    KPOP_HIP(hipMemcpyAsync(d_off.p, rel.data(), (uint64_t)(n_reads + 1) * 8, hipMemcpyHostToDevice, st));
-    const int R = pick_R((uint32_t)max_windows);
+    ReadSpectra spectra;  // (the spectra on the device: up to 32 dimensions)
+    KPOP_TRY(batch.alloc(offsets));
+    if (tw->n_dims <= 32) KPOP_TRY(spectra.alloc(batch, k));
+    KPOP_TRY(batch.copy(bases, st));
     if (tw->n_dims > 32) {
-      if (k <= 15)
-        KPOP_TRY(launch_count_twist_wave<uint32_t>(R, tv, d_bases.as<uint8_t>(), d_off.as<uint64_t>(), nullptr, n_reads, content, normalize, d_out.as<double>(), st));
-      else
-        KPOP_TRY(launch_count_twist_wave<uint64_t>(R, tv, d_bases.as<uint8_t>(), d_off.as<uint64_t>(), nullptr, n_reads, content, normalize, d_out.as<double>(), st));
+      const CountTwistPlan p = plan_count_twist(plan_input(&view, tv, n_reads, batch.n_items, (uint32_t)batch.max_len, content));
+      KPOP_TRY(launch_count_twist_reads(p, tv, batch.d_bases.as<uint8_t>(), batch.d_off.as<uint64_t>(), n_reads, content, normalize, d_out.as<double>(), st));
     } else {
-      DevBuf d_scr, d_oo, d_oh, d_oc;
-      uint64_t worst = 0;
-      for (uint32_t r = 0; r < n_reads; ++r) {
-        const uint64_t len = rel[r + 1] - rel[r];
-        worst += len >= (uint64_t)k ? len - k + 1 : 0;
-      }
-      KPOP_TRY(d_scr.alloc(count_wave_scratch_bytes(n_reads)));
-      KPOP_TRY(d_oo.alloc((uint64_t)(n_reads + 1) * 8));
-      KPOP_TRY(d_oh.alloc(worst * 8));
-      KPOP_TRY(d_oc.alloc(worst * 4));
-      KPOP_TRY(launch_count_wave(R, d_bases.as<uint8_t>(), d_off.as<uint64_t>(), n_reads, k, content, d_scr.p, d_oh.as<uint64_t>(),
-                                 d_oc.as<uint32_t>(), d_oo.as<uint64_t>(), st));
-      KPOP_TRY(launch_twist_csr<uint32_t>(tv, d_oh.as<uint64_t>(), d_oc.as<uint32_t>(), d_oo.as<uint64_t>(), n_reads, max_windows, normalize,
+      KPOP_TRY(spectra.count(batch, k, content, st));
+      KPOP_TRY(launch_twist_csr<uint32_t>(tv, spectra.d_oh.as<uint64_t>(), spectra.d_oc.as<uint32_t>(), spectra.d_oo.as<uint64_t>(), n_reads, max_windows, normalize,
                                           d_out.as<double>(), st));
     }
   } else {
-    // genomes: sort path, in sub-batches whose (spectrum id | hash) keys fit 63 bits, then the line-by-line twist
-    const int id_bits_max = 63 - hash_bits(k, content);
-    const uint64_t sub = id_bits_max >= 32 ? n_reads : std::max<uint64_t>(1, 1ull << id_bits_max);
-    for (uint64_t r0 = 0; r0 < n_reads; r0 += sub) {
-      const uint32_t nr = (uint32_t)std::min<uint64_t>(sub, n_reads - r0);
-      ArenaScope batch;
+    // genomes: sort path, then the line-by-line twist
+    KPOP_TRY(by_key_sub_batches(n_reads, k, content, [&](uint64_t r0, uint32_t nr) -> int {
+      ArenaScope sub_batch;
       SortedSpectra S;
       KPOP_TRY(sorted_count_device(bases, offsets + r0, nr, k, content, 1, ~0ull, S, st));
       // (no spectrum has more lines than its sequence has windows: a few long genomes then take the segmented launch)
       KPOP_TRY(launch_twist_csr<uint32_t>(tv, S.d_oh.as<uint64_t>(), S.d_oc.as<uint32_t>(), S.d_oo.as<uint64_t>(), nr, max_windows, normalize,
                                           d_out.as<double>() + r0 * tw->n_dims, st));
-      KPOP_HIP(hipStreamSynchronize(st));  // the batch's scratch goes back to the arena at the end of this scope
-    }
+      KPOP_HIP(hipStreamSynchronize(st));  // the sub-batch's scratch goes back to the arena at the end of this scope
+      return 0;
+    }));
   }
   KPOP_HIP(hipMemcpyAsync(out, d_out.p, out_bytes, hipMemcpyDeviceToHost, st));
   KPOP_HIP(hipStreamSynchronize(st));
@@ -2280,23 +2214,22 @@ extern "C" int kpop_twist(const kpop_twister *tw, const uint64_t *hash, const do
   ArenaScope scratch;
   if (!tw || !offsets || (!out && n_spectra)) KPOP_FAIL(KPOP_ERR_INVALID, "kpop_twist: null argument");
   if (n_spectra == 0) return KPOP_OK;
-  uint64_t max_lines = 0;
-  KPOP_TRY(check_offsets(offsets, n_spectra, &max_lines));
-  const uint64_t base0 = offsets[0], n_lines = offsets[n_spectra] - base0;
+  HostOffsets spectra;
+  KPOP_TRY(spectra.check(offsets, n_spectra));
+  const uint64_t base0 = spectra.base0, n_lines = spectra.n_items, max_lines = spectra.max_len;
   if (n_lines && (!hash || !value)) KPOP_FAIL(KPOP_ERR_INVALID, "kpop_twist: null hash/value");
   hipStream_t st = nullptr;
-  DevBuf d_h, d_v, d_off, d_out;
+  DevBuf d_h, d_v, d_out;
   KPOP_TRY(d_h.alloc(n_lines * 8));
   KPOP_TRY(d_v.alloc(n_lines * 8));
-  KPOP_TRY(d_off.alloc((uint64_t)(n_spectra + 1) * 8));
+  KPOP_TRY(spectra.alloc(offsets));
   KPOP_TRY(d_out.alloc((uint64_t)n_spectra * tw->n_dims * 8));
-  std::vector<uint64_t> rel(n_spectra + 1);
-  for (uint32_t r = 0; r <= n_spectra; ++r) rel[r] = offsets[r] - base0;
   if (n_lines) {
     KPOP_HIP(hipMemcpyAsync(d_h.p, hash + base0, n_lines * 8, hipMemcpyHostToDevice, st));
     KPOP_HIP(hipMemcpyAsync(d_v.p, value + base0, n_lines * 8, hipMemcpyHostToDevice, st));
   }
-  KPOP_HIP(hipMemcpyAsync(d_off.p, rel.data(), (uint64_t)(n_spectra + 1) * 8, hipMemcpyHostToDevice, st));
+  KPOP_TRY(spectra.copy(st));
+  const DevBuf &d_off = spectra.d_off;
   // kpop_tune("dense", 1): always the contraction on the matrix cores; 2: when the batch is dense enough for it to win
   // (measured crossover, DESIGN.md 5.9: >= 256 spectra holding >= 40 % of the twister's k-mers each); 0 (default): never --
   // the sparse form is the reference's order of additions, the dense one agrees with it to rounding only

@@ -1,5 +1,5 @@
-// tile_pipe.h -- count_twist_tile_pipe_kernel: the consensus + residual scheme of count_twist_tile_kernel (count_twist.hip, which
-// includes this file after the tile route's constants) as a two-stage software pipeline inside ONE persistent block per CU.
+// tile_pipe.h -- count_twist_tile_pipe_kernel: the consensus + residual scheme of count_twist_tile_kernel (count_twist.hip; the
+// routes' constants are count_twist_plan.h's) as a two-stage software pipeline inside ONE persistent block per CU.
 //
 // Round 4's kernel ran its phases one after the other between block-wide barriers: the matrix cores were busy 0.35 of a chunk's
 // time (0.17 of the launch) while bases were staged, rows looked up, the set built and the windows counted.  Here the block's
@@ -20,12 +20,21 @@
 #pragma once
 #include <type_traits>
 
+#include "count_twist_plan.h"
+#include "kmer.h"
+#include "read_hash.h"
+#include "twister.h"
+
 namespace kpop {
 
-constexpr uint32_t kPipeG = 64;                  // sequences a chunk
+using f64x4 = __attribute__((ext_vector_type(4))) double;
+// phase clocks of the tile kernels (kpop_tune("dbg", 16 << 24) only: s_memtime ticks of every block's thread 0, summed
+// over blocks and chunks; read and cleared by kpop_debug_counters)
+__device__ unsigned long long g_tile_stamps[16];
+
+constexpr uint32_t kPipeG = 64;                 // sequences a chunk
 constexpr uint32_t kPipeXW = 194;                // dwords of a row of X: 768 one-byte counts + 8 (2 mod 32: a half-wavefront's 16 rows x 2 columns of a ds_read_b32 on 32 banks)
 constexpr uint32_t kPipeAbsent = 0xFFFFFFFFu;    // a member's number when the twister has no row for it
-constexpr uint32_t kPipeListCap = 8 * kTileS;    // entries of a producer wavefront's residual list: 8 sequences x 512 windows
 // A sequence's stretch is staged as 2-BIT CODES, in 16-base units (33 of them: 512 windows + up to 14 bases more):
 //   F[33]  the codes first base most significant (a window's forward hash is a funnel shift of two of these dwords),
 //   R[33]  the COMPLEMENTS' codes first base least significant (its reverse complement's hash likewise),

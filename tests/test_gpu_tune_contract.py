@@ -19,8 +19,8 @@ from tune_contract import KNOBS, tuned
 
 pytestmark = pytest.mark.gpu
 
-# mirrors count_twist.hip ("static int pick_R", "constexpr uint32_t kWaveMaxWindows", "constexpr uint32_t kTileMinSeqs",
-# "constexpr uint32_t kSegWindows", and the segment length of kpop_dev_count_twist: "uint32_t seg_windows = cx.tune_seg ?")
+# mirrors kpop_amd/csrc/count_twist_plan.h (pick_R, kWaveMaxWindows, kTileMinSeqs, kSegWindows, and the segment length:
+# default_seg_windows); tests/host/count_twist_plan_check.cpp holds the C++ side to the same formulas without a GPU
 WAVE_MAX_WINDOWS, TILE_MIN_SEQS, SEG_WINDOWS_MAX = 512, 16, 16384
 DENSE_IMAGE_MAX_ROWS = 36864  # count_twist.hip, kpop_count_twist ("const bool dense_image =")
 

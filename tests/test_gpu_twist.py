@@ -832,7 +832,7 @@ def test_a_batch_past_the_tile_routes_bound_goes_through_in_sub_batches(kpop, or
     scale = float(stream_rows.abs().max())
     assert float((whole - stream_rows).abs().max()) <= 1e-12 * scale
     assert float((split - stream_rows).abs().max()) <= 1e-12 * scale
-    m = (40 << 20) // ((L // 512 + 2) * (d * 8 + 16))  # sequences a sub-batch (count_twist.hip)
+    m = (40 << 20) // ((L // 512 + 2) * (d * 8 + 16))  # sequences a sub-batch (count_twist_plan.h, plan_count_twist)
     assert 4096 <= m < n and not torch.equal(split, whole)  # (other groups share a consensus set: another order of additions)
     pick = [0, 1, m - 1, m, m + 1, n - 1]
     sb = np.concatenate([bases[r * L:(r + 1) * L].cpu().numpy() for r in pick])
