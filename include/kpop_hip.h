@@ -1041,6 +1041,60 @@ int kpop_distance_silhouette(const double *m, uint32_t rows, uint32_t n_dims, co
 int kpop_silhouette_summary(uint32_t r1, const uint32_t *class_of, uint32_t n_classes, const double *silhouette,
                             double *class_mean, double *overall_mean);
 
+/* ------------------------------------------------- farthest-first traversal of a resident set (k diverse rows, every k)
+ * kpop_representatives_within thins a set at a radius that is known; this is its partner when a COUNT is known, or
+ * nothing: one ordering of the rows (Gonzalez 1985) whose every prefix is a cover of the set, its radius written beside
+ * it.  d(j, i) is the reference chain's distance (lib/Space.ml:182-205 with the adaptors of lib/Matrix.ml:243-250) -- the
+ * bits kpop_refset_distance_rowwise writes under kpop_tune("distance_mfma", 0) when the set's own rows are the query --
+ * whatever kpop_tune says; symmetric bit for bit, the pair i == j never examined.
+ * STATE: every row has a COVER DISTANCE, +inf at first, and a COVER ROW, KPOP_NOISE at first.  Picking row c marks it
+ * picked; for every unpicked row x, d(x, c) replaces the cover distance iff it is a number and strictly less than it (-0
+ * taken as +0), and the cover row becomes c.  A NaN distance covers nothing; a tie keeps the earlier pick.
+ * ORDER: pick t < n_seeds is seeds[t].  Every later pick is the unpicked row greatest under (cover distance descending,
+ * row index ascending): with no seeds the first pick is row 0.  Before a pick that is not a seed the traversal stops if
+ * that row's cover distance is <= cover_radius (negative: never; +inf without seeds: at once; NaN: KPOP_ERR_INVALID); it
+ * also stops at max_picks picks (above r1: r1).  A row with a NaN in it keeps +inf and is picked as soon as its index
+ * comes up among the +inf rows.
+ * RESULT: *n_picks; for pick t, pick[t] the row, pick_radius[t] its cover distance at the moment it was picked (+inf for
+ * the first pick, a zero written as +0) and pick_parent[t] its cover row at that moment or KPOP_NOISE; for row i,
+ * rep_of[i] = i and rep_dist[i] = +0 when it was picked, otherwise its cover row (KPOP_NOISE: none) and its cover
+ * distance (+inf: none).  *n_passes: how often the call walked the whole set -- a fact about the run, not part of the
+ * contract.  Every output pointer but n_picks may be NULL.  r1 = 0 or max_picks = 0: KPOP_OK and *n_picks = 0.
+ * PROPERTIES: past the seeds and pick 0, pick_radius never increases; with cover_radius < 0 and the same seeds the result
+ * at max_picks = k is the first k entries of the result at any larger max_picks, bit for bit; with seeds = pick[0 .. k)
+ * of an earlier run the run reproduces pick, pick_radius and pick_parent from 0 on -- after kpop_refset_append the old
+ * picks go in as seeds and the traversal goes on over the grown set; a run stopped at cover_radius = R >= 0 leaves every
+ * row with rep_dist <= R (or +inf: a NaN) and every pick past the seeds with pick_radius > R, so that the picks lie
+ * pairwise farther apart than R, a maximal independent set of kpop_clusters_within's graph at R; the first k picks are a
+ * 2-approximation of the best k centres; rep_dist[i] is the least d(i, pick[t]) and rep_of[i] the pick at the first such
+ * t.  A strict total order and no floating-point sum across rows: the same bits on every run.
+ * ERRORS: a seed >= r1, a repeated seed, n_seeds > max_picks: KPOP_ERR_INVALID (the device form trusts the seeds'
+ * values and holds them inside the set).  The set's limits, slot and thread ownership hold as for every call on a set.
+ * Semantics: INTEGRATION.md 6l; timings: profiles/farthest_first.md. */
+/* (lib/Space.ml:182-205; lib/Matrix.ml:243-250.)  Host arrays: seeds[n_seeds]; pick, pick_radius, pick_parent with room
+   for min(max_picks, r1) entries, the first *n_picks written; rep_of[r1], rep_dist[r1].  Synchronises.                  */
+int kpop_farthest_first(kpop_refset *rs, uint32_t max_picks, double cover_radius, const uint32_t *seeds,
+                        uint32_t n_seeds, uint32_t *n_picks, uint32_t *pick, double *pick_radius, uint32_t *pick_parent,
+                        uint32_t *rep_of, double *rep_dist, uint32_t *n_passes);
+/* bytes of d_work for kpop_dev_farthest_first (lib/Space.ml:182-205 over the set against itself, see the block above),
+   for the set's r1 at the time of the call: 12 bytes a row for the cover distances and rows, 16 bytes a pick, 24 KiB of
+   buckets -- O(r1 + max_picks); no copy of rows                                                                        */
+uint64_t kpop_dev_farthest_first_workspace_bytes(const kpop_refset *rs, uint32_t max_picks);
+/* (lib/Space.ml:182-205; lib/Matrix.ml:243-250.)  Enqueues only, reads nothing back, allocates nothing: the seeds' groups,
+   then min(max_picks, r1) - n_seeds + 1 passes, each of which returns at once after the traversal has stopped.
+   d_seeds[n_seeds] TRUSTED to be distinct; d_pick, d_pick_radius, d_pick_parent [min(max_picks, r1)] each or NULL,
+   d_rep_of[r1] or NULL, d_rep_dist[r1] or NULL, d_counts[2] = {n_picks, n_passes}.                                      */
+int kpop_dev_farthest_first(kpop_refset *rs, uint32_t max_picks, double cover_radius, const uint32_t *d_seeds,
+                            uint32_t n_seeds, void *d_work, uint32_t *d_pick, double *d_pick_radius,
+                            uint32_t *d_pick_parent, uint32_t *d_rep_of, double *d_rep_dist, uint32_t *d_counts,
+                            void *stream);
+/* unprepared convenience (lib/Matrix.ml:191-266 for the distances, m against itself): a temporary set over m, then
+   kpop_farthest_first                                                                                                  */
+int kpop_distance_farthest_first(const double *m, uint32_t rows, uint32_t n_dims, const double *metric, int kind,
+                                 double p, int normalize, uint32_t max_picks, double cover_radius, const uint32_t *seeds,
+                                 uint32_t n_seeds, uint32_t *n_picks, uint32_t *pick, double *pick_radius,
+                                 uint32_t *pick_parent, uint32_t *rep_of, double *rep_dist, uint32_t *n_passes);
+
 /* ------------------------------------------------- k-mer database (KPopCountDB)
  * the operations of lib/KMerDB.ml that touch every count.  A database is the reference's
  * `storage: I32BAVector.t array` (lib/KMerDB.ml:54-63): n_cols spectra ("columns"), each a vector of n_rows int32

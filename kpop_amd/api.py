@@ -901,6 +901,25 @@ class RefSet:
         check(_lib.load().kpop_silhouette(self._h, _p(_nz(class_of, np.uint32), C.c_uint32), n_classes, *_silhouette_pointers(res)))
         return _silhouette_cut(res, r1, n_classes)
 
+    def farthest_first(self, max_picks=None, cover_radius=-1.0, seeds=None):
+        """The farthest-first traversal of the set -> FarthestFirst(pick u32 [n], pick_radius f64 [n], pick_parent u32 [n], rep_of u32 [r1],
+        rep_dist f64 [r1], n_passes).  Every row has a cover distance (+inf at first) and a cover row (NOISE at first); a pick lowers the
+        cover distance of every unpicked row that lies strictly nearer to it (a NaN covers nothing, a tie keeps the earlier pick).  The
+        seeds are picked first, in their order; every later pick is the unpicked row with the greatest cover distance, ties to the smaller
+        row (without seeds the first pick is row 0).  It stops at max_picks picks (None: every row), or before a pick that is not a seed
+        and whose cover distance is <= cover_radius (negative: never).  pick_radius[t], pick_parent[t]: the cover distance and row of
+        pick t when it was picked; rep_of, rep_dist: a picked row itself at +0, any other row its cover row and distance.  Every prefix
+        of the picks is a cover of the set at the radius written beside the next pick; seeds=pick[:k] of an earlier run, or that run's
+        whole tuple, reproduces it and goes on -- also after append.  The same bits on every run; n_passes is a fact about the run
+        (kpop_farthest_first, include/kpop_hip.h)."""
+        r1 = self.info()["r1"]
+        max_picks, seeds = _farthest_first_arguments(r1, max_picks, seeds)
+        res = _farthest_first_result(r1, max_picks)
+        n, passes = C.c_uint32(), C.c_uint32()
+        check(_lib.load().kpop_farthest_first(self._h, max_picks, float(cover_radius), _p(_nz(seeds, np.uint32), C.c_uint32), len(seeds), C.byref(n),
+                                              *_farthest_first_pointers(res), C.byref(passes)))
+        return _farthest_first_cut(res, r1, int(n.value), int(passes.value))
+
     def spanning_forest(self, max_distance=float("inf")):
         """The single-linkage tree of the set: the minimum spanning forest of the graph that joins rows i < j iff d(j, i) <= max_distance,
         under the order (d, i, j) -> (edge_i u32, edge_j u32, edge_dist f64, labels u32 [r1]).  The order is strict, so the forest is
@@ -1577,6 +1596,65 @@ def silhouette_summary(class_of, silhouette, n_classes=None):
     check(_lib.load().kpop_silhouette_summary(len(silhouette), _p(_nz(class_of, np.uint32), C.c_uint32), n_classes, _p(_nz(silhouette, np.float64), C.c_double),
                                               _p(class_mean, C.c_double), C.byref(overall)))
     return class_mean[:n_classes], float(overall.value)
+
+
+FarthestFirst = collections.namedtuple("FarthestFirst", "pick pick_radius pick_parent rep_of rep_dist n_passes")
+
+
+def _farthest_first_arguments(rows, max_picks, seeds):
+    """max_picks None: every row; seeds None: none, a FarthestFirst: its picks"""
+    max_picks = rows if max_picks is None else int(max_picks)
+    if not 0 <= max_picks <= 0xFFFFFFFF:
+        raise ValueError("max_picks: a count of rows")
+    if isinstance(seeds, FarthestFirst):
+        seeds = seeds.pick
+    seeds = np.zeros(0, dtype=np.uint32) if seeds is None else np.asarray(seeds)
+    if seeds.ndim != 1 or (len(seeds) and (seeds.min() < 0 or seeds.max() > 0xFFFFFFFF)):
+        raise ValueError("seeds: row indices")
+    return max_picks, _c(seeds, np.uint32)
+
+
+def _farthest_first_result(rows, max_picks):
+    k, n = max(min(max_picks, rows), 1), max(rows, 1)
+    return (np.zeros(k, dtype=np.uint32), np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.uint32), np.zeros(n, dtype=np.uint32),
+            np.zeros(n, dtype=np.float64))
+
+
+def _farthest_first_pointers(res):
+    return [_p(x, C.c_double if x.dtype == np.float64 else C.c_uint32) for x in res]
+
+
+def _farthest_first_cut(res, rows, n, n_passes):
+    return FarthestFirst(res[0][:n], res[1][:n], res[2][:n], res[3][:rows], res[4][:rows], n_passes)
+
+
+def dev_farthest_first_workspace_bytes(rs, max_picks):
+    """the size of d_work for dev_farthest_first, for the set's r1 at the time of the call"""
+    return int(_lib.load().kpop_dev_farthest_first_workspace_bytes(rs.handle, int(max_picks)))
+
+
+def dev_farthest_first(rs, max_picks, cover_radius, d_work, d_counts, d_pick=None, d_pick_radius=None, d_pick_parent=None, d_rep_of=None, d_rep_dist=None,
+                       d_seeds=None, n_seeds=0, stream=0):
+    """enqueue only: d_counts[2] (u32: n_picks, n_passes); d_pick / d_pick_parent (u32) and d_pick_radius (f64) with room for min(max_picks, r1)
+    entries, d_rep_of (u32 [r1]), d_rep_dist (f64 [r1]), each or None; d_seeds (u32 [n_seeds]) is trusted to hold distinct rows"""
+    check(_lib.load().kpop_dev_farthest_first(rs.handle, int(max_picks), float(cover_radius), d_seeds, int(n_seeds), d_work, d_pick, d_pick_radius,
+                                              d_pick_parent, d_rep_of, d_rep_dist, d_counts, stream))
+
+
+def distance_farthest_first(m, metric, kind=EUCLIDEAN, p=2.0, normalize=True, max_picks=None, cover_radius=-1.0, seeds=None):
+    """RefSet(m, ...).farthest_first(max_picks, cover_radius, seeds) without keeping the set: one call of kpop_distance_farthest_first ->
+    FarthestFirst"""
+    m, metric = _c(m, np.float64), _c(metric, np.float64)
+    if m.ndim != 2 or m.shape[1] != len(metric):
+        raise ValueError("Incompatible_geometries")  # lib/Matrix.ml:193-194
+    rows = m.shape[0]
+    max_picks, seeds = _farthest_first_arguments(rows, max_picks, seeds)
+    res = _farthest_first_result(rows, max_picks)
+    n, passes = C.c_uint32(), C.c_uint32()
+    check(_lib.load().kpop_distance_farthest_first(_p(_nz(m, np.float64), C.c_double), rows, len(metric), _p(_nz(metric, np.float64), C.c_double), int(kind),
+                                                   float(p), 1 if normalize else 0, max_picks, float(cover_radius), _p(_nz(seeds, np.uint32), C.c_uint32),
+                                                   len(seeds), C.byref(n), *_farthest_first_pointers(res), C.byref(passes)))
+    return _farthest_first_cut(res, rows, int(n.value), int(passes.value))
 
 
 def dense_labels(labels):
