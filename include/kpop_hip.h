@@ -1095,6 +1095,64 @@ int kpop_distance_farthest_first(const double *m, uint32_t rows, uint32_t n_dims
                                  uint32_t n_seeds, uint32_t *n_picks, uint32_t *pick, double *pick_radius,
                                  uint32_t *pick_parent, uint32_t *rep_of, double *rep_dist, uint32_t *n_passes);
 
+/* ------------------------------------------------- k-medoids on a resident set (kmedoids.hip)
+ * Clusters when a COUNT is known and no radius is: n_medoids groups, each around the real row that stands for it, every
+ * other row filed under its nearest centre.  Alternating k-medoids (Voronoi iteration; Park & Jun 2009) on the set's r1
+ * rows; d(j, i) is the distance of kpop_farthest_first and kpop_silhouette: the reference chain's bits, symmetric bit for
+ * bit, the pair i == j never examined, no kpop_tune key read; all three kinds, normalised or not.
+ * ASSIGNMENT of a labelling to a medoid list M[0 .. k): row M[c] has class c and dist +0 (a medoid always belongs to its
+ * own position, also when it is a duplicate of an earlier medoid: no class is ever empty); every other row j gets the
+ * class least under (d(j, M[c]) with -0 taken as +0, c ascending) over the c whose distance is a number, and dist[j] is
+ * that distance; a row with no such c is LEFT OUT: class_of = KPOP_NO_CLASS, dist = +inf, own_mean = NaN, in no sum.
+ * own_mean[j] is kpop_silhouette's for that labelling -- the sum of d(j, i) over the other rows of j's class divided by
+ * n_c - 1, +0 when n_c == 1 -- WITH THE BITS kpop_silhouette writes for the same class_of.
+ * UPDATE: M'[c] is the member of class c least under (own_mean with -0 as +0, row index) among the members whose own_mean
+ * is a number (kpop_silhouette's medoid); a class with no such member keeps M[c].
+ * THE LOOP:   L = assign(M = init); cost[0]; n_iter = 0
+ *             for t = 0, 1, ...:  own_mean = within-class means of L;  M' = update
+ *                                 if M' == M:       converged = 1, stop
+ *                                 if t == max_iter: converged = 0, stop
+ *                                 M = M';  L = assign(M);  n_iter += 1;  cost[n_iter]
+ * RESULT, always consistent: class_of / dist are the assignment to medoid[], own_mean and class_rows are of that
+ * labelling.  max_iter = 0 is the plain assignment to given rows (the nearest of ALL the representatives a caller
+ * holds), converged saying whether they are a fixed point already.  cost[t] is the sum of dist over the rows not left
+ * out, summed in an order that is a fixed function of r1, without a floating-point atomic: within r1 2^-53 relative of
+ * the exact sum, exact where every partial sum is representable; the entries of cost[max_iter + 1] past n_iter are the
+ * quiet NaN.
+ * PROPERTIES: the same bits on every run; a run of a rounds followed by a run of b rounds from its medoid[] gives the
+ * medoid, class_of, dist, own_mean, class_rows and converged of one run of a + b rounds, bit for bit, its cost the first
+ * run's followed by the second's from index 1 -- after kpop_refset_append the old medoids go in as init; in exact
+ * arithmetic cost never increases; kpop_silhouette(class_of, n_medoids) gives own_mean bit for bit, and its medoid is
+ * medoid[] when converged, the next round's medoid[] otherwise; permuting init permutes medoid / class_rows and relabels
+ * class_of, dist keeps its bits (own_mean too wherever no row is equidistant from two medoids).
+ * ERRORS: n_medoids == 0, n_medoids > r1, a null init, and in the host forms an init[c] >= r1 or a repeated init row:
+ * KPOP_ERR_INVALID (the device form trusts distinctness and holds every index inside the set); n_medoids > 65,535:
+ * KPOP_ERR_UNSUPPORTED (the 16-bit class key).  Every output pointer may be NULL except n_iter and converged (d_counts).
+ * Semantics: INTEGRATION.md 6m; timings: profiles/kmedoids.md. */
+/* (lib/Space.ml:182-205; lib/Matrix.ml:243-250.)  Host arrays: init[n_medoids]; medoid, class_rows [n_medoids];
+   class_of, dist, own_mean [r1]; cost[max_iter + 1].  Reads the done word back after every round and stops enqueuing
+   once the loop has stopped.  Synchronises.                                                                            */
+int kpop_kmedoids(kpop_refset *rs, uint32_t n_medoids, const uint32_t *init, uint32_t max_iter, uint32_t *medoid,
+                  uint32_t *class_of, double *dist, double *own_mean, uint32_t *class_rows, double *cost,
+                  uint32_t *n_iter, int *converged);
+/* bytes of d_work for kpop_dev_kmedoids (lib/Space.ml:182-205 over the set against itself, see the block above), for the
+   set's r1 at the time of the call: O(r1 + n_medoids + max_iter), no copy of a row; 0 for arguments the call refuses    */
+uint64_t kpop_dev_kmedoids_workspace_bytes(const kpop_refset *rs, uint32_t n_medoids, uint32_t max_iter);
+/* (lib/Space.ml:182-205; lib/Matrix.ml:243-250.)  Enqueues only, reads nothing back, allocates nothing: the worst case
+   of max_iter + 1 rounds, whose kernels return at once after the loop has stopped (the scans and the sort of such a
+   round run on unchanged data: O(r1) a round, no output altered).  d_init[n_medoids] TRUSTED to be distinct; d_medoid,
+   d_class_rows [n_medoids], d_class_of, d_dist, d_own_mean [r1], d_cost[max_iter + 1], each or NULL;
+   d_counts[2] = {n_iter, converged}.                                                                                    */
+int kpop_dev_kmedoids(kpop_refset *rs, uint32_t n_medoids, const uint32_t *d_init, uint32_t max_iter, void *d_work,
+                      uint32_t *d_medoid, uint32_t *d_class_of, double *d_dist, double *d_own_mean,
+                      uint32_t *d_class_rows, double *d_cost, uint32_t *d_counts, void *stream);
+/* unprepared convenience (lib/Matrix.ml:191-266 for the distances, m against itself): a temporary set over m, then
+   kpop_kmedoids                                                                                                        */
+int kpop_distance_kmedoids(const double *m, uint32_t rows, uint32_t n_dims, const double *metric, int kind, double p,
+                           int normalize, uint32_t n_medoids, const uint32_t *init, uint32_t max_iter, uint32_t *medoid,
+                           uint32_t *class_of, double *dist, double *own_mean, uint32_t *class_rows, double *cost,
+                           uint32_t *n_iter, int *converged);
+
 /* ------------------------------------------------- k-mer database (KPopCountDB)
  * the operations of lib/KMerDB.ml that touch every count.  A database is the reference's
  * `storage: I32BAVector.t array` (lib/KMerDB.ml:54-63): n_cols spectra ("columns"), each a vector of n_rows int32

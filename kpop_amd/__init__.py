@@ -19,7 +19,8 @@ from .api import (check, COSINE, DNA_DS, DNA_SS, PROTEIN, EUCLIDEAN, METRIC_FLAT
                   dev_dbscan_workspace_bytes, dev_dbscan, distance_dbscan, dev_core_distances_workspace_bytes, dev_core_distances,
                   dev_reachability_forest_workspace_bytes, dev_reachability_forest, distance_reachability_forest, reachability_cut,
                   Silhouette, dev_silhouette_workspace_bytes, dev_silhouette, distance_silhouette, silhouette_summary, dense_labels,
-                  FarthestFirst, dev_farthest_first_workspace_bytes, dev_farthest_first, distance_farthest_first)
+                  FarthestFirst, dev_farthest_first_workspace_bytes, dev_farthest_first, distance_farthest_first,
+                  KMedoids, dev_kmedoids_workspace_bytes, dev_kmedoids, distance_kmedoids)
 
 __all__ = ["init", "device_count", "count_reads", "Twister", "ca", "metric_compute", "distance_rowwise",
            "distance_summary", "embeddings", "splits_gaps", "summarize_distances", "parse_distance", "KPopError", "DNA_DS", "DNA_SS", "PROTEIN", "EUCLIDEAN", "COSINE",
@@ -36,4 +37,5 @@ __all__ = ["init", "device_count", "count_reads", "Twister", "ca", "metric_compu
            "dev_dbscan_workspace_bytes", "dev_dbscan", "distance_dbscan", "dev_core_distances_workspace_bytes", "dev_core_distances",
            "dev_reachability_forest_workspace_bytes", "dev_reachability_forest", "distance_reachability_forest", "reachability_cut",
            "Silhouette", "dev_silhouette_workspace_bytes", "dev_silhouette", "distance_silhouette", "silhouette_summary", "dense_labels",
-           "FarthestFirst", "dev_farthest_first_workspace_bytes", "dev_farthest_first", "distance_farthest_first"]
+           "FarthestFirst", "dev_farthest_first_workspace_bytes", "dev_farthest_first", "distance_farthest_first",
+           "KMedoids", "dev_kmedoids_workspace_bytes", "dev_kmedoids", "distance_kmedoids"]

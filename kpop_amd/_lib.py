@@ -226,6 +226,12 @@ SIGNATURES = {
     "kpop_dev_farthest_first": (C.c_int, [vp, C.c_uint32, C.c_double, vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp]),
     "kpop_distance_farthest_first": (C.c_int, [f64p, C.c_uint32, C.c_uint32, f64p, C.c_int, C.c_double, C.c_int, C.c_uint32, C.c_double, u32p, C.c_uint32, u32p,
                                                u32p, f64p, u32p, u32p, f64p, u32p]),
+    # k-medoids: clusters when a count is known (kmedoids.hip)
+    "kpop_kmedoids": (C.c_int, [vp, C.c_uint32, u32p, C.c_uint32, u32p, u32p, f64p, f64p, u32p, f64p, u32p, C.POINTER(C.c_int)]),
+    "kpop_dev_kmedoids_workspace_bytes": (C.c_uint64, [vp, C.c_uint32, C.c_uint32]),
+    "kpop_dev_kmedoids": (C.c_int, [vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "kpop_distance_kmedoids": (C.c_int, [f64p, C.c_uint32, C.c_uint32, f64p, C.c_int, C.c_double, C.c_int, C.c_uint32, u32p, C.c_uint32, u32p, u32p, f64p, f64p,
+                                         u32p, f64p, u32p, C.POINTER(C.c_int)]),
 }
 
 

@@ -920,6 +920,26 @@ class RefSet:
                                               *_farthest_first_pointers(res), C.byref(passes)))
         return _farthest_first_cut(res, r1, int(n.value), int(passes.value))
 
+    def kmedoids(self, medoids, max_iter=100):
+        """Alternating k-medoids (Voronoi iteration) on the set -> KMedoids(medoid u32 [k], class_of u32 [r1], dist f64 [r1], own_mean f64
+        [r1], class_rows u32 [k], cost f64 [n_iter + 1], n_iter, converged).  medoids: the k distinct rows to start from -- an index array;
+        a FarthestFirst tuple, whose picks are used; or an int k, meaning self.farthest_first(max_picks=k).pick: the k-centre seeding, a
+        2-approximation of the best k centres and the same rows on every run.  Assignment: a medoid has its own position as class and dist
+        +0, every other row the nearest medoid (ties to the earlier position; a row with no distance that is a number is left out: NO_CLASS,
+        +inf, NaN).  Update: a class's new medoid is its member with the least own_mean (ties to the smaller row), own_mean being
+        silhouette's for class_of, bit for bit.  The rounds stop when no medoid moves (converged) or after max_iter re-assignments;
+        max_iter=0 is the plain assignment to the given rows.  What is returned is consistent: class_of / dist are the assignment to
+        medoid, own_mean and class_rows are of that labelling; cost[t] is the sum of dist after t re-assignments.  medoids=an earlier run's
+        medoid goes on where that run stopped -- also after append.  The same bits on every run (kpop_kmedoids, include/kpop_hip.h)."""
+        r1 = self.info()["r1"]
+        if isinstance(medoids, (int, np.integer)) and not isinstance(medoids, bool):
+            medoids = self.farthest_first(max_picks=int(medoids)).pick
+        init, max_iter = _kmedoids_arguments(medoids, max_iter)
+        res = _kmedoids_result(r1, len(init), max_iter)
+        n, conv = C.c_uint32(), C.c_int()
+        check(_lib.load().kpop_kmedoids(self._h, len(init), _p(_nz(init, np.uint32), C.c_uint32), max_iter, *_kmedoids_pointers(res), C.byref(n), C.byref(conv)))
+        return _kmedoids_cut(res, r1, len(init), int(n.value), int(conv.value))
+
     def spanning_forest(self, max_distance=float("inf")):
         """The single-linkage tree of the set: the minimum spanning forest of the graph that joins rows i < j iff d(j, i) <= max_distance,
         under the order (d, i, j) -> (edge_i u32, edge_j u32, edge_dist f64, labels u32 [r1]).  The order is strict, so the forest is
@@ -1655,6 +1675,66 @@ def distance_farthest_first(m, metric, kind=EUCLIDEAN, p=2.0, normalize=True, ma
                                                    float(p), 1 if normalize else 0, max_picks, float(cover_radius), _p(_nz(seeds, np.uint32), C.c_uint32),
                                                    len(seeds), C.byref(n), *_farthest_first_pointers(res), C.byref(passes)))
     return _farthest_first_cut(res, rows, int(n.value), int(passes.value))
+
+
+KMedoids = collections.namedtuple("KMedoids", "medoid class_of dist own_mean class_rows cost n_iter converged")
+
+
+def _kmedoids_arguments(medoids, max_iter):
+    """medoids: row indices, or a FarthestFirst: its picks"""
+    if isinstance(medoids, FarthestFirst):
+        medoids = medoids.pick
+    medoids = np.asarray(medoids)
+    if medoids.ndim != 1 or (len(medoids) and (medoids.min() < 0 or medoids.max() > 0xFFFFFFFF)):
+        raise ValueError("medoids: row indices")
+    max_iter = int(max_iter)
+    if not 0 <= max_iter < 0xFFFFFFFF:
+        raise ValueError("max_iter: a count of rounds")
+    return _c(medoids, np.uint32), max_iter
+
+
+def _kmedoids_result(rows, k, max_iter):
+    n, k = max(rows, 1), max(min(k, 65536), 1)  # (the library refuses more medoids before it writes)
+    return (np.zeros(k, dtype=np.uint32), np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.float64), np.zeros(k, dtype=np.uint32),
+            np.zeros(max_iter + 1, dtype=np.float64))
+
+
+def _kmedoids_pointers(res):
+    return [_p(x, C.c_double if x.dtype == np.float64 else C.c_uint32) for x in res]
+
+
+def _kmedoids_cut(res, rows, k, n_iter, converged):
+    return KMedoids(res[0][:k], res[1][:rows], res[2][:rows], res[3][:rows], res[4][:k], res[5][:n_iter + 1], n_iter, bool(converged))
+
+
+def dev_kmedoids_workspace_bytes(rs, n_medoids, max_iter):
+    """the size of d_work for dev_kmedoids, for the set's r1 at the time of the call; 0 for arguments the call refuses"""
+    return int(_lib.load().kpop_dev_kmedoids_workspace_bytes(rs.handle, int(n_medoids), int(max_iter)))
+
+
+def dev_kmedoids(rs, n_medoids, d_init, max_iter, d_work, d_counts, d_medoid=None, d_class_of=None, d_dist=None, d_own_mean=None, d_class_rows=None, d_cost=None,
+                 stream=0):
+    """enqueue only, max_iter + 1 rounds: d_counts[2] (u32: n_iter, converged); d_medoid / d_class_rows (u32 [n_medoids]), d_class_of (u32 [r1]),
+    d_dist / d_own_mean (f64 [r1]), d_cost (f64 [max_iter + 1], NaN past n_iter), each or None; d_init (u32 [n_medoids]) is trusted to hold
+    distinct rows"""
+    check(_lib.load().kpop_dev_kmedoids(rs.handle, int(n_medoids), d_init, int(max_iter), d_work, d_medoid, d_class_of, d_dist, d_own_mean, d_class_rows, d_cost,
+                                        d_counts, stream))
+
+
+def distance_kmedoids(m, metric, medoids, kind=EUCLIDEAN, p=2.0, normalize=True, max_iter=100):
+    """RefSet(m, ...).kmedoids(medoids, max_iter) without keeping the set, medoids an index array or a FarthestFirst: one call of
+    kpop_distance_kmedoids -> KMedoids"""
+    m, metric = _c(m, np.float64), _c(metric, np.float64)
+    if m.ndim != 2 or m.shape[1] != len(metric):
+        raise ValueError("Incompatible_geometries")  # lib/Matrix.ml:193-194
+    rows = m.shape[0]
+    init, max_iter = _kmedoids_arguments(medoids, max_iter)
+    res = _kmedoids_result(rows, len(init), max_iter)
+    n, conv = C.c_uint32(), C.c_int()
+    check(_lib.load().kpop_distance_kmedoids(_p(_nz(m, np.float64), C.c_double), rows, len(metric), _p(_nz(metric, np.float64), C.c_double), int(kind), float(p),
+                                             1 if normalize else 0, len(init), _p(_nz(init, np.uint32), C.c_uint32), max_iter, *_kmedoids_pointers(res),
+                                             C.byref(n), C.byref(conv)))
+    return _kmedoids_cut(res, rows, len(init), int(n.value), int(conv.value))
 
 
 def dense_labels(labels):

@@ -72,6 +72,24 @@ struct PairStage {
     }
   }
 
+  // load_indexed, the rows gathered as well: row j0 + k of the tile is row jdx[j0 + k] of b, held below b_rows
+  __device__ __forceinline__ void load_indexed_both(const double *__restrict__ a, uint32_t a_rows, const uint32_t *__restrict__ idx, uint32_t i0, uint32_t i1,
+                                                    const double *__restrict__ b, uint32_t b_rows, const uint32_t *__restrict__ jdx, uint32_t j0, uint32_t j1,
+                                                    uint32_t n_dims, uint32_t c0, uint32_t d_end) {
+    const uint32_t sc = threadIdx.x % kPairDC, rbase = threadIdx.x / kPairDC;
+    const bool cok = c0 + sc < d_end;
+#pragma unroll
+    for (int q = 0; q < NA; ++q) {
+      const uint32_t row = rbase + q * 16;
+      ra[q] = (cok && i0 + row < i1) ? a[(uint64_t)min(idx[i0 + row], a_rows - 1) * n_dims + c0 + sc] : 0.0;
+    }
+#pragma unroll
+    for (int q = 0; q < NB; ++q) {
+      const uint32_t row = rbase + q * 16;
+      rb[q] = (cok && j0 + row < j1) ? b[(uint64_t)min(jdx[j0 + row], b_rows - 1) * n_dims + c0 + sc] : 0.0;
+    }
+  }
+
   // registers -> LDS, and the step's 16 metric values
   __device__ __forceinline__ void store(double (*As)[MAXW + 2], double (*Bs)[MAXTJ + 2], double *s_metric, const double *__restrict__ metric, uint32_t c0,
                                         uint32_t d_end) const {

@@ -10,11 +10,12 @@
 //   medoid -- the member least under (own_mean with -0 as +0, row index) among those whose own_mean is a number -- and that mean.
 //
 // Neither the r1 x r1 matrix nor an r1 x n_classes table is formed, nothing is read back, nothing synchronises:
-//   silhouette_keys_kernel    a row's sort key (its class; a row left out: n_classes, behind every class) and the class sizes
-//   exclusive_scan (scan.h), twice: where a class starts in the grouped order, and its first column tile -- a class's rows are cut
-//                             into column tiles of at most w positions, so every column tile holds ONE class; at most r1 / w + n_classes
-//   radix_sort_pairs_u64      (radix_sort.h, 16-bit keys) the row indices grouped by class, stable: ascending inside a class
-//   silhouette_tiles_kernel   the column tiles: positions, class, whether the class ends there
+//   class_tiles_group         (class_tiles.h, shared with kmedoids.hip) the rows grouped by class:
+//     silhouette_keys_kernel    a row's sort key (its class; a row left out: n_classes, behind every class) and the class sizes
+//     exclusive_scan (scan.h), twice: where a class starts in the grouped order, and its first column tile -- a class's rows are cut
+//                               into column tiles of at most w positions, so every column tile holds ONE class; at most r1 / w + n_classes
+//     radix_sort_pairs_u64      (radix_sort.h, 16-bit keys) the row indices grouped by class, stable: ascending inside a class
+//     silhouette_tiles_kernel   the column tiles: positions, class, whether the class ends there
 //   silhouette_pass_kernel    a workgroup owns a row tile j0 .. j1 in natural order and walks the column tiles in order, the columns
 //                             gathered through the grouped order (PairStage::load_indexed), both tile shapes of self_shape.  After a
 //                             tile a thread adds its four columns' distances onto its running sum of the row (the row itself and the
@@ -34,45 +35,23 @@
 // row changes every mean.
 #include <algorithm>
 
+#include "class_tiles.h"
 #include "common.h"
 #include "distance_routes.h"
-#include "radix_sort.h"
 #include "refset_call.h"
-#include "scan.h"
 #include "self_tile.h"
 
 namespace kpop {
 
-constexpr int kSilMaxW = 64, kSilMaxTJ = 256;
-constexpr uint32_t kSilNone = 0xFFFFFFFFu;    // KPOP_NO_CLASS
-constexpr uint32_t kSilMaxClasses = 65535u;  // (kpop_knn_vote's limit: a class and "left out" are a 16-bit sort key)
-constexpr uint32_t kSilLast = 1u << 31;       // SilTile::c: the class ends with this tile
-
-__device__ __forceinline__ double sil_nan() { return __longlong_as_double(0x7FF8000000000000ll); }
-
-// a lane's share of a row's sum, for reduce_row_lanes (self_tile.h): x + y is what both partners of an exchange compute
-struct LaneSum {
-  double v;
-};
-__device__ __forceinline__ LaneSum lane_xor(LaneSum s, uint32_t o) { return LaneSum{__shfl_xor(s.v, (int)o, 64)}; }
-
-// a column tile: positions i0 .. i1 of the grouped order, all of class c (| kSilLast), which has n rows
-struct SilTile {
-  uint32_t i0, i1, c, n;
-};
-
-// cnt[n_classes + 1]: the rows of a class, [n_classes] the rows left out; start[n_classes + 1]: where a class begins in the grouped
-// order; first_tile[n_classes + 1]: its first column tile, [n_classes] the number of tiles; tiles[max_tiles]; keys / vals: the sort's
-// two buffers each; own [r1], other, ocls [n_seg][r1]: what the pass leaves for a row and a segment; med_k, med_i [n_classes]: the
-// medoid's two minima, filled with ones by one memset
+// g: the grouping (class_tiles.h); own [r1], other, ocls [n_seg][r1]: what the pass leaves for a row and a segment; med_k, med_i
+// [n_classes]: the medoid's two minima, filled with ones by one memset
 struct SilWork {
-  uint32_t *cnt, *start, *first_tile, *vals_a, *vals_b, *ocls, *med_i;
-  uint64_t *sums, *keys_a, *keys_b, *med_k;
-  SilTile *tiles;
+  ClassTiles g;
+  uint32_t *ocls, *med_i;
+  uint64_t *med_k;
   double *own, *other;
-  void *radix;
   uint64_t fill_bytes, bytes;
-  uint32_t max_tiles, n_seg;
+  uint32_t n_seg;
 };
 
 // the column segments of a row tile: enough workgroups for a short set (2,048 and more where the set has the rows), a function of r1
@@ -83,21 +62,10 @@ static uint32_t silhouette_segments(uint32_t r1) {
 
 static SilWork silhouette_carve(void *base, uint32_t r1, uint32_t n_classes) {
   const uint64_t n = std::max(r1, 1u), nc = (uint64_t)n_classes + 1;
-  const SelfShape s = self_shape(r1);
   Carver c(base);
   SilWork f;
-  f.max_tiles = (uint32_t)(n / s.w + nc);
+  f.g = class_tiles_carve(c, r1, n_classes);
   f.n_seg = silhouette_segments(r1);
-  f.cnt = c.take<uint32_t>(nc * 4);
-  f.start = c.take<uint32_t>(nc * 4);
-  f.first_tile = c.take<uint32_t>(nc * 4);
-  f.sums = c.take<uint64_t>((scan_blocks(nc) + 1) * 8);
-  f.keys_a = c.take<uint64_t>(n * 8);
-  f.keys_b = c.take<uint64_t>(n * 8);
-  f.vals_a = c.take<uint32_t>(n * 4);
-  f.vals_b = c.take<uint32_t>(n * 4);
-  f.radix = c.take<char>(radix_scratch_bytes(n));
-  f.tiles = c.take<SilTile>((uint64_t)f.max_tiles * sizeof(SilTile));
   f.own = c.take<double>(n * 8);
   f.other = c.take<double>(n * f.n_seg * 8);
   f.ocls = c.take<uint32_t>(n * f.n_seg * 4);
@@ -107,56 +75,6 @@ static SilWork silhouette_carve(void *base, uint32_t r1, uint32_t n_classes) {
   f.fill_bytes = c.off - before;
   f.bytes = c.off;
   return f;
-}
-
-// the table is trusted and guarded: a class beyond n_classes counts as left out
-__global__ __launch_bounds__(256) void silhouette_keys_kernel(const uint32_t *__restrict__ class_of, uint32_t r1, uint32_t n_classes, uint64_t *__restrict__ keys,
-                                                              uint32_t *__restrict__ vals, uint32_t *__restrict__ cnt) {
-  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < r1; i += (uint64_t)gridDim.x * 256) {
-    const uint32_t c = min(class_of[i], n_classes);
-    keys[i] = c;
-    vals[i] = (uint32_t)i;
-    atomicAdd(cnt + c, 1u);
-  }
-}
-
-struct SilRowsIn {
-  const uint32_t *cnt;
-  __device__ uint32_t operator()(uint64_t i) const { return cnt[i]; }
-};
-struct SilTilesIn {  // (the rows left out get no tile)
-  const uint32_t *cnt;
-  uint32_t n_classes, w;
-  __device__ uint32_t operator()(uint64_t i) const { return i < n_classes ? (cnt[i] + w - 1) / w : 0u; }
-};
-struct SilPrefixOut {
-  uint32_t *out;
-  __device__ void operator()(uint64_t i, uint64_t prefix, uint32_t) const { out[i] = (uint32_t)prefix; }
-};
-
-// a block a class at a time, a thread a tile of it
-__global__ __launch_bounds__(256) void silhouette_tiles_kernel(const uint32_t *__restrict__ cnt, const uint32_t *__restrict__ start,
-                                                               const uint32_t *__restrict__ first_tile, uint32_t n_classes, uint32_t w, uint32_t max_tiles,
-                                                               SilTile *__restrict__ tiles) {
-  for (uint32_t c = blockIdx.x; c < n_classes; c += gridDim.x) {
-    const uint32_t n = cnt[c], s = start[c], t0 = first_tile[c], nt = (n + w - 1) / w;
-    for (uint32_t k = threadIdx.x; k < nt; k += 256) {
-      const uint32_t i0 = s + k * w, i1 = min(s + n, i0 + w);
-      if (t0 + k < max_tiles) tiles[t0 + k] = SilTile{i0, i1, c | (i1 == s + n ? kSilLast : 0u), n};
-    }
-  }
-}
-
-// a tile as the pass reads it, held to the set: a table that was never written walks nobody out of the grouped order
-__device__ __forceinline__ SilTile silhouette_tile(const SilTile *__restrict__ tiles, uint32_t t, uint32_t n_tiles, uint32_t r1, uint32_t w) {
-  SilTile x{0u, 0u, kSilLast, 1u};
-  if (t < n_tiles) {
-    x = tiles[t];
-    x.i0 = min(x.i0, r1);
-    x.i1 = min(min(x.i1, r1), x.i0 + w);
-    x.i1 = max(x.i1, x.i0);
-  }
-  return x;
 }
 
 // a: the set's rows as the chain reads them (divided by their norms when the set normalises), both operands.  Row tile blockIdx.x:
@@ -336,39 +254,32 @@ static int silhouette_dev(kpop_refset *rs, const uint32_t *d_class_of, uint32_t 
   const uint32_t r1 = rs->r1, D = rs->n_dims;
   if (r1 && !d_class_of) KPOP_FAIL(KPOP_ERR_INVALID, "%s: null class_of", who);
   const SelfShape s = self_shape(r1);
-  const SilWork f = silhouette_carve(d_work, r1, n_classes);
-  KPOP_HIP(hipMemsetAsync(f.cnt, 0, ((uint64_t)n_classes + 1) * 4, st));
+  SilWork f = silhouette_carve(d_work, r1, n_classes);
+  if (!r1) KPOP_HIP(hipMemsetAsync(f.g.cnt, 0, ((uint64_t)n_classes + 1) * 4, st));
   KPOP_HIP(hipMemsetAsync(f.med_k, 0xFF, f.fill_bytes, st));
   const dim3 classes_grid(div_up(n_classes, 256));
   if (r1) {
     const double *a = rs->rows;
     KPOP_TRY(refset_chain_rows(rs, st, &a));
     const dim3 rows_grid(std::min(div_up(r1, 256), 4096u));
-    silhouette_keys_kernel<<<rows_grid, dim3(256), 0, st>>>(d_class_of, r1, n_classes, f.keys_a, f.vals_a, f.cnt);
-    KPOP_LAUNCH_CHECK();
-    KPOP_TRY(exclusive_scan(SilRowsIn{f.cnt}, SilPrefixOut{f.start}, (uint64_t)n_classes + 1, f.sums, st));
-    KPOP_TRY(exclusive_scan(SilTilesIn{f.cnt, n_classes, s.w}, SilPrefixOut{f.first_tile}, (uint64_t)n_classes + 1, f.sums, st));
-    uint64_t *keys = nullptr;
-    uint32_t *perm = nullptr;
-    KPOP_TRY(radix_sort_pairs_u64(f.keys_a, f.keys_b, f.vals_a, f.vals_b, r1, 16, f.radix, st, &keys, &perm));
-    silhouette_tiles_kernel<<<dim3(std::min(n_classes, 4096u)), dim3(256), 0, st>>>(f.cnt, f.start, f.first_tile, n_classes, s.w, f.max_tiles, f.tiles);
-    KPOP_LAUNCH_CHECK();
+    KPOP_TRY(class_tiles_group(f.g, d_class_of, r1, n_classes, nullptr, st));
+    const uint32_t *perm = f.g.perm;
     const dim3 grid(div_up(r1, s.TJ), f.n_seg);
     KPOP_TRY(by_kind(rs->kind, [&](auto K) -> int {
       by_shape_rows(s, [&](auto TY) {
         silhouette_pass_kernel<decltype(K)::value, decltype(TY)::value><<<grid, dim3(256), 0, st>>>(a, s.w, r1, D, rs->metric, rs->p, s.n_cg, s.n_rg, d_class_of, n_classes,
-                                                                                                   perm, f.tiles, f.first_tile, f.max_tiles, f.own, f.other, f.ocls);
+                                                                                                   perm, f.g.tiles, f.g.first_tile, f.g.max_tiles, f.own, f.other, f.ocls);
       });
       KPOP_LAUNCH_CHECK();
       return 0;
     }));
-    silhouette_rows_kernel<<<rows_grid, dim3(256), 0, st>>>(d_class_of, r1, n_classes, f.cnt, f.own, f.other, f.ocls, f.n_seg, d_own_mean, d_other_mean, d_other_class, d_silhouette,
+    silhouette_rows_kernel<<<rows_grid, dim3(256), 0, st>>>(d_class_of, r1, n_classes, f.g.cnt, f.own, f.other, f.ocls, f.n_seg, d_own_mean, d_other_mean, d_other_class, d_silhouette,
                                                             f.med_k);
     KPOP_LAUNCH_CHECK();
     silhouette_medoid_kernel<<<rows_grid, dim3(256), 0, st>>>(d_class_of, r1, n_classes, f.own, f.med_k, f.med_i);
     KPOP_LAUNCH_CHECK();
   }
-  silhouette_classes_kernel<<<classes_grid, dim3(256), 0, st>>>(n_classes, r1, f.cnt, f.med_i, f.own, d_class_rows, d_medoid, d_medoid_mean);
+  silhouette_classes_kernel<<<classes_grid, dim3(256), 0, st>>>(n_classes, r1, f.g.cnt, f.med_i, f.own, d_class_rows, d_medoid, d_medoid_mean);
   KPOP_LAUNCH_CHECK();
   return KPOP_OK;
 }
