@@ -38,6 +38,18 @@ def _nz(a, dt):
     return a if a.size else np.zeros(1, dtype=dt)
 
 
+_CTYPE = {np.dtype(np.float64): C.c_double, np.dtype(np.uint32): C.c_uint32, np.dtype(np.uint64): C.c_uint64}
+
+
+def _ptr(a):
+    """the array as the typed pointer the C ABI takes (an empty one: a valid pointer all the same)"""
+    return _p(_nz(a, a.dtype), _CTYPE[a.dtype])
+
+
+def _pointers(res):
+    return [_ptr(x) for x in res]
+
+
 def init(device=0):
     check(_lib.load().kpop_init(int(device)))
 
@@ -679,6 +691,33 @@ def metric_compute(inertia, kind=METRIC_POWERS, power_int=1.0, threshold=1.0, po
 
 
 # --------------------------------------------------------------- distance
+def _set_geometry(m, metric, kind, p, normalize):
+    """a first operand and its distance as a kpop_distance_* call takes them -> (the seven leading arguments m, rows, n_dims, metric, kind,
+    p, normalize; rows)"""
+    m, metric = _c(m, np.float64), _c(metric, np.float64)
+    if m.ndim != 2 or m.shape[1] != len(metric):
+        raise ValueError("Incompatible_geometries")  # lib/Matrix.ml:193-194
+    return [_ptr(m), m.shape[0], len(metric), _ptr(metric), int(kind), float(p), 1 if normalize else 0], m.shape[0]
+
+
+def _query_rows(m2, n_dims):
+    """a second operand against n_dims dimensions"""
+    m2 = _c(m2, np.float64)
+    if m2.ndim != 2 or m2.shape[1] != n_dims:
+        raise ValueError("Incompatible_geometries")  # lib/Matrix.ml:193-194
+    return m2
+
+
+def _summary_call(fn, lead, r1, r2, keep_at_most, max_neighbours):
+    if max_neighbours is None:
+        max_neighbours = r1 if not keep_at_most else min(r1, max(keep_at_most * 4, 8))
+    max_neighbours = max(int(max_neighbours), 1)
+    res = (np.zeros((r2, 4), dtype=np.float64), np.zeros(r2, dtype=np.uint32), np.zeros((r2, max_neighbours), dtype=np.uint32),
+           np.zeros((r2, max_neighbours), dtype=np.float64), np.zeros((r2, max_neighbours), dtype=np.float64))
+    check(fn(*lead, int(keep_at_most or 0), max_neighbours, *_pointers(res)))
+    return res
+
+
 def distance_rowwise(m1, m2, metric, kind=EUCLIDEAN, p=2.0, normalize=True):
     """-> r2 x r1 matrix, rows = m2 (the file operand), cols = m1 (the register); lib/Matrix.ml:253,264-266."""
     m1 = _c(m1, np.float64)
@@ -689,10 +728,7 @@ def distance_rowwise(m1, m2, metric, kind=EUCLIDEAN, p=2.0, normalize=True):
     r1, d = m1.shape
     r2 = m2.shape[0]
     out = np.zeros((r2, r1), dtype=np.float64)
-    check(_lib.load().kpop_distance_rowwise(_p(_nz(m1, np.float64), C.c_double), r1,
-                                            _p(_nz(m2, np.float64), C.c_double), r2, d,
-                                            _p(metric, C.c_double), int(kind), float(p), 1 if normalize else 0,
-                                            _p(_nz(out, np.float64), C.c_double)))
+    check(_lib.load().kpop_distance_rowwise(_ptr(m1), r1, _ptr(m2), r2, d, _ptr(metric), int(kind), float(p), 1 if normalize else 0, _ptr(out)))
     return out
 
 
@@ -706,22 +742,8 @@ def distance_summary(m1, m2, metric, kind=EUCLIDEAN, p=2.0, normalize=True, keep
         raise ValueError("Incompatible_geometries")  # lib/Matrix.ml:698-699
     r1, d = m1.shape
     r2 = m2.shape[0]
-    if max_neighbours is None:
-        max_neighbours = r1 if not keep_at_most else min(r1, max(keep_at_most * 4, 8))
-    max_neighbours = max(int(max_neighbours), 1)
-    stats = np.zeros((r2, 4), dtype=np.float64)
-    n = np.zeros(r2, dtype=np.uint32)
-    idx = np.zeros((r2, max_neighbours), dtype=np.uint32)
-    dist = np.zeros((r2, max_neighbours), dtype=np.float64)
-    z = np.zeros((r2, max_neighbours), dtype=np.float64)
-    check(_lib.load().kpop_distance_summary(_p(_nz(m1, np.float64), C.c_double), r1,
-                                            _p(_nz(m2, np.float64), C.c_double), r2, d,
-                                            _p(metric, C.c_double), int(kind), float(p), 1 if normalize else 0,
-                                            int(keep_at_most or 0), max_neighbours,
-                                            _p(_nz(stats, np.float64), C.c_double), _p(_nz(n, np.uint32), C.c_uint32),
-                                            _p(_nz(idx, np.uint32), C.c_uint32), _p(_nz(dist, np.float64), C.c_double),
-                                            _p(_nz(z, np.float64), C.c_double)))
-    return stats, n, idx, dist, z
+    return _summary_call(_lib.load().kpop_distance_summary, [_ptr(m1), r1, _ptr(m2), r2, d, _p(metric, C.c_double), int(kind), float(p), 1 if normalize else 0],
+                         r1, r2, keep_at_most, max_neighbours)
 
 
 class RefSet:
@@ -773,59 +795,33 @@ class RefSet:
 
     def distance_rowwise(self, m2):
         """-> r2 x r1 matrix, as distance_rowwise(m1, m2, ...)"""
-        m2 = _c(m2, np.float64)
         i = self.info()
-        if m2.ndim != 2 or m2.shape[1] != i["n_dims"]:
-            raise ValueError("Incompatible_geometries")
+        m2 = _query_rows(m2, i["n_dims"])
         out = np.zeros((m2.shape[0], i["r1"]), dtype=np.float64)
-        check(_lib.load().kpop_refset_distance_rowwise(self._h, _p(_nz(m2, np.float64), C.c_double), m2.shape[0], _p(_nz(out, np.float64), C.c_double)))
+        check(_lib.load().kpop_refset_distance_rowwise(self._h, _ptr(m2), m2.shape[0], _ptr(out)))
         return out
 
     def distance_summary(self, m2, keep_at_most=2, max_neighbours=None):
         """-> stats, n, idx, dist, z, as distance_summary(m1, m2, ...)"""
-        m2 = _c(m2, np.float64)
         i = self.info()
-        if m2.ndim != 2 or m2.shape[1] != i["n_dims"]:
-            raise ValueError("Incompatible_geometries")
-        r1, r2 = i["r1"], m2.shape[0]
-        if max_neighbours is None:
-            max_neighbours = r1 if not keep_at_most else min(r1, max(keep_at_most * 4, 8))
-        max_neighbours = max(int(max_neighbours), 1)
-        stats = np.zeros((r2, 4), dtype=np.float64)
-        n = np.zeros(r2, dtype=np.uint32)
-        idx = np.zeros((r2, max_neighbours), dtype=np.uint32)
-        dist = np.zeros((r2, max_neighbours), dtype=np.float64)
-        z = np.zeros((r2, max_neighbours), dtype=np.float64)
-        check(_lib.load().kpop_refset_distance_summary(self._h, _p(_nz(m2, np.float64), C.c_double), r2, int(keep_at_most or 0), max_neighbours,
-                                                       _p(_nz(stats, np.float64), C.c_double), _p(_nz(n, np.uint32), C.c_uint32),
-                                                       _p(_nz(idx, np.uint32), C.c_uint32), _p(_nz(dist, np.float64), C.c_double),
-                                                       _p(_nz(z, np.float64), C.c_double)))
-        return stats, n, idx, dist, z
+        m2 = _query_rows(m2, i["n_dims"])
+        return _summary_call(_lib.load().kpop_refset_distance_summary, [self._h, _ptr(m2), m2.shape[0]], i["r1"], m2.shape[0], keep_at_most, max_neighbours)
 
     def within(self, m2, max_distance, capacity=None):
         """Every row of the set within max_distance of each row of m2 -> (offsets[r2 + 1] u64, idx u32, dist f64), CSR; a row's list
         ascending by (distance, index): the neighbour list of distance_summary (lib/Matrix.ml:632-690) cut at a distance instead of a
         count.  capacity=None: one call counts, a second fills arrays of exactly that size; a capacity that turns out too small raises
         KPopError with code ERR_CAPACITY (kpop_neighbours_within, include/kpop_hip.h)."""
-        m2 = _c(m2, np.float64)
-        i = self.info()
-        if m2.ndim != 2 or m2.shape[1] != i["n_dims"]:
-            raise ValueError("Incompatible_geometries")
+        m2 = _query_rows(m2, self.info()["n_dims"])
         r2 = m2.shape[0]
-        lib = _lib.load()
-        offsets = np.zeros(r2 + 1, dtype=np.uint64)
-        pm2, poff = _p(_nz(m2, np.float64), C.c_double), _p(offsets, C.c_uint64)
+        fn = _lib.load().kpop_neighbours_within
         if capacity is None:
-            check(lib.kpop_neighbours_within(self._h, pm2, r2, float(max_distance), 0, poff, None, None))
+            offsets = np.zeros(r2 + 1, dtype=np.uint64)
+            check(fn(self._h, _ptr(m2), r2, float(max_distance), 0, _ptr(offsets), None, None))
             capacity = int(offsets[r2])
             if capacity == 0:  # (nothing to fill: the offsets are all there is)
                 return offsets, np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.float64)
-        capacity = int(capacity)
-        idx = np.zeros(max(capacity, 1), dtype=np.uint32)
-        dist = np.zeros(max(capacity, 1), dtype=np.float64)
-        check(lib.kpop_neighbours_within(self._h, pm2, r2, float(max_distance), capacity, poff, _p(idx, C.c_uint32), _p(dist, C.c_double)))
-        total = int(offsets[r2])
-        return offsets, idx[:total], dist[:total]
+        return _within_call(fn, [self._h, _ptr(m2), r2, float(max_distance)], r2, capacity)
 
     def clusters(self, max_distance, known=None):
         """The connected components of the graph that joins rows i < j iff d(j, i) <= max_distance -> (labels u32 [r1], n_clusters):
@@ -841,9 +837,7 @@ class RefSet:
                 raise ValueError("known: the labels of the first rows of the set, at most %d" % r1)
             known_rows = len(known)
             labels[:known_rows] = known
-        n = C.c_uint32()
-        check(_lib.load().kpop_clusters_within(self._h, float(max_distance), known_rows, _p(labels, C.c_uint32), C.byref(n)))
-        return labels[:r1], int(n.value)
+        return _clusters_call(_lib.load().kpop_clusters_within, [self._h, float(max_distance), known_rows], r1, labels)
 
     def representatives(self, max_distance, known=None):
         """The greedy cover of the set in row order -> (rep_of u32 [r1], rep_dist f64 [r1], n_reps): row i is a representative iff no
@@ -867,9 +861,7 @@ class RefSet:
             known_rows = len(known)
             rep_of[:known_rows] = known
             rep_dist[:known_rows] = np.nan if known_dist is None else known_dist
-        n = C.c_uint32()
-        check(_lib.load().kpop_representatives_within(self._h, float(max_distance), known_rows, _p(rep_of, C.c_uint32), _p(rep_dist, C.c_double), C.byref(n)))
-        return rep_of[:r1], rep_dist[:r1], int(n.value)
+        return _representatives_call(_lib.load().kpop_representatives_within, [self._h, float(max_distance), known_rows], r1, rep_of, rep_dist)
 
     def dbscan(self, eps, min_pts):
         """DBSCAN of the set -> (labels u32 [r1], core_of u32 [r1], degree u32 [r1], counts u32 [3]).  degree[i] = 1 + the rows within
@@ -879,12 +871,7 @@ class RefSet:
         nothing; every other row is noise: labels[i] = core_of[i] = NOISE.  counts: the clusters, the core rows, the noise rows.  The
         same bits on every run.  No earlier result is a valid start: after append the call is made again in full (kpop_dbscan,
         include/kpop_hip.h)."""
-        r1 = self.info()["r1"]
-        labels, core_of, degree = (np.zeros(max(r1, 1), dtype=np.uint32) for _ in range(3))
-        counts = np.zeros(3, dtype=np.uint32)
-        check(_lib.load().kpop_dbscan(self._h, float(eps), _min_pts(min_pts), _p(labels, C.c_uint32), _p(core_of, C.c_uint32), _p(degree, C.c_uint32),
-                                      _p(counts, C.c_uint32)))
-        return labels[:r1], core_of[:r1], degree[:r1], counts
+        return _dbscan_call(_lib.load().kpop_dbscan, [self._h, float(eps), _min_pts(min_pts)], self.info()["r1"])
 
     def silhouette(self, class_of, n_classes=None):
         """The silhouette and the medoids of the set under a labelling -> Silhouette(own_mean f64 [r1], other_mean f64 [r1], other_class
@@ -895,11 +882,7 @@ class RefSet:
         the member of a class with the least own_mean (ties to the smaller row), medoid_mean that mean.  The same bits on every run and
         under any renumbering of the classes.  n_classes None: one more than the largest class.  No earlier result is a valid start:
         after append the call is made again in full (kpop_silhouette, include/kpop_hip.h)."""
-        r1 = self.info()["r1"]
-        class_of, n_classes = _left_out_classes(class_of, r1, n_classes)
-        res = _silhouette_result(r1, n_classes)
-        check(_lib.load().kpop_silhouette(self._h, _p(_nz(class_of, np.uint32), C.c_uint32), n_classes, *_silhouette_pointers(res)))
-        return _silhouette_cut(res, r1, n_classes)
+        return _silhouette_call(_lib.load().kpop_silhouette, [self._h], self.info()["r1"], class_of, n_classes)
 
     def farthest_first(self, max_picks=None, cover_radius=-1.0, seeds=None):
         """The farthest-first traversal of the set -> FarthestFirst(pick u32 [n], pick_radius f64 [n], pick_parent u32 [n], rep_of u32 [r1],
@@ -912,13 +895,7 @@ class RefSet:
         of the picks is a cover of the set at the radius written beside the next pick; seeds=pick[:k] of an earlier run, or that run's
         whole tuple, reproduces it and goes on -- also after append.  The same bits on every run; n_passes is a fact about the run
         (kpop_farthest_first, include/kpop_hip.h)."""
-        r1 = self.info()["r1"]
-        max_picks, seeds = _farthest_first_arguments(r1, max_picks, seeds)
-        res = _farthest_first_result(r1, max_picks)
-        n, passes = C.c_uint32(), C.c_uint32()
-        check(_lib.load().kpop_farthest_first(self._h, max_picks, float(cover_radius), _p(_nz(seeds, np.uint32), C.c_uint32), len(seeds), C.byref(n),
-                                              *_farthest_first_pointers(res), C.byref(passes)))
-        return _farthest_first_cut(res, r1, int(n.value), int(passes.value))
+        return _farthest_first_call(_lib.load().kpop_farthest_first, [self._h], self.info()["r1"], max_picks, cover_radius, seeds)
 
     def kmedoids(self, medoids, max_iter=100):
         """Alternating k-medoids (Voronoi iteration) on the set -> KMedoids(medoid u32 [k], class_of u32 [r1], dist f64 [r1], own_mean f64
@@ -931,30 +908,16 @@ class RefSet:
         max_iter=0 is the plain assignment to the given rows.  What is returned is consistent: class_of / dist are the assignment to
         medoid, own_mean and class_rows are of that labelling; cost[t] is the sum of dist after t re-assignments.  medoids=an earlier run's
         medoid goes on where that run stopped -- also after append.  The same bits on every run (kpop_kmedoids, include/kpop_hip.h)."""
-        r1 = self.info()["r1"]
         if isinstance(medoids, (int, np.integer)) and not isinstance(medoids, bool):
             medoids = self.farthest_first(max_picks=int(medoids)).pick
-        init, max_iter = _kmedoids_arguments(medoids, max_iter)
-        res = _kmedoids_result(r1, len(init), max_iter)
-        n, conv = C.c_uint32(), C.c_int()
-        check(_lib.load().kpop_kmedoids(self._h, len(init), _p(_nz(init, np.uint32), C.c_uint32), max_iter, *_kmedoids_pointers(res), C.byref(n), C.byref(conv)))
-        return _kmedoids_cut(res, r1, len(init), int(n.value), int(conv.value))
+        return _kmedoids_call(_lib.load().kpop_kmedoids, [self._h], self.info()["r1"], medoids, max_iter)
 
     def spanning_forest(self, max_distance=float("inf")):
         """The single-linkage tree of the set: the minimum spanning forest of the graph that joins rows i < j iff d(j, i) <= max_distance,
         under the order (d, i, j) -> (edge_i u32, edge_j u32, edge_dist f64, labels u32 [r1]).  The order is strict, so the forest is
         unique: the same bits on every run, the edges listed ascending.  labels are clusters(max_distance)'s; forest_cut of the edges
         at any T <= max_distance gives clusters(T) (kpop_spanning_forest, include/kpop_hip.h)."""
-        r1 = self.info()["r1"]
-        room = max(r1 - 1, 1)
-        ei, ej = np.zeros(room, dtype=np.uint32), np.zeros(room, dtype=np.uint32)
-        ed = np.zeros(room, dtype=np.float64)
-        labels = np.zeros(max(r1, 1), dtype=np.uint32)
-        n = C.c_uint32()
-        check(_lib.load().kpop_spanning_forest(self._h, float(max_distance), C.byref(n), _p(ei, C.c_uint32), _p(ej, C.c_uint32), _p(ed, C.c_double),
-                                               _p(labels, C.c_uint32)))
-        n = int(n.value)
-        return ei[:n], ej[:n], ed[:n], labels[:r1]
+        return _forest_call(_lib.load().kpop_spanning_forest, [self._h, float(max_distance)], self.info()["r1"], core=False)
 
     def core_distances(self, min_pts):
         """Every row's core distance -> f64 [r1]: +0 for min_pts = 1, otherwise the distance to its (min_pts - 1)-th nearest OTHER row
@@ -973,17 +936,7 @@ class RefSet:
         spanning_forest(max_distance).  reachability_cut of the edges at any T <= max_distance gives dbscan(T, min_pts)'s labels on the
         core rows, every other row alone (DBSCAN*: border rows are not attached).  No earlier result is a valid start after append
         (kpop_reachability_tree, include/kpop_hip.h)."""
-        r1 = self.info()["r1"]
-        room = max(r1 - 1, 1)
-        ei, ej = np.zeros(room, dtype=np.uint32), np.zeros(room, dtype=np.uint32)
-        ed = np.zeros(room, dtype=np.float64)
-        core = np.zeros(max(r1, 1), dtype=np.float64)
-        labels = np.zeros(max(r1, 1), dtype=np.uint32)
-        n = C.c_uint32()
-        check(_lib.load().kpop_reachability_tree(self._h, _min_pts(min_pts), float(max_distance), C.byref(n), _p(ei, C.c_uint32), _p(ej, C.c_uint32),
-                                                 _p(ed, C.c_double), _p(core, C.c_double), _p(labels, C.c_uint32)))
-        n = int(n.value)
-        return ei[:n], ej[:n], ed[:n], core[:r1], labels[:r1]
+        return _forest_call(_lib.load().kpop_reachability_tree, [self._h, _min_pts(min_pts), float(max_distance)], self.info()["r1"], core=True)
 
     def knn_vote(self, m2, class_of, k=5, n_classes=None):
         """The k-NN classifier of the reference's README on the device -> (cls u32, votes u32, n u32, first f64), one entry a row of m2.
@@ -991,35 +944,20 @@ class RefSet:
         nearest rows of the set by (distance, index) plus every further row at the k-th distance (lib/Matrix.ml:641-650); n its length,
         cls the class with the most members in it -- among equals the one whose nearest member comes first --, votes its count, first that
         member's distance.  An empty list gives NO_CLASS, 0, 0, NaN (kpop_knn_vote, include/kpop_hip.h)."""
-        m2 = _c(m2, np.float64)
         i = self.info()
-        if m2.ndim != 2 or m2.shape[1] != i["n_dims"]:
-            raise ValueError("Incompatible_geometries")
+        m2 = _query_rows(m2, i["n_dims"])
         class_of, n_classes = _classes(class_of, i["r1"], n_classes)
-        r2 = m2.shape[0]
-        cls, votes, n = (np.zeros(r2, dtype=np.uint32) for _ in range(3))
-        first = np.zeros(r2, dtype=np.float64)
-        check(_lib.load().kpop_knn_vote(self._h, _p(_nz(class_of, np.uint32), C.c_uint32), n_classes, _p(_nz(m2, np.float64), C.c_double), r2, int(k),
-                                        _p(_nz(cls, np.uint32), C.c_uint32), _p(_nz(votes, np.uint32), C.c_uint32), _p(_nz(n, np.uint32), C.c_uint32),
-                                        _p(_nz(first, np.float64), C.c_double)))
-        return cls, votes, n, first
+        return _knn_call(_lib.load().kpop_knn_vote, [self._h, _ptr(class_of), n_classes, _ptr(m2), m2.shape[0], int(k)], (m2.shape[0],))
 
     def knn_vote_ks(self, m2, class_of, ks, n_classes=None):
         """knn_vote at every k of ks (strictly ascending, each in 1..128, at most 32 of them) from ONE pass over the pairs ->
         (cls, votes, n, first), each [len(ks)][rows of m2]; slice t is knn_vote(m2, class_of, k=ks[t]) bit for bit (kpop_knn_ks_vote,
         include/kpop_hip.h)."""
-        m2 = _c(m2, np.float64)
         i = self.info()
-        if m2.ndim != 2 or m2.shape[1] != i["n_dims"]:
-            raise ValueError("Incompatible_geometries")
+        m2 = _query_rows(m2, i["n_dims"])
         class_of, n_classes = _classes(class_of, i["r1"], n_classes)
         ks = _ks(ks)
-        r2 = m2.shape[0]
-        cls, votes, n, first = _ks_outputs(len(ks), r2)
-        check(_lib.load().kpop_knn_ks_vote(self._h, _p(_nz(class_of, np.uint32), C.c_uint32), n_classes, _p(_nz(m2, np.float64), C.c_double), r2,
-                                           _p(_nz(ks, np.uint32), C.c_uint32), len(ks), _p(_nz(cls, np.uint32), C.c_uint32),
-                                           _p(_nz(votes, np.uint32), C.c_uint32), _p(_nz(n, np.uint32), C.c_uint32), _p(_nz(first, np.float64), C.c_double)))
-        return cls, votes, n, first
+        return _knn_call(_lib.load().kpop_knn_ks_vote, [self._h, _ptr(class_of), n_classes, _ptr(m2), m2.shape[0], _ptr(ks), len(ks)], (len(ks), m2.shape[0]))
 
     def knn_validate(self, class_of, ks=(1, 3, 5), group_of=None, n_classes=None):
         """The set as its own test: every row classified by its neighbours among the OTHER rows, at every k of ks, from one pass over the
@@ -1027,18 +965,7 @@ class RefSet:
         class at ks[t] is their own.  group_of=None leaves out the row itself (leave-one-out); otherwise every row of the row's group is
         left out of its list (the fold of a cross-validation, an outbreak) -- by index or group, never by distance: a duplicate in another
         group stays.  A row with no list gives NO_CLASS, 0, 0, NaN and is never correct (kpop_knn_validate, include/kpop_hip.h)."""
-        i = self.info()
-        r1 = i["r1"]
-        class_of, n_classes = _classes(class_of, r1, n_classes)
-        group_of = _groups(group_of, r1)
-        ks = _ks(ks)
-        cls, votes, n, first = _ks_outputs(len(ks), r1)
-        correct = np.zeros(max(len(ks), 1), dtype=np.uint64)
-        check(_lib.load().kpop_knn_validate(self._h, _p(_nz(class_of, np.uint32), C.c_uint32), n_classes,
-                                            None if group_of is None else _p(_nz(group_of, np.uint32), C.c_uint32), _p(_nz(ks, np.uint32), C.c_uint32), len(ks),
-                                            _p(_nz(cls, np.uint32), C.c_uint32), _p(_nz(votes, np.uint32), C.c_uint32), _p(_nz(n, np.uint32), C.c_uint32),
-                                            _p(_nz(first, np.float64), C.c_double), _p(correct, C.c_uint64)))
-        return cls, votes, n, first, correct[:len(ks)]
+        return _knn_validate_call(_lib.load().kpop_knn_validate, [self._h], self.info()["r1"], class_of, n_classes, group_of, ks)
 
     def free(self):
         if self._h is not None and self._h.value:
@@ -1082,19 +1009,7 @@ def summarize_distances(dist, keep_at_most=2, max_neighbours=None):
     """Matrix.summarize_distance (lib/Matrix.ml:767-810) on an existing r2 x r1 distance matrix."""
     dist = _c(dist, np.float64)
     r2, r1 = dist.shape
-    if max_neighbours is None:
-        max_neighbours = r1 if not keep_at_most else min(r1, max(keep_at_most * 4, 8))
-    max_neighbours = max(int(max_neighbours), 1)
-    stats = np.zeros((r2, 4), dtype=np.float64)
-    n = np.zeros(r2, dtype=np.uint32)
-    idx = np.zeros((r2, max_neighbours), dtype=np.uint32)
-    dd = np.zeros((r2, max_neighbours), dtype=np.float64)
-    z = np.zeros((r2, max_neighbours), dtype=np.float64)
-    check(_lib.load().kpop_summarize_distances(_p(_nz(dist, np.float64), C.c_double), r2, r1, int(keep_at_most or 0),
-                                               max_neighbours, _p(_nz(stats, np.float64), C.c_double),
-                                               _p(_nz(n, np.uint32), C.c_uint32), _p(_nz(idx, np.uint32), C.c_uint32),
-                                               _p(_nz(dd, np.float64), C.c_double), _p(_nz(z, np.float64), C.c_double)))
-    return stats, n, idx, dd, z
+    return _summary_call(_lib.load().kpop_summarize_distances, [_ptr(dist), r2, r1], r1, r2, keep_at_most, max_neighbours)
 
 
 # ------------------------------------------------- device-resident entry points
@@ -1208,20 +1123,19 @@ def dev_knn_vote(rs, d_class_of, n_classes, d_m2, r2, k, d_work, d_cls, d_votes,
     check(_lib.load().kpop_dev_knn_vote(rs.handle, d_class_of, int(n_classes), d_m2, int(r2), int(k), d_work, d_cls, d_votes, d_n, d_first, stream))
 
 
+def _knn_call(fn, lead, shape, *more):
+    """cls, votes, n, first of a vote: one entry a query row, or one a k and query row.  more: the outputs that follow them"""
+    res = (np.zeros(shape, dtype=np.uint32), np.zeros(shape, dtype=np.uint32), np.zeros(shape, dtype=np.uint32), np.zeros(shape, dtype=np.float64))
+    check(fn(*lead, *_pointers(res + more)))
+    return res
+
+
 def distance_knn_vote(m1, class_of, m2, metric, k=5, kind=EUCLIDEAN, p=2.0, normalize=True, n_classes=None):
     """RefSet(m1, ...).knn_vote(m2, class_of, k) without keeping the set: one call of kpop_distance_knn_vote"""
-    m1, m2, metric = _c(m1, np.float64), _c(m2, np.float64), _c(metric, np.float64)
-    if m1.ndim != 2 or m2.ndim != 2 or m1.shape[1] != len(metric) or m2.shape[1] != len(metric):
-        raise ValueError("Incompatible_geometries")  # lib/Matrix.ml:193-194
-    class_of, n_classes = _classes(class_of, m1.shape[0], n_classes)
-    r2 = m2.shape[0]
-    cls, votes, n = (np.zeros(r2, dtype=np.uint32) for _ in range(3))
-    first = np.zeros(r2, dtype=np.float64)
-    check(_lib.load().kpop_distance_knn_vote(_p(_nz(m1, np.float64), C.c_double), m1.shape[0], _p(_nz(class_of, np.uint32), C.c_uint32), n_classes,
-                                             _p(_nz(m2, np.float64), C.c_double), r2, len(metric), _p(_nz(metric, np.float64), C.c_double), int(kind),
-                                             float(p), 1 if normalize else 0, int(k), _p(_nz(cls, np.uint32), C.c_uint32),
-                                             _p(_nz(votes, np.uint32), C.c_uint32), _p(_nz(n, np.uint32), C.c_uint32), _p(_nz(first, np.float64), C.c_double)))
-    return cls, votes, n, first
+    lead, r1 = _set_geometry(m1, metric, kind, p, normalize)
+    m2 = _query_rows(m2, lead[2])
+    class_of, n_classes = _classes(class_of, r1, n_classes)
+    return _knn_call(_lib.load().kpop_distance_knn_vote, lead[:2] + [_ptr(class_of), n_classes, _ptr(m2), m2.shape[0]] + lead[2:] + [int(k)], (m2.shape[0],))
 
 
 def _ks(ks):
@@ -1241,11 +1155,6 @@ def _groups(group_of, r1):
     if len(group_of) and (group_of.min() < 0 or group_of.max() > 0xFFFFFFFF):
         raise ValueError("group_of: groups are uint32")
     return _c(group_of, np.uint32)
-
-
-def _ks_outputs(n_ks, rows):
-    cls, votes, n = (np.zeros((n_ks, rows), dtype=np.uint32) for _ in range(3))
-    return cls, votes, n, np.zeros((n_ks, rows), dtype=np.float64)
 
 
 def dev_knn_vote_ks_workspace_bytes(rs, r2, k_max, n_classes):
@@ -1275,24 +1184,19 @@ def dev_knn_validate(rs, d_class_of, n_classes, d_group_of, first_row, n_rows, k
                                             len(ks), d_work, d_cls, d_votes, d_n, d_first, d_correct, stream))
 
 
-def distance_knn_validate(m, class_of, metric, ks=(1, 3, 5), group_of=None, kind=EUCLIDEAN, p=2.0, normalize=True, n_classes=None):
-    """RefSet(m, ...).knn_validate(class_of, ks, group_of) without keeping the set: one call of kpop_distance_knn_validate"""
-    m, metric = _c(m, np.float64), _c(metric, np.float64)
-    if m.ndim != 2 or m.shape[1] != len(metric):
-        raise ValueError("Incompatible_geometries")  # lib/Matrix.ml:193-194
-    r1 = m.shape[0]
+def _knn_validate_call(fn, lead, r1, class_of, n_classes, group_of, ks):
     class_of, n_classes = _classes(class_of, r1, n_classes)
     group_of = _groups(group_of, r1)
     ks = _ks(ks)
-    cls, votes, n, first = _ks_outputs(len(ks), r1)
     correct = np.zeros(max(len(ks), 1), dtype=np.uint64)
-    check(_lib.load().kpop_distance_knn_validate(_p(_nz(m, np.float64), C.c_double), r1, len(metric), _p(_nz(metric, np.float64), C.c_double), int(kind),
-                                                 float(p), 1 if normalize else 0, _p(_nz(class_of, np.uint32), C.c_uint32), n_classes,
-                                                 None if group_of is None else _p(_nz(group_of, np.uint32), C.c_uint32),
-                                                 _p(_nz(ks, np.uint32), C.c_uint32), len(ks), _p(_nz(cls, np.uint32), C.c_uint32),
-                                                 _p(_nz(votes, np.uint32), C.c_uint32), _p(_nz(n, np.uint32), C.c_uint32), _p(_nz(first, np.float64), C.c_double),
-                                                 _p(correct, C.c_uint64)))
-    return cls, votes, n, first, correct[:len(ks)]
+    res = _knn_call(fn, lead + [_ptr(class_of), n_classes, None if group_of is None else _ptr(group_of), _ptr(ks), len(ks)], (len(ks), r1), correct)
+    return res + (correct[:len(ks)],)
+
+
+def distance_knn_validate(m, class_of, metric, ks=(1, 3, 5), group_of=None, kind=EUCLIDEAN, p=2.0, normalize=True, n_classes=None):
+    """RefSet(m, ...).knn_validate(class_of, ks, group_of) without keeping the set: one call of kpop_distance_knn_validate"""
+    lead, r1 = _set_geometry(m, metric, kind, p, normalize)
+    return _knn_validate_call(_lib.load().kpop_distance_knn_validate, lead, r1, class_of, n_classes, group_of, ks)
 
 
 def confusion_matrix(class_of, predicted, n_classes):
@@ -1323,26 +1227,27 @@ def dev_neighbours_within(rs, d_m2, r2, max_distance, capacity, d_work, d_offset
     check(_lib.load().kpop_dev_neighbours_within(rs.handle, d_m2, int(r2), float(max_distance), int(capacity), d_work, d_offsets, d_idx, d_dist, stream))
 
 
+def _within_call(fn, lead, r2, capacity):
+    capacity = int(capacity)
+    offsets = np.zeros(r2 + 1, dtype=np.uint64)
+    idx = np.zeros(max(capacity, 1), dtype=np.uint32)
+    dist = np.zeros(max(capacity, 1), dtype=np.float64)
+    check(fn(*lead, capacity, _ptr(offsets), _ptr(idx), _ptr(dist)))
+    total = int(offsets[r2])
+    return offsets, idx[:total], dist[:total]
+
+
 def distance_within(m1, m2, metric, max_distance, kind=EUCLIDEAN, p=2.0, normalize=True, capacity=None):
     """RefSet(m1, ...).within(m2, max_distance) without keeping the set; with a capacity, one call of kpop_distance_within"""
-    m1, m2, metric = _c(m1, np.float64), _c(m2, np.float64), _c(metric, np.float64)
     if capacity is None:
-        rs = RefSet(m1, metric, kind=kind, p=p, normalize=normalize)
+        rs = RefSet(_c(m1, np.float64), _c(metric, np.float64), kind=kind, p=p, normalize=normalize)
         try:
             return rs.within(m2, max_distance)
         finally:
             rs.free()
-    if m1.ndim != 2 or m2.ndim != 2 or m1.shape[1] != len(metric) or m2.shape[1] != len(metric):
-        raise ValueError("Incompatible_geometries")  # lib/Matrix.ml:193-194
-    r2, capacity = m2.shape[0], int(capacity)
-    offsets = np.zeros(r2 + 1, dtype=np.uint64)
-    idx = np.zeros(max(capacity, 1), dtype=np.uint32)
-    dist = np.zeros(max(capacity, 1), dtype=np.float64)
-    check(_lib.load().kpop_distance_within(_p(_nz(m1, np.float64), C.c_double), m1.shape[0], _p(_nz(m2, np.float64), C.c_double), r2, len(metric),
-                                           _p(_nz(metric, np.float64), C.c_double), int(kind), float(p), 1 if normalize else 0, float(max_distance),
-                                           capacity, _p(offsets, C.c_uint64), _p(idx, C.c_uint32), _p(dist, C.c_double)))
-    total = int(offsets[r2])
-    return offsets, idx[:total], dist[:total]
+    lead, r1 = _set_geometry(m1, metric, kind, p, normalize)
+    m2 = _query_rows(m2, lead[2])
+    return _within_call(_lib.load().kpop_distance_within, lead[:2] + [_ptr(m2), m2.shape[0]] + lead[2:] + [float(max_distance)], m2.shape[0], capacity)
 
 
 def dev_clusters_within_workspace_bytes(rs):
@@ -1355,17 +1260,16 @@ def dev_clusters_within(rs, max_distance, d_work, d_labels, d_n_clusters, known_
     check(_lib.load().kpop_dev_clusters_within(rs.handle, float(max_distance), int(known_rows), d_work, d_labels, d_n_clusters, stream))
 
 
+def _clusters_call(fn, lead, r1, labels):
+    n = C.c_uint32()
+    check(fn(*lead, _ptr(labels), C.byref(n)))
+    return labels[:r1], int(n.value)
+
+
 def distance_clusters(m, metric, kind=EUCLIDEAN, p=2.0, normalize=True, max_distance=0.0):
     """RefSet(m, ...).clusters(max_distance) without keeping the set: one call of kpop_distance_clusters -> (labels u32 [rows], n_clusters)"""
-    m, metric = _c(m, np.float64), _c(metric, np.float64)
-    if m.ndim != 2 or m.shape[1] != len(metric):
-        raise ValueError("Incompatible_geometries")  # lib/Matrix.ml:193-194
-    rows = m.shape[0]
-    labels = np.zeros(max(rows, 1), dtype=np.uint32)
-    n = C.c_uint32()
-    check(_lib.load().kpop_distance_clusters(_p(_nz(m, np.float64), C.c_double), rows, len(metric), _p(_nz(metric, np.float64), C.c_double), int(kind),
-                                             float(p), 1 if normalize else 0, float(max_distance), _p(labels, C.c_uint32), C.byref(n)))
-    return labels[:rows], int(n.value)
+    lead, rows = _set_geometry(m, metric, kind, p, normalize)
+    return _clusters_call(_lib.load().kpop_distance_clusters, lead + [float(max_distance)], rows, np.zeros(max(rows, 1), dtype=np.uint32))
 
 
 def dev_representatives_within_workspace_bytes(rs):
@@ -1379,20 +1283,18 @@ def dev_representatives_within(rs, max_distance, d_work, d_rep_of, d_rep_dist, d
     check(_lib.load().kpop_dev_representatives_within(rs.handle, float(max_distance), int(known_rows), d_work, d_rep_of, d_rep_dist, d_n_reps, stream))
 
 
+def _representatives_call(fn, lead, r1, rep_of, rep_dist):
+    n = C.c_uint32()
+    check(fn(*lead, _ptr(rep_of), _ptr(rep_dist), C.byref(n)))
+    return rep_of[:r1], rep_dist[:r1], int(n.value)
+
+
 def distance_representatives(m, metric, kind=EUCLIDEAN, p=2.0, normalize=True, max_distance=0.0):
     """RefSet(m, ...).representatives(max_distance) without keeping the set: one call of kpop_distance_representatives ->
     (rep_of u32 [rows], rep_dist f64 [rows], n_reps)"""
-    m, metric = _c(m, np.float64), _c(metric, np.float64)
-    if m.ndim != 2 or m.shape[1] != len(metric):
-        raise ValueError("Incompatible_geometries")  # lib/Matrix.ml:193-194
-    rows = m.shape[0]
-    rep_of = np.zeros(max(rows, 1), dtype=np.uint32)
-    rep_dist = np.zeros(max(rows, 1), dtype=np.float64)
-    n = C.c_uint32()
-    check(_lib.load().kpop_distance_representatives(_p(_nz(m, np.float64), C.c_double), rows, len(metric), _p(_nz(metric, np.float64), C.c_double), int(kind),
-                                                    float(p), 1 if normalize else 0, float(max_distance), _p(rep_of, C.c_uint32), _p(rep_dist, C.c_double),
-                                                    C.byref(n)))
-    return rep_of[:rows], rep_dist[:rows], int(n.value)
+    lead, rows = _set_geometry(m, metric, kind, p, normalize)
+    return _representatives_call(_lib.load().kpop_distance_representatives, lead + [float(max_distance)], rows, np.zeros(max(rows, 1), dtype=np.uint32),
+                                 np.zeros(max(rows, 1), dtype=np.float64))
 
 
 NOISE = 0xFFFFFFFF  # KPOP_NOISE: the label and the core row of a row that is neither a core row nor within eps of one
@@ -1416,19 +1318,18 @@ def dev_dbscan(rs, eps, min_pts, d_work, d_labels, d_core_of, d_degree, d_counts
     check(_lib.load().kpop_dev_dbscan(rs.handle, float(eps), _min_pts(min_pts), d_work, d_labels, d_core_of, d_degree, d_counts, stream))
 
 
+def _dbscan_call(fn, lead, r1):
+    labels, core_of, degree = (np.zeros(max(r1, 1), dtype=np.uint32) for _ in range(3))
+    counts = np.zeros(3, dtype=np.uint32)
+    check(fn(*lead, _ptr(labels), _ptr(core_of), _ptr(degree), _ptr(counts)))
+    return labels[:r1], core_of[:r1], degree[:r1], counts
+
+
 def distance_dbscan(m, metric, kind=EUCLIDEAN, p=2.0, normalize=True, eps=0.0, min_pts=1):
     """RefSet(m, ...).dbscan(eps, min_pts) without keeping the set: one call of kpop_distance_dbscan ->
     (labels u32 [rows], core_of u32 [rows], degree u32 [rows], counts u32 [3])"""
-    m, metric = _c(m, np.float64), _c(metric, np.float64)
-    if m.ndim != 2 or m.shape[1] != len(metric):
-        raise ValueError("Incompatible_geometries")  # lib/Matrix.ml:193-194
-    rows = m.shape[0]
-    labels, core_of, degree = (np.zeros(max(rows, 1), dtype=np.uint32) for _ in range(3))
-    counts = np.zeros(3, dtype=np.uint32)
-    check(_lib.load().kpop_distance_dbscan(_p(_nz(m, np.float64), C.c_double), rows, len(metric), _p(_nz(metric, np.float64), C.c_double), int(kind),
-                                           float(p), 1 if normalize else 0, float(eps), _min_pts(min_pts), _p(labels, C.c_uint32), _p(core_of, C.c_uint32),
-                                           _p(degree, C.c_uint32), _p(counts, C.c_uint32)))
-    return labels[:rows], core_of[:rows], degree[:rows], counts
+    lead, rows = _set_geometry(m, metric, kind, p, normalize)
+    return _dbscan_call(_lib.load().kpop_distance_dbscan, lead + [float(eps), _min_pts(min_pts)], rows)
 
 
 def dev_spanning_forest_workspace_bytes(rs):
@@ -1442,23 +1343,22 @@ def dev_spanning_forest(rs, max_distance, d_work, d_n_edges, d_edge_i, d_edge_j,
     check(_lib.load().kpop_dev_spanning_forest(rs.handle, float(max_distance), d_work, d_n_edges, d_edge_i, d_edge_j, d_edge_dist, d_labels, stream))
 
 
+def _forest_call(fn, lead, r1, core):
+    """the edges of a forest, cut at their count, then the rows' core distances (core: the mutual-reachability forest) and labels"""
+    room = max(r1 - 1, 1)
+    edges = (np.zeros(room, dtype=np.uint32), np.zeros(room, dtype=np.uint32), np.zeros(room, dtype=np.float64))
+    rows = ((np.zeros(max(r1, 1), dtype=np.float64),) if core else ()) + (np.zeros(max(r1, 1), dtype=np.uint32),)
+    n = C.c_uint32()
+    check(fn(*lead, C.byref(n), *_pointers(edges + rows)))
+    n = int(n.value)
+    return tuple(x[:n] for x in edges) + tuple(x[:r1] for x in rows)
+
+
 def distance_spanning_forest(m, metric, kind=EUCLIDEAN, p=2.0, normalize=True, max_distance=float("inf")):
     """RefSet(m, ...).spanning_forest(max_distance) without keeping the set: one call of kpop_distance_spanning_forest
     -> (edge_i, edge_j, edge_dist, labels)"""
-    m, metric = _c(m, np.float64), _c(metric, np.float64)
-    if m.ndim != 2 or m.shape[1] != len(metric):
-        raise ValueError("Incompatible_geometries")
-    rows = m.shape[0]
-    room = max(rows - 1, 1)
-    ei, ej = np.zeros(room, dtype=np.uint32), np.zeros(room, dtype=np.uint32)
-    ed = np.zeros(room, dtype=np.float64)
-    labels = np.zeros(max(rows, 1), dtype=np.uint32)
-    n = C.c_uint32()
-    check(_lib.load().kpop_distance_spanning_forest(_p(_nz(m, np.float64), C.c_double), rows, len(metric), _p(_nz(metric, np.float64), C.c_double),
-                                                    int(kind), float(p), 1 if normalize else 0, float(max_distance), C.byref(n), _p(ei, C.c_uint32),
-                                                    _p(ej, C.c_uint32), _p(ed, C.c_double), _p(labels, C.c_uint32)))
-    n = int(n.value)
-    return ei[:n], ej[:n], ed[:n], labels[:rows]
+    lead, rows = _set_geometry(m, metric, kind, p, normalize)
+    return _forest_call(_lib.load().kpop_distance_spanning_forest, lead + [float(max_distance)], rows, core=False)
 
 
 def forest_cut(r1, edge_i, edge_j, edge_dist, T):
@@ -1503,22 +1403,8 @@ def dev_reachability_forest(rs, min_pts, max_distance, d_work, d_n_edges, d_edge
 def distance_reachability_forest(m, metric, kind=EUCLIDEAN, p=2.0, normalize=True, min_pts=1, max_distance=float("inf")):
     """RefSet(m, ...).reachability_forest(min_pts, max_distance) without keeping the set: one call of kpop_distance_reachability_tree
     -> (edge_i, edge_j, edge_dist, core_dist, labels)"""
-    m, metric = _c(m, np.float64), _c(metric, np.float64)
-    if m.ndim != 2 or m.shape[1] != len(metric):
-        raise ValueError("Incompatible_geometries")
-    rows = m.shape[0]
-    room = max(rows - 1, 1)
-    ei, ej = np.zeros(room, dtype=np.uint32), np.zeros(room, dtype=np.uint32)
-    ed = np.zeros(room, dtype=np.float64)
-    core = np.zeros(max(rows, 1), dtype=np.float64)
-    labels = np.zeros(max(rows, 1), dtype=np.uint32)
-    n = C.c_uint32()
-    check(_lib.load().kpop_distance_reachability_tree(_p(_nz(m, np.float64), C.c_double), rows, len(metric), _p(_nz(metric, np.float64), C.c_double),
-                                                      int(kind), float(p), 1 if normalize else 0, _min_pts(min_pts), float(max_distance), C.byref(n),
-                                                      _p(ei, C.c_uint32), _p(ej, C.c_uint32), _p(ed, C.c_double), _p(core, C.c_double),
-                                                      _p(labels, C.c_uint32)))
-    n = int(n.value)
-    return ei[:n], ej[:n], ed[:n], core[:rows], labels[:rows]
+    lead, rows = _set_geometry(m, metric, kind, p, normalize)
+    return _forest_call(_lib.load().kpop_distance_reachability_tree, lead + [_min_pts(min_pts), float(max_distance)], rows, core=True)
 
 
 def reachability_cut(r1, edge_i, edge_j, edge_dist, core_dist, T):
@@ -1563,17 +1449,12 @@ def _left_out_classes(class_of, r1, n_classes):
     return class_of, n_classes
 
 
-def _silhouette_result(r1, n_classes):
+def _silhouette_call(fn, lead, r1, class_of, n_classes):
+    class_of, n_classes = _left_out_classes(class_of, r1, n_classes)
     rows, classes = max(r1, 1), max(min(n_classes, 65536), 1)  # (the library refuses more classes before it writes)
-    return Silhouette(np.zeros(rows, dtype=np.float64), np.zeros(rows, dtype=np.float64), np.zeros(rows, dtype=np.uint32), np.zeros(rows, dtype=np.float64),
-                      np.zeros(classes, dtype=np.uint32), np.zeros(classes, dtype=np.uint32), np.zeros(classes, dtype=np.float64))
-
-
-def _silhouette_pointers(res):
-    return [_p(x, C.c_double if x.dtype == np.float64 else C.c_uint32) for x in res]
-
-
-def _silhouette_cut(res, r1, n_classes):
+    res = (np.zeros(rows, dtype=np.float64), np.zeros(rows, dtype=np.float64), np.zeros(rows, dtype=np.uint32), np.zeros(rows, dtype=np.float64),
+           np.zeros(classes, dtype=np.uint32), np.zeros(classes, dtype=np.uint32), np.zeros(classes, dtype=np.float64))
+    check(fn(*lead, _ptr(class_of), n_classes, *_pointers(res)))
     return Silhouette(*[x[:r1] for x in res[:4]], *[x[:n_classes] for x in res[4:]])
 
 
@@ -1593,15 +1474,8 @@ def dev_silhouette(rs, d_class_of, n_classes, d_work, d_own_mean=None, d_other_m
 
 def distance_silhouette(m, metric, class_of, kind=EUCLIDEAN, p=2.0, normalize=True, n_classes=None):
     """RefSet(m, ...).silhouette(class_of, n_classes) without keeping the set: one call of kpop_distance_silhouette -> Silhouette"""
-    m, metric = _c(m, np.float64), _c(metric, np.float64)
-    if m.ndim != 2 or m.shape[1] != len(metric):
-        raise ValueError("Incompatible_geometries")  # lib/Matrix.ml:193-194
-    rows = m.shape[0]
-    class_of, n_classes = _left_out_classes(class_of, rows, n_classes)
-    res = _silhouette_result(rows, n_classes)
-    check(_lib.load().kpop_distance_silhouette(_p(_nz(m, np.float64), C.c_double), rows, len(metric), _p(_nz(metric, np.float64), C.c_double), int(kind),
-                                               float(p), 1 if normalize else 0, _p(_nz(class_of, np.uint32), C.c_uint32), n_classes, *_silhouette_pointers(res)))
-    return _silhouette_cut(res, rows, n_classes)
+    lead, rows = _set_geometry(m, metric, kind, p, normalize)
+    return _silhouette_call(_lib.load().kpop_distance_silhouette, lead, rows, class_of, n_classes)
 
 
 def silhouette_summary(class_of, silhouette, n_classes=None):
@@ -1634,18 +1508,14 @@ def _farthest_first_arguments(rows, max_picks, seeds):
     return max_picks, _c(seeds, np.uint32)
 
 
-def _farthest_first_result(rows, max_picks):
+def _farthest_first_call(fn, lead, rows, max_picks, cover_radius, seeds):
+    max_picks, seeds = _farthest_first_arguments(rows, max_picks, seeds)
     k, n = max(min(max_picks, rows), 1), max(rows, 1)
-    return (np.zeros(k, dtype=np.uint32), np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.uint32), np.zeros(n, dtype=np.uint32),
-            np.zeros(n, dtype=np.float64))
-
-
-def _farthest_first_pointers(res):
-    return [_p(x, C.c_double if x.dtype == np.float64 else C.c_uint32) for x in res]
-
-
-def _farthest_first_cut(res, rows, n, n_passes):
-    return FarthestFirst(res[0][:n], res[1][:n], res[2][:n], res[3][:rows], res[4][:rows], n_passes)
+    res = (np.zeros(k, dtype=np.uint32), np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.uint32), np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.float64))
+    picks, passes = C.c_uint32(), C.c_uint32()
+    check(fn(*lead, max_picks, float(cover_radius), _ptr(seeds), len(seeds), C.byref(picks), *_pointers(res), C.byref(passes)))
+    picks = int(picks.value)
+    return FarthestFirst(res[0][:picks], res[1][:picks], res[2][:picks], res[3][:rows], res[4][:rows], int(passes.value))
 
 
 def dev_farthest_first_workspace_bytes(rs, max_picks):
@@ -1664,17 +1534,8 @@ def dev_farthest_first(rs, max_picks, cover_radius, d_work, d_counts, d_pick=Non
 def distance_farthest_first(m, metric, kind=EUCLIDEAN, p=2.0, normalize=True, max_picks=None, cover_radius=-1.0, seeds=None):
     """RefSet(m, ...).farthest_first(max_picks, cover_radius, seeds) without keeping the set: one call of kpop_distance_farthest_first ->
     FarthestFirst"""
-    m, metric = _c(m, np.float64), _c(metric, np.float64)
-    if m.ndim != 2 or m.shape[1] != len(metric):
-        raise ValueError("Incompatible_geometries")  # lib/Matrix.ml:193-194
-    rows = m.shape[0]
-    max_picks, seeds = _farthest_first_arguments(rows, max_picks, seeds)
-    res = _farthest_first_result(rows, max_picks)
-    n, passes = C.c_uint32(), C.c_uint32()
-    check(_lib.load().kpop_distance_farthest_first(_p(_nz(m, np.float64), C.c_double), rows, len(metric), _p(_nz(metric, np.float64), C.c_double), int(kind),
-                                                   float(p), 1 if normalize else 0, max_picks, float(cover_radius), _p(_nz(seeds, np.uint32), C.c_uint32),
-                                                   len(seeds), C.byref(n), *_farthest_first_pointers(res), C.byref(passes)))
-    return _farthest_first_cut(res, rows, int(n.value), int(passes.value))
+    lead, rows = _set_geometry(m, metric, kind, p, normalize)
+    return _farthest_first_call(_lib.load().kpop_distance_farthest_first, lead, rows, max_picks, cover_radius, seeds)
 
 
 KMedoids = collections.namedtuple("KMedoids", "medoid class_of dist own_mean class_rows cost n_iter converged")
@@ -1693,18 +1554,15 @@ def _kmedoids_arguments(medoids, max_iter):
     return _c(medoids, np.uint32), max_iter
 
 
-def _kmedoids_result(rows, k, max_iter):
-    n, k = max(rows, 1), max(min(k, 65536), 1)  # (the library refuses more medoids before it writes)
-    return (np.zeros(k, dtype=np.uint32), np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.float64), np.zeros(k, dtype=np.uint32),
-            np.zeros(max_iter + 1, dtype=np.float64))
-
-
-def _kmedoids_pointers(res):
-    return [_p(x, C.c_double if x.dtype == np.float64 else C.c_uint32) for x in res]
-
-
-def _kmedoids_cut(res, rows, k, n_iter, converged):
-    return KMedoids(res[0][:k], res[1][:rows], res[2][:rows], res[3][:rows], res[4][:k], res[5][:n_iter + 1], n_iter, bool(converged))
+def _kmedoids_call(fn, lead, rows, medoids, max_iter):
+    init, max_iter = _kmedoids_arguments(medoids, max_iter)
+    n, k = max(rows, 1), max(min(len(init), 65536), 1)  # (the library refuses more medoids before it writes)
+    res = (np.zeros(k, dtype=np.uint32), np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.float64), np.zeros(k, dtype=np.uint32),
+           np.zeros(max_iter + 1, dtype=np.float64))
+    n_iter, conv = C.c_uint32(), C.c_int()
+    check(fn(*lead, len(init), _ptr(init), max_iter, *_pointers(res), C.byref(n_iter), C.byref(conv)))
+    n_iter, k = int(n_iter.value), len(init)
+    return KMedoids(res[0][:k], res[1][:rows], res[2][:rows], res[3][:rows], res[4][:k], res[5][:n_iter + 1], n_iter, bool(conv.value))
 
 
 def dev_kmedoids_workspace_bytes(rs, n_medoids, max_iter):
@@ -1724,17 +1582,8 @@ def dev_kmedoids(rs, n_medoids, d_init, max_iter, d_work, d_counts, d_medoid=Non
 def distance_kmedoids(m, metric, medoids, kind=EUCLIDEAN, p=2.0, normalize=True, max_iter=100):
     """RefSet(m, ...).kmedoids(medoids, max_iter) without keeping the set, medoids an index array or a FarthestFirst: one call of
     kpop_distance_kmedoids -> KMedoids"""
-    m, metric = _c(m, np.float64), _c(metric, np.float64)
-    if m.ndim != 2 or m.shape[1] != len(metric):
-        raise ValueError("Incompatible_geometries")  # lib/Matrix.ml:193-194
-    rows = m.shape[0]
-    init, max_iter = _kmedoids_arguments(medoids, max_iter)
-    res = _kmedoids_result(rows, len(init), max_iter)
-    n, conv = C.c_uint32(), C.c_int()
-    check(_lib.load().kpop_distance_kmedoids(_p(_nz(m, np.float64), C.c_double), rows, len(metric), _p(_nz(metric, np.float64), C.c_double), int(kind), float(p),
-                                             1 if normalize else 0, len(init), _p(_nz(init, np.uint32), C.c_uint32), max_iter, *_kmedoids_pointers(res),
-                                             C.byref(n), C.byref(conv)))
-    return _kmedoids_cut(res, rows, len(init), int(n.value), int(conv.value))
+    lead, rows = _set_geometry(m, metric, kind, p, normalize)
+    return _kmedoids_call(_lib.load().kpop_distance_kmedoids, lead, rows, medoids, max_iter)
 
 
 def dense_labels(labels):

@@ -127,23 +127,20 @@ extern "C" int kpop_clusters_within(kpop_refset *rs, double max_distance, uint32
   const char *who = "kpop_clusters_within";
   KPOP_TRY(refset_check_handle(rs, who));
   ArenaScope scratch;
-  if (max_distance != max_distance) KPOP_FAIL(KPOP_ERR_INVALID, "%s: the distance is not a number", who);
+  KPOP_TRY(check_distance_is_a_number(max_distance, who));
   if (!n_clusters || (rs->r1 && !labels)) KPOP_FAIL(KPOP_ERR_INVALID, "%s: null argument", who);
   const uint32_t r1 = rs->r1;
   if (known_rows > r1) KPOP_FAIL(KPOP_ERR_INVALID, "%s: %u known rows in a set of %u", who, known_rows, r1);
   KPOP_TRY(check_known_prefix(labels, known_rows, who, "labels", "a label"));
   *n_clusters = 0;
   if (r1 == 0) return KPOP_OK;
-  hipStream_t st = nullptr;
-  DevBuf dl, dn;
-  KPOP_TRY(dl.alloc((uint64_t)r1 * 4));
-  KPOP_TRY(dn.alloc(256));
-  if (known_rows) KPOP_HIP(hipMemcpyAsync(dl.p, labels, (uint64_t)known_rows * 4, hipMemcpyHostToDevice, st));
-  KPOP_TRY(clusters_dev(rs, max_distance, known_rows, dl.as<uint32_t>(), dn.as<uint32_t>(), st));
-  KPOP_HIP(hipMemcpyAsync(labels, dl.p, (uint64_t)r1 * 4, hipMemcpyDeviceToHost, st));
-  KPOP_HIP(hipMemcpyAsync(n_clusters, dn.p, 4, hipMemcpyDeviceToHost, st));
-  KPOP_HIP(hipStreamSynchronize(st));
-  return KPOP_OK;
+  HostCall h;
+  uint32_t *dl = h.out(labels, r1);
+  uint32_t *dn = h.scalars(n_clusters, 1);
+  h.up(dl, labels, known_rows);
+  KPOP_TRY(h.upload());
+  KPOP_TRY(clusters_dev(rs, max_distance, known_rows, dl, dn, h.st));
+  return h.finish();
 }
 
 extern "C" int kpop_distance_clusters(const double *m, uint32_t rows, uint32_t n_dims, const double *metric, int kind, double p, int normalize,

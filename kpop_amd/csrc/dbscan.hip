@@ -389,21 +389,12 @@ extern "C" int kpop_dbscan(kpop_refset *rs, double eps, uint32_t min_pts, uint32
   counts[0] = counts[1] = counts[2] = 0;
   const uint32_t r1 = rs->r1;
   if (r1 == 0) return KPOP_OK;
-  hipStream_t st = nullptr;
-  DevBuf work, dl, dc, dd, dn;
-  KPOP_TRY(work.alloc(dbscan_carve(nullptr, r1).bytes));
-  KPOP_TRY(dl.alloc((uint64_t)r1 * 4));
-  if (core_of) KPOP_TRY(dc.alloc((uint64_t)r1 * 4));
-  if (degree) KPOP_TRY(dd.alloc((uint64_t)r1 * 4));
-  KPOP_TRY(dn.alloc(256));
-  KPOP_TRY(dbscan_dev(rs, eps, min_pts, work.p, dl.as<uint32_t>(), core_of ? dc.as<uint32_t>() : nullptr, degree ? dd.as<uint32_t>() : nullptr,
-                      dn.as<uint32_t>(), st, who));
-  KPOP_HIP(hipMemcpyAsync(labels, dl.p, (uint64_t)r1 * 4, hipMemcpyDeviceToHost, st));
-  if (core_of) KPOP_HIP(hipMemcpyAsync(core_of, dc.p, (uint64_t)r1 * 4, hipMemcpyDeviceToHost, st));
-  if (degree) KPOP_HIP(hipMemcpyAsync(degree, dd.p, (uint64_t)r1 * 4, hipMemcpyDeviceToHost, st));
-  KPOP_HIP(hipMemcpyAsync(counts, dn.p, 12, hipMemcpyDeviceToHost, st));
-  KPOP_HIP(hipStreamSynchronize(st));
-  return KPOP_OK;
+  HostCall h;
+  void *work = h.work(dbscan_carve(nullptr, r1).bytes);
+  uint32_t *dl = h.out(labels, r1), *dc = h.out(core_of, r1), *dd = h.out(degree, r1), *dn = h.scalars(counts, 3);
+  KPOP_TRY(h.upload());
+  KPOP_TRY(dbscan_dev(rs, eps, min_pts, work, dl, dc, dd, dn, h.st, who));
+  return h.finish();
 }
 
 extern "C" int kpop_distance_dbscan(const double *m, uint32_t rows, uint32_t n_dims, const double *metric, int kind, double p, int normalize, double eps,

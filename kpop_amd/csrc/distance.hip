@@ -23,6 +23,7 @@
 #include <string.h>
 
 #include "common.h"
+#include "host_call.h"
 #include "summary_types.h"
 #include "radix_sort.h"
 #include "space_ops.h"
@@ -1810,29 +1811,16 @@ extern "C" int kpop_summarize_distances(const double *dist, uint32_t r2, uint32_
   ArenaScope scratch;
   if (r2 == 0) return KPOP_OK;
   if (!out_stats || !out_n || (r1 && !dist)) KPOP_FAIL(KPOP_ERR_INVALID, "kpop_summarize_distances: null argument");
-  hipStream_t st = nullptr;
-  DevBuf dd, ds, dn, di, dv, dz;
-  const uint64_t nn = (uint64_t)r2 * max_neighbours;
-  KPOP_TRY(dd.alloc((uint64_t)r1 * r2 * 8));
-  KPOP_TRY(ds.alloc((uint64_t)r2 * 4 * 8));
-  KPOP_TRY(dn.alloc((uint64_t)r2 * 4));
-  KPOP_TRY(di.alloc(nn * 4));
-  KPOP_TRY(dv.alloc(nn * 8));
-  KPOP_TRY(dz.alloc(nn * 8));
-  if (r1) KPOP_HIP(hipMemcpyAsync(dd.p, dist, (uint64_t)r1 * r2 * 8, hipMemcpyHostToDevice, st));
-  KPOP_TRY(kpop_dev_summarize_distances(dd.as<double>(), r2, r1, keep_at_most, max_neighbours, ds.as<double>(),
-                                        dn.as<uint32_t>(), di.as<uint32_t>(), dv.as<double>(), dz.as<double>(), st));
-  KPOP_HIP(hipMemcpyAsync(out_stats, ds.p, (uint64_t)r2 * 4 * 8, hipMemcpyDeviceToHost, st));
-  KPOP_HIP(hipMemcpyAsync(out_n, dn.p, (uint64_t)r2 * 4, hipMemcpyDeviceToHost, st));
-  if (nn) {
-    KPOP_HIP(hipMemcpyAsync(out_idx, di.p, nn * 4, hipMemcpyDeviceToHost, st));
-    KPOP_HIP(hipMemcpyAsync(out_dist, dv.p, nn * 8, hipMemcpyDeviceToHost, st));
-    KPOP_HIP(hipMemcpyAsync(out_z, dz.p, nn * 8, hipMemcpyDeviceToHost, st));
-  }
-  KPOP_HIP(hipStreamSynchronize(st));
+  const SummaryOut host{out_stats, out_n, out_idx, out_dist, out_z, keep_at_most, max_neighbours};
+  HostCall h;
+  const double *dd = h.in(dist, (uint64_t)r1 * r2);
+  const SummaryOut dev = summary_stage(h, r2, host);
+  KPOP_TRY(h.upload());
+  KPOP_TRY(kpop_dev_summarize_distances(dd, r2, r1, keep_at_most, max_neighbours, dev.stats, dev.n, dev.idx, dev.dist, dev.z, h.st));
+  KPOP_TRY(h.finish());
   LongListSource src;
-  src.d_rows = dd.as<double>();
-  return fill_long_lists(src, r1, r2, SummaryOut{out_stats, out_n, out_idx, out_dist, out_z, keep_at_most, max_neighbours}, st);
+  src.d_rows = dd;
+  return fill_long_lists(src, r1, r2, host, h.st);
 }
 
 extern "C" int kpop_distance_rowwise(const double *m1, uint32_t r1, const double *m2, uint32_t r2, uint32_t n_dims,
@@ -1871,39 +1859,21 @@ extern "C" int kpop_distance_summary(const double *m1, uint32_t r1, const double
   if (!m2 || !metric || !out_stats || !out_n || (r1 && !m1))
     KPOP_FAIL(KPOP_ERR_INVALID, "kpop_distance_summary: null argument");
   if (n_dims == 0) KPOP_FAIL(KPOP_ERR_INVALID, "kpop_distance_summary: n_dims must be positive");
-  hipStream_t st = nullptr;
-  DevBuf d1, d2, dm, dw, ds, dn, di, dd, dz;
-  const uint64_t nn = (uint64_t)r2 * max_neighbours;
-  KPOP_TRY(d1.alloc((uint64_t)r1 * n_dims * 8));
-  KPOP_TRY(d2.alloc((uint64_t)r2 * n_dims * 8));
-  KPOP_TRY(dm.alloc((uint64_t)n_dims * 8));
-  KPOP_TRY(dw.alloc(kpop_dev_distance_workspace_bytes(r1, r2, n_dims)));
-  KPOP_TRY(ds.alloc((uint64_t)r2 * 4 * 8));
-  KPOP_TRY(dn.alloc((uint64_t)r2 * 4));
-  KPOP_TRY(di.alloc(nn * 4));
-  KPOP_TRY(dd.alloc(nn * 8));
-  KPOP_TRY(dz.alloc(nn * 8));
-  if (r1) KPOP_HIP(hipMemcpyAsync(d1.p, m1, (uint64_t)r1 * n_dims * 8, hipMemcpyHostToDevice, st));
-  KPOP_HIP(hipMemcpyAsync(d2.p, m2, (uint64_t)r2 * n_dims * 8, hipMemcpyHostToDevice, st));
-  KPOP_HIP(hipMemcpyAsync(dm.p, metric, (uint64_t)n_dims * 8, hipMemcpyHostToDevice, st));
-  KPOP_TRY(kpop_dev_distance_summary(d1.as<double>(), r1, d2.as<double>(), r2, n_dims, dm.as<double>(), kind, p,
-                                     normalize, keep_at_most, max_neighbours, dw.p, ds.as<double>(), dn.as<uint32_t>(),
-                                     di.as<uint32_t>(), dd.as<double>(), dz.as<double>(), st));
-  KPOP_HIP(hipMemcpyAsync(out_stats, ds.p, (uint64_t)r2 * 4 * 8, hipMemcpyDeviceToHost, st));
-  KPOP_HIP(hipMemcpyAsync(out_n, dn.p, (uint64_t)r2 * 4, hipMemcpyDeviceToHost, st));
-  if (nn) {
-    KPOP_HIP(hipMemcpyAsync(out_idx, di.p, nn * 4, hipMemcpyDeviceToHost, st));
-    KPOP_HIP(hipMemcpyAsync(out_dist, dd.p, nn * 8, hipMemcpyDeviceToHost, st));
-    KPOP_HIP(hipMemcpyAsync(out_z, dz.p, nn * 8, hipMemcpyDeviceToHost, st));
-  }
-  KPOP_HIP(hipStreamSynchronize(st));
+  const SummaryOut host{out_stats, out_n, out_idx, out_dist, out_z, keep_at_most, max_neighbours};
+  HostCall h;
+  const double *d1 = h.in(m1, (uint64_t)r1 * n_dims), *d2 = h.in(m2, (uint64_t)r2 * n_dims), *dm = h.in(metric, n_dims);
+  void *dw = h.work(kpop_dev_distance_workspace_bytes(r1, r2, n_dims));
+  const SummaryOut dev = summary_stage(h, r2, host);
+  KPOP_TRY(h.upload());
+  KPOP_TRY(kpop_dev_distance_summary(d1, r1, d2, r2, n_dims, dm, kind, p, normalize, keep_at_most, max_neighbours, dw, dev.stats, dev.n, dev.idx, dev.dist, dev.z, h.st));
+  KPOP_TRY(h.finish());
   LongListSource src;
-  src.d1 = d1.as<double>();
-  src.d2 = d2.as<double>();
-  src.dm = dm.as<double>();
+  src.d1 = d1;
+  src.d2 = d2;
+  src.dm = dm;
   src.n_dims = n_dims;
   src.kind = kind;
   src.normalize = normalize;
   src.p = p;
-  return fill_long_lists(src, r1, r2, SummaryOut{out_stats, out_n, out_idx, out_dist, out_z, keep_at_most, max_neighbours}, st);
+  return fill_long_lists(src, r1, r2, host, h.st);
 }

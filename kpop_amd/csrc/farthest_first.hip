@@ -516,45 +516,25 @@ extern "C" int kpop_farthest_first(kpop_refset *rs, uint32_t max_picks, double c
   ArenaScope scratch;
   KPOP_TRY(farthest_first_arguments(rs, max_picks, cover_radius, n_seeds, seeds, n_picks, who));
   const uint32_t r1 = rs->r1;
-  {
-    std::vector<bool> seen(r1, false);
-    for (uint32_t t = 0; t < n_seeds; ++t) {
-      if (seeds[t] >= r1) KPOP_FAIL(KPOP_ERR_INVALID, "%s: seeds[%u] = %u in a set of %u rows", who, t, seeds[t], r1);
-      if (seen[seeds[t]]) KPOP_FAIL(KPOP_ERR_INVALID, "%s: seeds[%u] = %u is a repeated seed", who, t, seeds[t]);
-      seen[seeds[t]] = true;
-    }
-  }
+  KPOP_TRY(check_distinct_rows(seeds, n_seeds, r1, who, "seeds", "seed"));
   *n_picks = 0;
   if (n_passes) *n_passes = 0;
   if (r1 == 0) return KPOP_OK;
   const uint32_t k = std::min(max_picks, r1);
-  hipStream_t st = nullptr;
-  DevBuf work, ds, dp, dr, da, dof, dd, dn;
-  KPOP_TRY(work.alloc(farthest_first_carve(nullptr, r1, k).bytes));
-  KPOP_TRY(dn.alloc(256));
-  if (n_seeds) {
-    KPOP_TRY(ds.alloc((uint64_t)n_seeds * 4));
-    KPOP_HIP(hipMemcpyAsync(ds.p, seeds, (uint64_t)n_seeds * 4, hipMemcpyHostToDevice, st));
-  }
-  if (pick && k) KPOP_TRY(dp.alloc((uint64_t)k * 4));
-  if (pick_radius && k) KPOP_TRY(dr.alloc((uint64_t)k * 8));
-  if (pick_parent && k) KPOP_TRY(da.alloc((uint64_t)k * 4));
-  if (rep_of) KPOP_TRY(dof.alloc((uint64_t)r1 * 4));
-  if (rep_dist) KPOP_TRY(dd.alloc((uint64_t)r1 * 8));
-  KPOP_TRY(farthest_first_dev(rs, max_picks, cover_radius, ds.as<uint32_t>(), n_seeds, work.p, dp.as<uint32_t>(), dr.as<double>(), da.as<uint32_t>(),
-                              dof.as<uint32_t>(), dd.as<double>(), dn.as<uint32_t>(), true, st, who));
+  HostCall h;
+  void *work = h.work(farthest_first_carve(nullptr, r1, k).bytes);
+  uint32_t *dn = h.scalars<uint32_t>();
+  const uint32_t *ds = n_seeds ? h.in(seeds, n_seeds) : nullptr;
+  uint32_t *dp = h.counted(pick, k);
+  double *dr = h.counted(pick_radius, k);
+  uint32_t *da = h.counted(pick_parent, k), *dof = h.out(rep_of, r1);
+  double *dd = h.out(rep_dist, r1);
+  KPOP_TRY(h.upload());
+  KPOP_TRY(farthest_first_dev(rs, max_picks, cover_radius, ds, n_seeds, work, dp, dr, da, dof, dd, dn, true, h.st, who));
   uint32_t counts[2] = {0, 0};
-  KPOP_HIP(hipMemcpyAsync(counts, dn.p, 8, hipMemcpyDeviceToHost, st));
-  KPOP_HIP(hipStreamSynchronize(st));
+  KPOP_TRY(h.read(counts, dn, 2));
   const uint32_t n = std::min(counts[0], k);
-  if (n) {
-    if (pick) KPOP_HIP(hipMemcpyAsync(pick, dp.p, (uint64_t)n * 4, hipMemcpyDeviceToHost, st));
-    if (pick_radius) KPOP_HIP(hipMemcpyAsync(pick_radius, dr.p, (uint64_t)n * 8, hipMemcpyDeviceToHost, st));
-    if (pick_parent) KPOP_HIP(hipMemcpyAsync(pick_parent, da.p, (uint64_t)n * 4, hipMemcpyDeviceToHost, st));
-  }
-  if (rep_of) KPOP_HIP(hipMemcpyAsync(rep_of, dof.p, (uint64_t)r1 * 4, hipMemcpyDeviceToHost, st));
-  if (rep_dist) KPOP_HIP(hipMemcpyAsync(rep_dist, dd.p, (uint64_t)r1 * 8, hipMemcpyDeviceToHost, st));
-  KPOP_HIP(hipStreamSynchronize(st));
+  KPOP_TRY(h.finish(n));
   *n_picks = n;
   if (n_passes) *n_passes = counts[1];
   return KPOP_OK;

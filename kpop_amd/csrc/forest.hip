@@ -459,32 +459,23 @@ extern "C" int kpop_spanning_forest(kpop_refset *rs, double max_distance, uint32
   const char *who = "kpop_spanning_forest";
   KPOP_TRY(refset_check_handle(rs, who));
   ArenaScope scratch;
-  if (max_distance != max_distance) KPOP_FAIL(KPOP_ERR_INVALID, "%s: the distance is not a number", who);
+  KPOP_TRY(check_distance_is_a_number(max_distance, who));
   const uint32_t r1 = rs->r1;
   if (!n_edges || (r1 > 1 && (!edge_i || !edge_j || !edge_dist))) KPOP_FAIL(KPOP_ERR_INVALID, "%s: null argument", who);
   *n_edges = 0;
   if (r1 == 0) return KPOP_OK;
-  hipStream_t st = nullptr;
   const uint64_t m = std::max(r1, 2u) - 1;
-  DevBuf work, dn, di, dj, dd, dl;
-  KPOP_TRY(work.alloc(forest_carve(nullptr, r1).bytes));
-  KPOP_TRY(dn.alloc(256));
-  KPOP_TRY(di.alloc(m * 4));
-  KPOP_TRY(dj.alloc(m * 4));
-  KPOP_TRY(dd.alloc(m * 8));
-  KPOP_TRY(dl.alloc((uint64_t)r1 * 4));
-  KPOP_TRY(forest_dev(rs, nullptr, max_distance, work.p, dn.as<uint32_t>(), di.as<uint32_t>(), dj.as<uint32_t>(), dd.as<double>(), dl.as<uint32_t>(), st, true, who));
+  HostCall h;
+  void *work = h.work(forest_carve(nullptr, r1).bytes);
+  uint32_t *dn = h.scalars<uint32_t>(), *di = h.counted(edge_i, m), *dj = h.counted(edge_j, m);
+  double *dd = h.counted(edge_dist, m);
+  uint32_t *dl = h.out(labels, r1);
+  KPOP_TRY(h.upload());
+  KPOP_TRY(forest_dev(rs, nullptr, max_distance, work, dn, di, dj, dd, dl, h.st, true, who));
   uint32_t n = 0;
-  KPOP_HIP(hipMemcpyAsync(&n, dn.p, 4, hipMemcpyDeviceToHost, st));
-  KPOP_HIP(hipStreamSynchronize(st));
+  KPOP_TRY(h.read(&n, dn, 1));
   if (n > m) KPOP_FAIL(KPOP_ERR_HIP, "%s: %u edges on %u rows", who, n, r1);  // (cannot happen: a forest)
-  if (n) {
-    KPOP_HIP(hipMemcpyAsync(edge_i, di.p, (uint64_t)n * 4, hipMemcpyDeviceToHost, st));
-    KPOP_HIP(hipMemcpyAsync(edge_j, dj.p, (uint64_t)n * 4, hipMemcpyDeviceToHost, st));
-    KPOP_HIP(hipMemcpyAsync(edge_dist, dd.p, (uint64_t)n * 8, hipMemcpyDeviceToHost, st));
-  }
-  if (labels) KPOP_HIP(hipMemcpyAsync(labels, dl.p, (uint64_t)r1 * 4, hipMemcpyDeviceToHost, st));
-  KPOP_HIP(hipStreamSynchronize(st));
+  KPOP_TRY(h.finish(n));
   *n_edges = n;
   return KPOP_OK;
 }
@@ -500,7 +491,7 @@ extern "C" int kpop_distance_spanning_forest(const double *m, uint32_t rows, uin
 extern "C" int kpop_forest_cut(uint32_t r1, uint32_t n_edges, const uint32_t *edge_i, const uint32_t *edge_j, const double *edge_dist, double T,
                                uint32_t *labels, uint32_t *n_clusters) {
   const char *who = "kpop_forest_cut";
-  if (T != T) KPOP_FAIL(KPOP_ERR_INVALID, "%s: the distance is not a number", who);
+  KPOP_TRY(check_distance_is_a_number(T, who));
   if (!n_clusters || (r1 && !labels) || (n_edges && (!edge_i || !edge_j || !edge_dist))) KPOP_FAIL(KPOP_ERR_INVALID, "%s: null argument", who);
   for (uint32_t e = 0; e < n_edges; ++e)
     if (!(edge_i[e] < edge_j[e] && edge_j[e] < r1))

@@ -526,38 +526,20 @@ extern "C" int kpop_kmedoids(kpop_refset *rs, uint32_t n_medoids, const uint32_t
   KPOP_TRY(kmedoids_arguments(rs, n_medoids, init, n_iter, who));
   if (!converged) KPOP_FAIL(KPOP_ERR_INVALID, "%s: null count", who);
   const uint32_t r1 = rs->r1, k = n_medoids;
-  {
-    std::vector<bool> seen(r1, false);
-    for (uint32_t c = 0; c < k; ++c) {
-      if (init[c] >= r1) KPOP_FAIL(KPOP_ERR_INVALID, "%s: init[%u] = %u in a set of %u rows", who, c, init[c], r1);
-      if (seen[init[c]]) KPOP_FAIL(KPOP_ERR_INVALID, "%s: init[%u] = %u is a repeated row", who, c, init[c]);
-      seen[init[c]] = true;
-    }
-  }
-  hipStream_t st = nullptr;
-  const uint64_t rows8 = (uint64_t)r1 * 8, rows4 = (uint64_t)r1 * 4, k4 = (uint64_t)k * 4, cost8 = ((uint64_t)max_iter + 1) * 8;
-  DevBuf work, di, dm, dc, dd, dow, dr, dco, dn;
-  KPOP_TRY(work.alloc(kmedoids_carve(nullptr, r1, k, max_iter).bytes));
-  KPOP_TRY(di.alloc(k4));
-  KPOP_TRY(dn.alloc(256));
-  if (medoid) KPOP_TRY(dm.alloc(k4));
-  if (class_of) KPOP_TRY(dc.alloc(rows4));
-  if (dist) KPOP_TRY(dd.alloc(rows8));
-  if (own_mean) KPOP_TRY(dow.alloc(rows8));
-  if (class_rows) KPOP_TRY(dr.alloc(k4));
-  if (cost) KPOP_TRY(dco.alloc(cost8));
-  KPOP_HIP(hipMemcpyAsync(di.p, init, k4, hipMemcpyHostToDevice, st));
-  KPOP_TRY(kmedoids_dev(rs, k, di.as<uint32_t>(), max_iter, work.p, dm.as<uint32_t>(), dc.as<uint32_t>(), dd.as<double>(), dow.as<double>(), dr.as<uint32_t>(),
-                        dco.as<double>(), dn.as<uint32_t>(), true, st, who));
+  KPOP_TRY(check_distinct_rows(init, k, r1, who, "init", "row"));
+  const uint64_t n_cost = (uint64_t)max_iter + 1;
   uint32_t counts[2] = {0, 0};
-  KPOP_HIP(hipMemcpyAsync(counts, dn.p, 8, hipMemcpyDeviceToHost, st));
-  if (medoid) KPOP_HIP(hipMemcpyAsync(medoid, dm.p, k4, hipMemcpyDeviceToHost, st));
-  if (class_of) KPOP_HIP(hipMemcpyAsync(class_of, dc.p, rows4, hipMemcpyDeviceToHost, st));
-  if (dist) KPOP_HIP(hipMemcpyAsync(dist, dd.p, rows8, hipMemcpyDeviceToHost, st));
-  if (own_mean) KPOP_HIP(hipMemcpyAsync(own_mean, dow.p, rows8, hipMemcpyDeviceToHost, st));
-  if (class_rows) KPOP_HIP(hipMemcpyAsync(class_rows, dr.p, k4, hipMemcpyDeviceToHost, st));
-  if (cost) KPOP_HIP(hipMemcpyAsync(cost, dco.p, cost8, hipMemcpyDeviceToHost, st));
-  KPOP_HIP(hipStreamSynchronize(st));
+  HostCall h;
+  void *work = h.work(kmedoids_carve(nullptr, r1, k, max_iter).bytes);
+  const uint32_t *di = h.in(init, k);
+  uint32_t *dn = h.scalars(counts, 2);
+  uint32_t *dm = h.out(medoid, k), *dc = h.out(class_of, r1);
+  double *dd = h.out(dist, r1), *dow = h.out(own_mean, r1);
+  uint32_t *dr = h.out(class_rows, k);
+  double *dco = h.out(cost, n_cost);
+  KPOP_TRY(h.upload());
+  KPOP_TRY(kmedoids_dev(rs, k, di, max_iter, work, dm, dc, dd, dow, dr, dco, dn, true, h.st, who));
+  KPOP_TRY(h.finish());
   *n_iter = counts[0];
   *converged = (int)counts[1];
   return KPOP_OK;

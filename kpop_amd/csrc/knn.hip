@@ -545,33 +545,29 @@ extern "C" int kpop_knn_vote(kpop_refset *rs, const uint32_t *class_of, uint32_t
   KPOP_TRY(knn_check_sizes(k, n_classes, who));
   const uint32_t r1 = rs->r1, D = rs->n_dims;
   if ((r1 && !class_of) || (r2 && (!out_class || !out_votes || !out_n)) || (r1 && r2 && !m2)) KPOP_FAIL(KPOP_ERR_INVALID, "%s: null argument", who);
-  for (uint32_t i = 0; i < r1; ++i)
-    if (class_of[i] >= n_classes) KPOP_FAIL(KPOP_ERR_INVALID, "%s: row %u has class %u of %u", who, i, class_of[i], n_classes);
+  KPOP_TRY(check_row_classes(class_of, r1, n_classes, false, who));
   if (r2 == 0) return KPOP_OK;
-  hipStream_t st = nullptr;
   // the query rows in chunks that keep the workspace bounded (a quarter of a GiB, or what 64 rows take)
   const uint64_t per_row = knn_carve(nullptr, 1024, k, n_classes, D, rs->normalize != 0).bytes / 1024 + (uint64_t)D * 8 + 32;
   const uint32_t chunk = (uint32_t)std::min<uint64_t>(r2, std::max<uint64_t>(64, (256ull << 20) / per_row));
-  DevBuf dc, d2, dw, ocl, ovo, on, ofd;
-  KPOP_TRY(dc.alloc((uint64_t)r1 * 4));
-  KPOP_TRY(d2.alloc((uint64_t)chunk * D * 8));
+  HostCall h;
+  const hipStream_t st = h.st;
+  const uint32_t *dc = h.in(class_of, r1);
+  double *d2 = h.dev<double>((uint64_t)chunk * D);
   // (the last chunk may be cut into more segments than a whole one: the larger of the two workspaces)
-  KPOP_TRY(dw.alloc(std::max(kpop_dev_knn_vote_workspace_bytes(rs, chunk, k, n_classes),
-                             kpop_dev_knn_vote_workspace_bytes(rs, r2 % chunk ? r2 % chunk : chunk, k, n_classes))));
-  KPOP_TRY(ocl.alloc((uint64_t)chunk * 4));
-  KPOP_TRY(ovo.alloc((uint64_t)chunk * 4));
-  KPOP_TRY(on.alloc((uint64_t)chunk * 4));
-  KPOP_TRY(ofd.alloc((uint64_t)chunk * 8));
-  if (r1) KPOP_HIP(hipMemcpyAsync(dc.p, class_of, (uint64_t)r1 * 4, hipMemcpyHostToDevice, st));
+  void *dw = h.work(std::max(kpop_dev_knn_vote_workspace_bytes(rs, chunk, k, n_classes),
+                             kpop_dev_knn_vote_workspace_bytes(rs, r2 % chunk ? r2 % chunk : chunk, k, n_classes)));
+  uint32_t *ocl = h.dev<uint32_t>(chunk), *ovo = h.dev<uint32_t>(chunk), *on = h.dev<uint32_t>(chunk);
+  double *ofd = out_first_dist ? h.dev<double>(chunk) : nullptr;
+  KPOP_TRY(h.upload());
   for (uint32_t j0 = 0; j0 < r2; j0 += chunk) {
     const uint32_t nr = std::min(chunk, r2 - j0);
-    if (r1) KPOP_HIP(hipMemcpyAsync(d2.p, m2 + (uint64_t)j0 * D, (uint64_t)nr * D * 8, hipMemcpyHostToDevice, st));
-    KPOP_TRY(knn_dev(rs, dc.as<uint32_t>(), n_classes, d2.as<double>(), nr, k, dw.p, ocl.as<uint32_t>(), ovo.as<uint32_t>(), on.as<uint32_t>(), ofd.as<double>(), st,
-                     who));
-    KPOP_HIP(hipMemcpyAsync(out_class + j0, ocl.p, (uint64_t)nr * 4, hipMemcpyDeviceToHost, st));
-    KPOP_HIP(hipMemcpyAsync(out_votes + j0, ovo.p, (uint64_t)nr * 4, hipMemcpyDeviceToHost, st));
-    KPOP_HIP(hipMemcpyAsync(out_n + j0, on.p, (uint64_t)nr * 4, hipMemcpyDeviceToHost, st));
-    if (out_first_dist) KPOP_HIP(hipMemcpyAsync(out_first_dist + j0, ofd.p, (uint64_t)nr * 8, hipMemcpyDeviceToHost, st));
+    if (r1) KPOP_HIP(hipMemcpyAsync(d2, m2 + (uint64_t)j0 * D, (uint64_t)nr * D * 8, hipMemcpyHostToDevice, st));
+    KPOP_TRY(knn_dev(rs, dc, n_classes, d2, nr, k, dw, ocl, ovo, on, ofd, st, who));
+    KPOP_HIP(hipMemcpyAsync(out_class + j0, ocl, (uint64_t)nr * 4, hipMemcpyDeviceToHost, st));
+    KPOP_HIP(hipMemcpyAsync(out_votes + j0, ovo, (uint64_t)nr * 4, hipMemcpyDeviceToHost, st));
+    KPOP_HIP(hipMemcpyAsync(out_n + j0, on, (uint64_t)nr * 4, hipMemcpyDeviceToHost, st));
+    if (ofd) KPOP_HIP(hipMemcpyAsync(out_first_dist + j0, ofd, (uint64_t)nr * 8, hipMemcpyDeviceToHost, st));
     KPOP_HIP(hipStreamSynchronize(st));
   }
   return KPOP_OK;

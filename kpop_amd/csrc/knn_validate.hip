@@ -324,9 +324,9 @@ static uint32_t knn_rows_a_call(uint32_t rows, uint32_t K, uint32_t n_classes, u
 
 // slices [n_ks][nr] of a call -> the caller's [n_ks][rows] at row j0
 template <class T>
-static int knn_slices_back(T *out, uint32_t rows, uint32_t j0, const DevBuf &from, uint32_t nr, uint32_t n_ks, hipStream_t st) {
+static int knn_slices_back(T *out, uint32_t rows, uint32_t j0, const T *from, uint32_t nr, uint32_t n_ks, hipStream_t st) {
   for (uint32_t t = 0; t < n_ks; ++t)
-    KPOP_HIP(hipMemcpyAsync(out + (uint64_t)t * rows + j0, reinterpret_cast<const T *>(from.p) + (uint64_t)t * nr, (uint64_t)nr * sizeof(T), hipMemcpyDeviceToHost, st));
+    KPOP_HIP(hipMemcpyAsync(out + (uint64_t)t * rows + j0, from + (uint64_t)t * nr, (uint64_t)nr * sizeof(T), hipMemcpyDeviceToHost, st));
   return 0;
 }
 
@@ -358,31 +358,28 @@ extern "C" int kpop_knn_ks_vote(kpop_refset *rs, const uint32_t *class_of, uint3
   KPOP_TRY(knn_check_sizes(K, n_classes, who));
   const uint32_t r1 = rs->r1, D = rs->n_dims;
   if ((r1 && !class_of) || (r2 && (!out_class || !out_votes || !out_n)) || (r1 && r2 && !m2)) KPOP_FAIL(KPOP_ERR_INVALID, "%s: null argument", who);
-  for (uint32_t i = 0; i < r1; ++i)
-    if (class_of[i] >= n_classes) KPOP_FAIL(KPOP_ERR_INVALID, "%s: row %u has class %u of %u", who, i, class_of[i], n_classes);
+  KPOP_TRY(check_row_classes(class_of, r1, n_classes, false, who));
   if (r2 == 0) return KPOP_OK;
-  hipStream_t st = nullptr;
   const uint32_t chunk = knn_rows_a_call(r2, K, n_classes, D, rs->normalize != 0, n_ks, (uint64_t)D * 8);
-  DevBuf dc, d2, dw, ocl, ovo, on, ofd;
-  KPOP_TRY(dc.alloc((uint64_t)r1 * 4));
-  KPOP_TRY(d2.alloc((uint64_t)chunk * D * 8));
+  const uint64_t slices = (uint64_t)n_ks * chunk;
+  HostCall h;
+  const hipStream_t st = h.st;
+  const uint32_t *dc = h.in(class_of, r1);
+  double *d2 = h.dev<double>((uint64_t)chunk * D);
   // (the last chunk may be cut into more segments than a whole one: the larger of the two workspaces)
-  KPOP_TRY(dw.alloc(std::max(kpop_dev_knn_ks_vote_workspace_bytes(rs, chunk, K, n_classes),
-                             kpop_dev_knn_ks_vote_workspace_bytes(rs, r2 % chunk ? r2 % chunk : chunk, K, n_classes))));
-  KPOP_TRY(ocl.alloc((uint64_t)n_ks * chunk * 4));
-  KPOP_TRY(ovo.alloc((uint64_t)n_ks * chunk * 4));
-  KPOP_TRY(on.alloc((uint64_t)n_ks * chunk * 4));
-  KPOP_TRY(ofd.alloc((uint64_t)n_ks * chunk * 8));
-  if (r1) KPOP_HIP(hipMemcpyAsync(dc.p, class_of, (uint64_t)r1 * 4, hipMemcpyHostToDevice, st));
+  void *dw = h.work(std::max(kpop_dev_knn_ks_vote_workspace_bytes(rs, chunk, K, n_classes),
+                             kpop_dev_knn_ks_vote_workspace_bytes(rs, r2 % chunk ? r2 % chunk : chunk, K, n_classes)));
+  uint32_t *ocl = h.dev<uint32_t>(slices), *ovo = h.dev<uint32_t>(slices), *on = h.dev<uint32_t>(slices);
+  double *ofd = out_first_dist ? h.dev<double>(slices) : nullptr;
+  KPOP_TRY(h.upload());
   for (uint32_t j0 = 0; j0 < r2; j0 += chunk) {
     const uint32_t nr = std::min(chunk, r2 - j0);
-    if (r1) KPOP_HIP(hipMemcpyAsync(d2.p, m2 + (uint64_t)j0 * D, (uint64_t)nr * D * 8, hipMemcpyHostToDevice, st));
-    KPOP_TRY(vote_ks_dev(rs, dc.as<uint32_t>(), n_classes, d2.as<double>(), nr, ks, n_ks, dw.p, ocl.as<uint32_t>(), ovo.as<uint32_t>(), on.as<uint32_t>(),
-                         ofd.as<double>(), st, who));
+    if (r1) KPOP_HIP(hipMemcpyAsync(d2, m2 + (uint64_t)j0 * D, (uint64_t)nr * D * 8, hipMemcpyHostToDevice, st));
+    KPOP_TRY(vote_ks_dev(rs, dc, n_classes, d2, nr, ks, n_ks, dw, ocl, ovo, on, ofd, st, who));
     KPOP_TRY(knn_slices_back(out_class, r2, j0, ocl, nr, n_ks, st));
     KPOP_TRY(knn_slices_back(out_votes, r2, j0, ovo, nr, n_ks, st));
     KPOP_TRY(knn_slices_back(out_n, r2, j0, on, nr, n_ks, st));
-    if (out_first_dist) KPOP_TRY(knn_slices_back(out_first_dist, r2, j0, ofd, nr, n_ks, st));
+    if (ofd) KPOP_TRY(knn_slices_back(out_first_dist, r2, j0, ofd, nr, n_ks, st));
     KPOP_HIP(hipStreamSynchronize(st));
   }
   return KPOP_OK;
@@ -413,36 +410,31 @@ extern "C" int kpop_knn_validate(kpop_refset *rs, const uint32_t *class_of, uint
   KPOP_TRY(knn_check_sizes(K, n_classes, who));
   const uint32_t r1 = rs->r1, D = rs->n_dims;
   if (!out_correct || (r1 && (!class_of || !out_class || !out_votes || !out_n))) KPOP_FAIL(KPOP_ERR_INVALID, "%s: null argument", who);
-  for (uint32_t i = 0; i < r1; ++i)
-    if (class_of[i] >= n_classes) KPOP_FAIL(KPOP_ERR_INVALID, "%s: row %u has class %u of %u", who, i, class_of[i], n_classes);
+  KPOP_TRY(check_row_classes(class_of, r1, n_classes, false, who));
   for (uint32_t t = 0; t < n_ks; ++t) out_correct[t] = 0;
   if (r1 == 0) return KPOP_OK;
-  hipStream_t st = nullptr;
   // the set's rows in ranges that keep the workspace bounded; the query side of a range is the set's own (divided) rows: nothing a row
   const uint32_t chunk = knn_rows_a_call(r1, K, n_classes, D, false, n_ks, 0);
-  DevBuf dc, dg, dw, ocl, ovo, on, ofd, oco;
-  KPOP_TRY(dc.alloc((uint64_t)r1 * 4));
-  if (group_of) KPOP_TRY(dg.alloc((uint64_t)r1 * 4));
+  const uint64_t slices = (uint64_t)n_ks * chunk;
+  HostCall h;
+  const hipStream_t st = h.st;
+  const uint32_t *dc = h.in(class_of, r1), *dg = group_of ? h.in(group_of, r1) : nullptr;
   // (the last range may be cut into more segments than a whole one: the larger of the two workspaces)
-  KPOP_TRY(dw.alloc(std::max(kpop_dev_knn_validate_workspace_bytes(rs, chunk, K, n_classes),
-                             kpop_dev_knn_validate_workspace_bytes(rs, r1 % chunk ? r1 % chunk : chunk, K, n_classes))));
-  KPOP_TRY(ocl.alloc((uint64_t)n_ks * chunk * 4));
-  KPOP_TRY(ovo.alloc((uint64_t)n_ks * chunk * 4));
-  KPOP_TRY(on.alloc((uint64_t)n_ks * chunk * 4));
-  KPOP_TRY(ofd.alloc((uint64_t)n_ks * chunk * 8));
-  KPOP_TRY(oco.alloc((uint64_t)kKMaxKs * 8));
-  KPOP_HIP(hipMemcpyAsync(dc.p, class_of, (uint64_t)r1 * 4, hipMemcpyHostToDevice, st));
-  if (group_of) KPOP_HIP(hipMemcpyAsync(dg.p, group_of, (uint64_t)r1 * 4, hipMemcpyHostToDevice, st));
+  void *dw = h.work(std::max(kpop_dev_knn_validate_workspace_bytes(rs, chunk, K, n_classes),
+                             kpop_dev_knn_validate_workspace_bytes(rs, r1 % chunk ? r1 % chunk : chunk, K, n_classes)));
+  uint32_t *ocl = h.dev<uint32_t>(slices), *ovo = h.dev<uint32_t>(slices), *on = h.dev<uint32_t>(slices);
+  double *ofd = out_first_dist ? h.dev<double>(slices) : nullptr;
+  uint64_t *oco = h.dev<uint64_t>(kKMaxKs);
+  KPOP_TRY(h.upload());
   for (uint32_t j0 = 0; j0 < r1; j0 += chunk) {
     const uint32_t nr = std::min(chunk, r1 - j0);
     uint64_t correct[kKMaxKs];
-    KPOP_TRY(validate_dev(rs, dc.as<uint32_t>(), n_classes, group_of ? dg.as<uint32_t>() : nullptr, j0, nr, ks, n_ks, dw.p, ocl.as<uint32_t>(), ovo.as<uint32_t>(),
-                          on.as<uint32_t>(), ofd.as<double>(), oco.as<uint64_t>(), st, who));
+    KPOP_TRY(validate_dev(rs, dc, n_classes, dg, j0, nr, ks, n_ks, dw, ocl, ovo, on, ofd, oco, st, who));
     KPOP_TRY(knn_slices_back(out_class, r1, j0, ocl, nr, n_ks, st));
     KPOP_TRY(knn_slices_back(out_votes, r1, j0, ovo, nr, n_ks, st));
     KPOP_TRY(knn_slices_back(out_n, r1, j0, on, nr, n_ks, st));
-    if (out_first_dist) KPOP_TRY(knn_slices_back(out_first_dist, r1, j0, ofd, nr, n_ks, st));
-    KPOP_HIP(hipMemcpyAsync(correct, oco.p, (uint64_t)n_ks * 8, hipMemcpyDeviceToHost, st));
+    if (ofd) KPOP_TRY(knn_slices_back(out_first_dist, r1, j0, ofd, nr, n_ks, st));
+    KPOP_HIP(hipMemcpyAsync(correct, oco, (uint64_t)n_ks * 8, hipMemcpyDeviceToHost, st));
     KPOP_HIP(hipStreamSynchronize(st));
     for (uint32_t t = 0; t < n_ks; ++t) out_correct[t] += correct[t];
   }

@@ -147,14 +147,12 @@ extern "C" int kpop_core_distances(kpop_refset *rs, uint32_t min_pts, double *co
   const uint32_t r1 = rs->r1;
   if (r1 == 0) return KPOP_OK;
   if (!core_dist) KPOP_FAIL(KPOP_ERR_INVALID, "%s: null argument", who);
-  hipStream_t st = nullptr;
-  DevBuf work, dc;
-  KPOP_TRY(work.alloc(core_workspace_bytes(r1, min_pts, rs->n_dims)));
-  KPOP_TRY(dc.alloc((uint64_t)r1 * 8));
-  KPOP_TRY(core_dev(rs, min_pts, work.p, dc.as<double>(), st));
-  KPOP_HIP(hipMemcpyAsync(core_dist, dc.p, (uint64_t)r1 * 8, hipMemcpyDeviceToHost, st));
-  KPOP_HIP(hipStreamSynchronize(st));
-  return KPOP_OK;
+  HostCall h;
+  void *work = h.work(core_workspace_bytes(r1, min_pts, rs->n_dims));
+  double *dc = h.out(core_dist, r1);
+  KPOP_TRY(h.upload());
+  KPOP_TRY(core_dev(rs, min_pts, work, dc, h.st));
+  return h.finish();
 }
 
 extern "C" uint64_t kpop_dev_reachability_tree_workspace_bytes(const kpop_refset *rs, uint32_t min_pts) {
@@ -176,35 +174,23 @@ extern "C" int kpop_reachability_tree(kpop_refset *rs, uint32_t min_pts, double 
   KPOP_TRY(refset_check_handle(rs, who));
   ArenaScope scratch;
   KPOP_TRY(reach_check_min_pts(min_pts, who));
-  if (max_distance != max_distance) KPOP_FAIL(KPOP_ERR_INVALID, "%s: the distance is not a number", who);
+  KPOP_TRY(check_distance_is_a_number(max_distance, who));
   const uint32_t r1 = rs->r1;
   if (!n_edges || (r1 > 1 && (!edge_i || !edge_j || !edge_dist))) KPOP_FAIL(KPOP_ERR_INVALID, "%s: null argument", who);
   *n_edges = 0;
   if (r1 == 0) return KPOP_OK;
-  hipStream_t st = nullptr;
   const uint64_t m = std::max(r1, 2u) - 1;
-  DevBuf work, dn, di, dj, dd, dc, dl;
-  KPOP_TRY(work.alloc(reach_carve(nullptr, r1, min_pts, rs->n_dims).bytes));
-  KPOP_TRY(dn.alloc(256));
-  KPOP_TRY(di.alloc(m * 4));
-  KPOP_TRY(dj.alloc(m * 4));
-  KPOP_TRY(dd.alloc(m * 8));
-  KPOP_TRY(dc.alloc((uint64_t)r1 * 8));
-  KPOP_TRY(dl.alloc((uint64_t)r1 * 4));
-  KPOP_TRY(reach_dev(rs, min_pts, max_distance, work.p, dn.as<uint32_t>(), di.as<uint32_t>(), dj.as<uint32_t>(), dd.as<double>(), dc.as<double>(), dl.as<uint32_t>(),
-                     st, true, who));
+  HostCall h;
+  void *work = h.work(reach_carve(nullptr, r1, min_pts, rs->n_dims).bytes);
+  uint32_t *dn = h.scalars<uint32_t>(), *di = h.counted(edge_i, m), *dj = h.counted(edge_j, m);
+  double *dd = h.counted(edge_dist, m), *dc = h.out(core_dist, r1);
+  uint32_t *dl = h.out(labels, r1);
+  KPOP_TRY(h.upload());
+  KPOP_TRY(reach_dev(rs, min_pts, max_distance, work, dn, di, dj, dd, dc, dl, h.st, true, who));
   uint32_t n = 0;
-  KPOP_HIP(hipMemcpyAsync(&n, dn.p, 4, hipMemcpyDeviceToHost, st));
-  KPOP_HIP(hipStreamSynchronize(st));
+  KPOP_TRY(h.read(&n, dn, 1));
   if (n > m) KPOP_FAIL(KPOP_ERR_HIP, "%s: %u edges on %u rows", who, n, r1);  // (cannot happen: a forest)
-  if (n) {
-    KPOP_HIP(hipMemcpyAsync(edge_i, di.p, (uint64_t)n * 4, hipMemcpyDeviceToHost, st));
-    KPOP_HIP(hipMemcpyAsync(edge_j, dj.p, (uint64_t)n * 4, hipMemcpyDeviceToHost, st));
-    KPOP_HIP(hipMemcpyAsync(edge_dist, dd.p, (uint64_t)n * 8, hipMemcpyDeviceToHost, st));
-  }
-  if (core_dist) KPOP_HIP(hipMemcpyAsync(core_dist, dc.p, (uint64_t)r1 * 8, hipMemcpyDeviceToHost, st));
-  if (labels) KPOP_HIP(hipMemcpyAsync(labels, dl.p, (uint64_t)r1 * 4, hipMemcpyDeviceToHost, st));
-  KPOP_HIP(hipStreamSynchronize(st));
+  KPOP_TRY(h.finish(n));
   *n_edges = n;
   return KPOP_OK;
 }
@@ -221,7 +207,7 @@ extern "C" int kpop_distance_reachability_tree(const double *m, uint32_t rows, u
 extern "C" int kpop_reachability_cut(uint32_t r1, uint32_t n_edges, const uint32_t *edge_i, const uint32_t *edge_j, const double *edge_dist,
                                      const double *core_dist, double T, uint32_t *labels, uint32_t *counts) {
   const char *who = "kpop_reachability_cut";
-  if (T != T) KPOP_FAIL(KPOP_ERR_INVALID, "%s: the distance is not a number", who);
+  KPOP_TRY(check_distance_is_a_number(T, who));
   if (!counts || (r1 && (!labels || !core_dist)) || (n_edges && (!edge_i || !edge_j || !edge_dist))) KPOP_FAIL(KPOP_ERR_INVALID, "%s: null argument", who);
   uint32_t n_components = 0;
   KPOP_TRY(kpop_forest_cut(r1, n_edges, edge_i, edge_j, edge_dist, T, labels, &n_components));

@@ -20,6 +20,7 @@
 
 #include "common.h"
 #include "distance_routes.h"
+#include "refset_call.h"
 #include "row_norms.h"
 
 namespace kpop {
@@ -362,17 +363,13 @@ extern "C" int kpop_refset_distance_rowwise(kpop_refset *rs, const double *m2, u
   ArenaScope scratch;
   if (rs->r1 == 0 || r2 == 0) return KPOP_OK;
   if (!m2 || !out) KPOP_FAIL(KPOP_ERR_INVALID, "kpop_refset_distance_rowwise: null argument");
-  hipStream_t st = nullptr;
-  const uint32_t D = rs->n_dims;
-  DevBuf d2, dw, dout;
-  KPOP_TRY(d2.alloc((uint64_t)r2 * D * 8));
-  KPOP_TRY(dw.alloc(kpop_dev_refset_workspace_bytes(rs, r2)));
-  KPOP_TRY(dout.alloc((uint64_t)rs->r1 * r2 * 8));
-  KPOP_HIP(hipMemcpyAsync(d2.p, m2, (uint64_t)r2 * D * 8, hipMemcpyHostToDevice, st));
-  KPOP_TRY(refset_dev_rowwise(rs, d2.as<double>(), r2, dw.p, dout.as<double>(), st));
-  KPOP_HIP(hipMemcpyAsync(out, dout.p, (uint64_t)rs->r1 * r2 * 8, hipMemcpyDeviceToHost, st));
-  KPOP_HIP(hipStreamSynchronize(st));
-  return KPOP_OK;
+  HostCall h;
+  const double *d2 = h.in(m2, (uint64_t)r2 * rs->n_dims);
+  void *dw = h.work(kpop_dev_refset_workspace_bytes(rs, r2));
+  double *dout = h.out(out, (uint64_t)rs->r1 * r2);
+  KPOP_TRY(h.upload());
+  KPOP_TRY(refset_dev_rowwise(rs, d2, r2, dw, dout, h.st));
+  return h.finish();
 }
 
 extern "C" int kpop_refset_distance_summary(kpop_refset *rs, const double *m2, uint32_t r2, uint32_t keep_at_most, uint32_t max_neighbours,
@@ -381,27 +378,13 @@ extern "C" int kpop_refset_distance_summary(kpop_refset *rs, const double *m2, u
   ArenaScope scratch;
   if (r2 == 0) return KPOP_OK;
   if (!m2 || !out_stats || !out_n) KPOP_FAIL(KPOP_ERR_INVALID, "kpop_refset_distance_summary: null argument");
-  hipStream_t st = nullptr;
-  const uint32_t D = rs->n_dims;
-  DevBuf d2, dw, ds, dn, di, dd, dz;
-  const uint64_t nn = (uint64_t)r2 * max_neighbours;
-  KPOP_TRY(d2.alloc((uint64_t)r2 * D * 8));
-  KPOP_TRY(dw.alloc(kpop_dev_refset_workspace_bytes(rs, r2)));
-  KPOP_TRY(ds.alloc((uint64_t)r2 * 4 * 8));
-  KPOP_TRY(dn.alloc((uint64_t)r2 * 4));
-  KPOP_TRY(di.alloc(nn * 4));
-  KPOP_TRY(dd.alloc(nn * 8));
-  KPOP_TRY(dz.alloc(nn * 8));
-  KPOP_HIP(hipMemcpyAsync(d2.p, m2, (uint64_t)r2 * D * 8, hipMemcpyHostToDevice, st));
-  KPOP_TRY(refset_dev_summary(rs, d2.as<double>(), r2, dw.p,
-                              SummaryOut{ds.as<double>(), dn.as<uint32_t>(), di.as<uint32_t>(), dd.as<double>(), dz.as<double>(), keep_at_most, max_neighbours}, st));
-  KPOP_HIP(hipMemcpyAsync(out_stats, ds.p, (uint64_t)r2 * 4 * 8, hipMemcpyDeviceToHost, st));
-  KPOP_HIP(hipMemcpyAsync(out_n, dn.p, (uint64_t)r2 * 4, hipMemcpyDeviceToHost, st));
-  if (nn) {
-    KPOP_HIP(hipMemcpyAsync(out_idx, di.p, nn * 4, hipMemcpyDeviceToHost, st));
-    KPOP_HIP(hipMemcpyAsync(out_dist, dd.p, nn * 8, hipMemcpyDeviceToHost, st));
-    KPOP_HIP(hipMemcpyAsync(out_z, dz.p, nn * 8, hipMemcpyDeviceToHost, st));
-  }
-  KPOP_HIP(hipStreamSynchronize(st));
-  return refset_fill_long_lists(rs, d2.as<double>(), r2, SummaryOut{out_stats, out_n, out_idx, out_dist, out_z, keep_at_most, max_neighbours}, st);
+  const SummaryOut host{out_stats, out_n, out_idx, out_dist, out_z, keep_at_most, max_neighbours};
+  HostCall h;
+  const double *d2 = h.in(m2, (uint64_t)r2 * rs->n_dims);
+  void *dw = h.work(kpop_dev_refset_workspace_bytes(rs, r2));
+  const SummaryOut dev = summary_stage(h, r2, host);
+  KPOP_TRY(h.upload());
+  KPOP_TRY(refset_dev_summary(rs, d2, r2, dw, dev, h.st));
+  KPOP_TRY(h.finish());
+  return refset_fill_long_lists(rs, d2, r2, host, h.st);
 }

@@ -1,7 +1,10 @@
-// refset_call.h -- the host side of a call on a resident set, once: what within.hip, clusters.hip, forest.hip, knn.hip,
-// knn_validate.hip, representatives.hip and dbscan.hip do around their kernels.
+// refset_call.h -- the host side of a call on a resident set, once: what within.hip, clusters.hip, representatives.hip, dbscan.hip,
+// forest.hip, reachability.hip, knn.hip, knn_validate.hip, silhouette.hip, farthest_first.hip and kmedoids.hip do around their kernels,
+// and the host-buffer forms of refset.hip with them: the set's rows as the chain reads them, the workspace carved, the one-shot form,
+// the argument checks that several entry points share, and -- host_call.h -- the device side of a host-buffer call (HostCall).
 #pragma once
 #include "common.h"
+#include "host_call.h"
 #include "refset.h"
 
 namespace kpop {
@@ -45,6 +48,33 @@ static inline int check_known_prefix(const uint32_t *x, uint32_t known_rows, con
   for (uint32_t i = 0; i < known_rows; ++i)
     if (x[i] > i || x[x[i]] != x[i])
       KPOP_FAIL(KPOP_ERR_INVALID, "%s: %s[%u] = %u is not %s this call returns (%s[i] <= i, %s[%s[i]] == %s[i])", who, name, i, x[i], noun, name, name, name, name);
+  return 0;
+}
+
+// a radius or a threshold of a host form: any number, none that is not one
+static inline int check_distance_is_a_number(double d, const char *who) {
+  if (d != d) KPOP_FAIL(KPOP_ERR_INVALID, "%s: the distance is not a number", who);
+  return 0;
+}
+
+// a class for every row of a labelled set.  or_none: KPOP_NO_CLASS is a row's class too, and leaves the row out
+static inline int check_row_classes(const uint32_t *class_of, uint32_t r1, uint32_t n_classes, bool or_none, const char *who) {
+  for (uint32_t i = 0; i < r1; ++i) {
+    if (class_of[i] < n_classes || (or_none && class_of[i] == KPOP_NO_CLASS)) continue;
+    if (or_none) KPOP_FAIL(KPOP_ERR_INVALID, "%s: row %u has class %u of %u (KPOP_NO_CLASS leaves a row out)", who, i, class_of[i], n_classes);
+    KPOP_FAIL(KPOP_ERR_INVALID, "%s: row %u has class %u of %u", who, i, class_of[i], n_classes);
+  }
+  return 0;
+}
+
+// n distinct rows of a set of r1.  name: the array's; noun: what a repeated entry is called ("seed", "row")
+static inline int check_distinct_rows(const uint32_t *x, uint32_t n, uint32_t r1, const char *who, const char *name, const char *noun) {
+  std::vector<bool> seen(r1, false);
+  for (uint32_t t = 0; t < n; ++t) {
+    if (x[t] >= r1) KPOP_FAIL(KPOP_ERR_INVALID, "%s: %s[%u] = %u in a set of %u rows", who, name, t, x[t], r1);
+    if (seen[x[t]]) KPOP_FAIL(KPOP_ERR_INVALID, "%s: %s[%u] = %u is a repeated %s", who, name, t, x[t], noun);
+    seen[x[t]] = true;
+  }
   return 0;
 }
 

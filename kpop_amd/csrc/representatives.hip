@@ -384,29 +384,23 @@ extern "C" int kpop_representatives_within(kpop_refset *rs, double max_distance,
   const char *who = "kpop_representatives_within";
   KPOP_TRY(refset_check_handle(rs, who));
   ArenaScope scratch;
-  if (max_distance != max_distance) KPOP_FAIL(KPOP_ERR_INVALID, "%s: the distance is not a number", who);
+  KPOP_TRY(check_distance_is_a_number(max_distance, who));
   if (!n_reps || (rs->r1 && !rep_of)) KPOP_FAIL(KPOP_ERR_INVALID, "%s: null argument", who);
   const uint32_t r1 = rs->r1;
   if (known_rows > r1) KPOP_FAIL(KPOP_ERR_INVALID, "%s: %u known rows in a set of %u", who, known_rows, r1);
   KPOP_TRY(check_known_prefix(rep_of, known_rows, who, "rep_of", "an entry"));
   *n_reps = 0;
   if (r1 == 0) return KPOP_OK;
-  hipStream_t st = nullptr;
-  DevBuf work, dr, dd, dn;
-  KPOP_TRY(work.alloc(representatives_carve(nullptr, r1).bytes));
-  KPOP_TRY(dr.alloc((uint64_t)r1 * 4));
-  if (rep_dist) KPOP_TRY(dd.alloc((uint64_t)r1 * 8));
-  KPOP_TRY(dn.alloc(256));
-  if (known_rows) KPOP_HIP(hipMemcpyAsync(dr.p, rep_of, (uint64_t)known_rows * 4, hipMemcpyHostToDevice, st));
-  KPOP_TRY(representatives_dev(rs, max_distance, known_rows, work.p, dr.as<uint32_t>(), rep_dist ? dd.as<double>() : nullptr, dn.as<uint32_t>(), st, who));
-  if (known_rows < r1) {  // (the known rows' entries are the caller's: neither array is written there)
-    KPOP_HIP(hipMemcpyAsync(rep_of + known_rows, dr.as<uint32_t>() + known_rows, (uint64_t)(r1 - known_rows) * 4, hipMemcpyDeviceToHost, st));
-    if (rep_dist)
-      KPOP_HIP(hipMemcpyAsync(rep_dist + known_rows, dd.as<double>() + known_rows, (uint64_t)(r1 - known_rows) * 8, hipMemcpyDeviceToHost, st));
-  }
-  KPOP_HIP(hipMemcpyAsync(n_reps, dn.p, 4, hipMemcpyDeviceToHost, st));
-  KPOP_HIP(hipStreamSynchronize(st));
-  return KPOP_OK;
+  HostCall h;
+  void *work = h.work(representatives_carve(nullptr, r1).bytes);
+  // (the known rows' entries are the caller's: neither array is written there, neither comes down there)
+  uint32_t *dr = h.out(rep_of, r1, known_rows);
+  double *dd = h.out(rep_dist, r1, known_rows);
+  uint32_t *dn = h.scalars(n_reps, 1);
+  h.up(dr, rep_of, known_rows);
+  KPOP_TRY(h.upload());
+  KPOP_TRY(representatives_dev(rs, max_distance, known_rows, work, dr, dd, dn, h.st, who));
+  return h.finish();
 }
 
 extern "C" int kpop_distance_representatives(const double *m, uint32_t rows, uint32_t n_dims, const double *metric, int kind, double p, int normalize,

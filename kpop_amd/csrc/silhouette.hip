@@ -309,35 +309,18 @@ extern "C" int kpop_silhouette(kpop_refset *rs, const uint32_t *class_of, uint32
   KPOP_TRY(silhouette_check(n_classes, who));
   const uint32_t r1 = rs->r1;
   if (r1 && !class_of) KPOP_FAIL(KPOP_ERR_INVALID, "%s: null class_of", who);
-  for (uint32_t i = 0; i < r1; ++i)
-    if (class_of[i] >= n_classes && class_of[i] != KPOP_NO_CLASS)
-      KPOP_FAIL(KPOP_ERR_INVALID, "%s: row %u has class %u of %u (KPOP_NO_CLASS leaves a row out)", who, i, class_of[i], n_classes);
-  hipStream_t st = nullptr;
-  const uint64_t rows8 = (uint64_t)r1 * 8, rows4 = (uint64_t)r1 * 4, cls8 = (uint64_t)n_classes * 8, cls4 = (uint64_t)n_classes * 4;
-  DevBuf work, dc, d_own, d_other, d_ocls, d_sil, d_rows, d_med, d_mm;
-  KPOP_TRY(work.alloc(silhouette_carve(nullptr, r1, n_classes).bytes));
-  KPOP_TRY(dc.alloc(rows4));
-  if (own_mean) KPOP_TRY(d_own.alloc(rows8));
-  if (other_mean) KPOP_TRY(d_other.alloc(rows8));
-  if (other_class) KPOP_TRY(d_ocls.alloc(rows4));
-  if (silhouette) KPOP_TRY(d_sil.alloc(rows8));
-  if (class_rows) KPOP_TRY(d_rows.alloc(cls4));
-  if (medoid) KPOP_TRY(d_med.alloc(cls4));
-  if (medoid_mean) KPOP_TRY(d_mm.alloc(cls8));
-  if (r1) KPOP_HIP(hipMemcpyAsync(dc.p, class_of, rows4, hipMemcpyHostToDevice, st));
-  KPOP_TRY(silhouette_dev(rs, dc.as<uint32_t>(), n_classes, work.p, d_own.as<double>(), d_other.as<double>(), d_ocls.as<uint32_t>(), d_sil.as<double>(),
-                          d_rows.as<uint32_t>(), d_med.as<uint32_t>(), d_mm.as<double>(), st, who));
-  if (r1) {
-    if (own_mean) KPOP_HIP(hipMemcpyAsync(own_mean, d_own.p, rows8, hipMemcpyDeviceToHost, st));
-    if (other_mean) KPOP_HIP(hipMemcpyAsync(other_mean, d_other.p, rows8, hipMemcpyDeviceToHost, st));
-    if (other_class) KPOP_HIP(hipMemcpyAsync(other_class, d_ocls.p, rows4, hipMemcpyDeviceToHost, st));
-    if (silhouette) KPOP_HIP(hipMemcpyAsync(silhouette, d_sil.p, rows8, hipMemcpyDeviceToHost, st));
-  }
-  if (class_rows) KPOP_HIP(hipMemcpyAsync(class_rows, d_rows.p, cls4, hipMemcpyDeviceToHost, st));
-  if (medoid) KPOP_HIP(hipMemcpyAsync(medoid, d_med.p, cls4, hipMemcpyDeviceToHost, st));
-  if (medoid_mean) KPOP_HIP(hipMemcpyAsync(medoid_mean, d_mm.p, cls8, hipMemcpyDeviceToHost, st));
-  KPOP_HIP(hipStreamSynchronize(st));
-  return KPOP_OK;
+  KPOP_TRY(check_row_classes(class_of, r1, n_classes, true, who));
+  HostCall h;
+  void *work = h.work(silhouette_carve(nullptr, r1, n_classes).bytes);
+  const uint32_t *dc = h.in(class_of, r1);
+  double *d_own = h.out(own_mean, r1), *d_other = h.out(other_mean, r1);
+  uint32_t *d_ocls = h.out(other_class, r1);
+  double *d_sil = h.out(silhouette, r1);
+  uint32_t *d_rows = h.out(class_rows, n_classes), *d_med = h.out(medoid, n_classes);
+  double *d_mm = h.out(medoid_mean, n_classes);
+  KPOP_TRY(h.upload());
+  KPOP_TRY(silhouette_dev(rs, dc, n_classes, work, d_own, d_other, d_ocls, d_sil, d_rows, d_med, d_mm, h.st, who));
+  return h.finish();
 }
 
 extern "C" int kpop_distance_silhouette(const double *m, uint32_t rows, uint32_t n_dims, const double *metric, int kind, double p, int normalize,
@@ -354,9 +337,7 @@ extern "C" int kpop_silhouette_summary(uint32_t r1, const uint32_t *class_of, ui
   const char *who = "kpop_silhouette_summary";
   KPOP_TRY(silhouette_check(n_classes, who));
   if (!class_mean || !overall_mean || (r1 && (!class_of || !silhouette))) KPOP_FAIL(KPOP_ERR_INVALID, "%s: null argument", who);
-  for (uint32_t i = 0; i < r1; ++i)
-    if (class_of[i] >= n_classes && class_of[i] != KPOP_NO_CLASS)
-      KPOP_FAIL(KPOP_ERR_INVALID, "%s: row %u has class %u of %u (KPOP_NO_CLASS leaves a row out)", who, i, class_of[i], n_classes);
+  KPOP_TRY(check_row_classes(class_of, r1, n_classes, true, who));
   std::vector<uint64_t> rows(n_classes, 0);
   for (uint32_t c = 0; c < n_classes; ++c) class_mean[c] = 0.0;
   double all = 0.0;

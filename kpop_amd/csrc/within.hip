@@ -335,34 +335,25 @@ extern "C" int kpop_neighbours_within(kpop_refset *rs, const double *m2, uint32_
                                       uint32_t *out_idx, double *out_dist) {
   KPOP_TRY(refset_check_handle(rs, "kpop_neighbours_within"));
   ArenaScope scratch;
-  if (max_distance != max_distance) KPOP_FAIL(KPOP_ERR_INVALID, "kpop_neighbours_within: the distance is not a number");
+  KPOP_TRY(check_distance_is_a_number(max_distance, "kpop_neighbours_within"));
   if (!out_offsets || (r2 && rs->r1 && !m2)) KPOP_FAIL(KPOP_ERR_INVALID, "kpop_neighbours_within: null argument");
   if ((out_idx == nullptr) != (out_dist == nullptr)) KPOP_FAIL(KPOP_ERR_INVALID, "kpop_neighbours_within: one of the two lists is null");
   if (!out_idx) capacity = 0;
-  hipStream_t st = nullptr;
-  const uint32_t D = rs->n_dims;
-  DevBuf d2, dw, doff, di, dd;
-  KPOP_TRY(d2.alloc((uint64_t)r2 * D * 8));
-  KPOP_TRY(dw.alloc(kpop_dev_neighbours_within_workspace_bytes(rs, r2, capacity)));
-  KPOP_TRY(doff.alloc(((uint64_t)r2 + 1) * 8));
-  KPOP_TRY(di.alloc(capacity * 4));
-  KPOP_TRY(dd.alloc(capacity * 8));
-  if (r2 && rs->r1) KPOP_HIP(hipMemcpyAsync(d2.p, m2, (uint64_t)r2 * D * 8, hipMemcpyHostToDevice, st));
-  KPOP_TRY(within_dev(rs, d2.as<double>(), r2, max_distance, capacity, dw.p, doff.as<uint64_t>(), capacity ? di.as<uint32_t>() : nullptr,
-                      capacity ? dd.as<double>() : nullptr, st));
-  KPOP_HIP(hipMemcpyAsync(out_offsets, doff.p, ((uint64_t)r2 + 1) * 8, hipMemcpyDeviceToHost, st));
-  KPOP_HIP(hipStreamSynchronize(st));
+  HostCall h;
+  const double *d2 = h.in(rs->r1 ? m2 : nullptr, (uint64_t)r2 * rs->n_dims);
+  void *dw = h.work(kpop_dev_neighbours_within_workspace_bytes(rs, r2, capacity));
+  uint64_t *doff = h.dev<uint64_t>((uint64_t)r2 + 1);
+  uint32_t *di = h.counted(out_idx, capacity);
+  double *dd = h.counted(out_dist, capacity);
+  KPOP_TRY(h.upload());
+  KPOP_TRY(within_dev(rs, d2, r2, max_distance, capacity, dw, doff, di, dd, h.st));
+  KPOP_TRY(h.read(out_offsets, doff, (uint64_t)r2 + 1));
   const uint64_t total = out_offsets[r2];
   if (!out_idx) return KPOP_OK;
   if (total > capacity)
     KPOP_FAIL(KPOP_ERR_CAPACITY, "kpop_neighbours_within: %llu neighbours, room for %llu (the offsets are complete)", (unsigned long long)total,
               (unsigned long long)capacity);
-  if (total) {
-    KPOP_HIP(hipMemcpyAsync(out_idx, di.p, total * 4, hipMemcpyDeviceToHost, st));
-    KPOP_HIP(hipMemcpyAsync(out_dist, dd.p, total * 8, hipMemcpyDeviceToHost, st));
-    KPOP_HIP(hipStreamSynchronize(st));
-  }
-  return KPOP_OK;
+  return total ? h.finish(total) : KPOP_OK;
 }
 
 extern "C" int kpop_distance_within(const double *m1, uint32_t r1, const double *m2, uint32_t r2, uint32_t n_dims, const double *metric, int kind, double p,
