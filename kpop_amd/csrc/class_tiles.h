@@ -6,7 +6,7 @@
 //                             into column tiles of at most w positions, so every column tile holds ONE class; at most r1 / w + n_classes
 //   radix_sort_pairs_u64      (radix_sort.h, 16-bit keys) the row indices grouped by class, stable: ascending inside a class
 //   silhouette_tiles_kernel   the column tiles: positions, class, whether the class ends there
-// A pass then gathers a tile's columns through the grouped order (PairStage::load_indexed).  THE SUMS over a class that both passes
+// A pass then gathers a tile's columns through the grouped order (PairRowsAt of pair_tile.h).  THE SUMS over a class that both passes
 // take: position k of the class goes to lane (k % w) / 4, a lane adds its positions ascending, the lanes meet in a fixed tree
 // (reduce_row_lanes over LaneSum) at the class's last tile -- an order that depends on r1 (the tile shape) and on the class's members
 // in ascending row order alone.
@@ -122,11 +122,15 @@ __global__ __launch_bounds__(256) void silhouette_tiles_kernel(const uint32_t *_
   }
 }
 
-// a tile as a pass reads it, held to the set: a table that was never written walks nobody out of the grouped order
-__device__ __forceinline__ SilTile silhouette_tile(const SilTile *__restrict__ tiles, uint32_t t, uint32_t n_tiles, uint32_t r1, uint32_t w) {
-  SilTile x{0u, 0u, kSilLast, 1u};
+// tile t as a pass reads it, held to the set: a table that was never written walks nobody out of the grouped order.  Beyond n_tiles
+// an empty tile, which ends the pass's walk (pair_sweep_tile in pair_tile.h; the tile after it is tile t + 1)
+struct SilStep : SilTile {
+  uint32_t t;
+};
+__device__ __forceinline__ SilStep silhouette_tile(const SilTile *__restrict__ tiles, uint32_t t, uint32_t n_tiles, uint32_t r1, uint32_t w) {
+  SilStep x{{0u, 0u, kSilLast, 1u}, t};
   if (t < n_tiles) {
-    x = tiles[t];
+    static_cast<SilTile &>(x) = tiles[t];
     x.i0 = min(x.i0, r1);
     x.i1 = min(min(x.i1, r1), x.i0 + w);
     x.i1 = max(x.i1, x.i0);

@@ -51,7 +51,8 @@ __global__ __launch_bounds__(256, 1) void clusters_tile_kernel(const double *__r
   const uint32_t ti = cg * 4, tj = rg * TY;  // (n_cg n_rg = 256 in both shapes: every thread holds pairs)
   for (uint32_t n = threadIdx.x; n < w + TJ; n += 256) s_par[n] = n;  // (the loop's barriers come before anybody unites)
   double acc[TY][4];
-  pair_tile_distances<KIND, TY, kCMaxW, kCMaxTJ>(acc, As, Bs, s_metric, a, t.i0, t.i1, a, t.j0, t.j1, n_dims, metric, p, ti, tj, true);
+  const PairRows rows{a, r1};
+  pair_tile_distances<KIND, TY, kCMaxW, kCMaxTJ>(acc, As, Bs, s_metric, rows, t.i0, t.i1, rows, t.j0, t.j1, n_dims, metric, p, ti, tj, true);
   const uint32_t mask = self_hit_mask<TY>(acc, t, ti, tj, max_distance, known_rows);
   if (!__syncthreads_or(mask != 0)) return;  // most tiles of a sparse graph
   tile_forest_unite<TY>(mask, s_par, t, w, TJ, ti, tj, parent);

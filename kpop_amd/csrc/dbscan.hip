@@ -135,7 +135,8 @@ __global__ __launch_bounds__(256, 1) void dbscan_degree_kernel(const double *__r
   const uint32_t ti = cg * 4, tj = rg * TY;
   for (uint32_t n = threadIdx.x; n < w + TJ; n += 256) s_cnt[n] = 0;  // (the loop's barriers come before anybody adds)
   double acc[TY][4];
-  pair_tile_distances<KIND, TY, kDbMaxW, kDbMaxTJ>(acc, As, Bs, s_metric, a, t.i0, t.i1, a, t.j0, t.j1, n_dims, metric, p, ti, tj, true);
+  const PairRows rows{a, r1};
+  pair_tile_distances<KIND, TY, kDbMaxW, kDbMaxTJ>(acc, As, Bs, s_metric, rows, t.i0, t.i1, rows, t.j0, t.j1, n_dims, metric, p, ti, tj, true);
   const uint32_t mask = self_hit_mask<TY>(acc, t, ti, tj, eps);
   if (!__syncthreads_or(mask != 0)) return;  // most tiles of a sparse graph
   const auto sum = [](uint32_t x, uint32_t y) { return x + y; };
@@ -200,7 +201,8 @@ __global__ __launch_bounds__(256, 1) void dbscan_union_kernel(const double *__re
   const uint32_t cg = threadIdx.x % n_cg, rg = threadIdx.x / n_cg;
   const uint32_t ti = cg * 4, tj = rg * TY;
   double acc[TY][4];
-  pair_tile_distances<KIND, TY, kDbMaxW, kDbMaxTJ>(acc, As, Bs, s_metric, a, t.i0, t.i1, a, t.j0, t.j1, n_dims, metric, p, ti, tj, true);
+  const PairRows rows{a, r1};
+  pair_tile_distances<KIND, TY, kDbMaxW, kDbMaxTJ>(acc, As, Bs, s_metric, rows, t.i0, t.i1, rows, t.j0, t.j1, n_dims, metric, p, ti, tj, true);
   const DbHits hits = dbscan_hits<TY>(acc, t, w, ti, tj, eps, s_core);
   const uint32_t mask = hits.both, mixed = hits.mixed;
   if (__syncthreads_or(mixed != 0)) {
@@ -251,7 +253,8 @@ __global__ __launch_bounds__(256, 1) void dbscan_border_kernel(const double *__r
   const uint32_t cg = threadIdx.x % n_cg, rg = threadIdx.x / n_cg;
   const uint32_t ti = cg * 4, tj = rg * TY;
   double acc[TY][4];
-  pair_tile_distances<KIND, TY, kDbMaxW, kDbMaxTJ>(acc, As, Bs, s_metric, a, t.i0, t.i1, a, t.j0, t.j1, n_dims, metric, p, ti, tj, true);
+  const PairRows rows{a, r1};
+  pair_tile_distances<KIND, TY, kDbMaxW, kDbMaxTJ>(acc, As, Bs, s_metric, rows, t.i0, t.i1, rows, t.j0, t.j1, n_dims, metric, p, ti, tj, true);
   const uint32_t mixed = dbscan_hits<TY>(acc, t, w, ti, tj, eps, s_core).mixed;
   if (!__syncthreads_or(mixed != 0)) return;
   const auto least = [](uint32_t x, uint32_t y) { return min(x, y); };

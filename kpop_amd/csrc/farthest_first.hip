@@ -13,8 +13,8 @@
 // distance as a distance_key word, 0 for a picked row: no distance's key is 0), crow[], the picks with their radii and parents, the
 // buckets, and the control words.
 //   farthest_first_pass_kernel     the rows of the set against the group, the group's rows gathered as the tile's columns (the indexed
-//                                  load of pair_tile.h: no copy of a row is kept).  A workgroup takes strips of 256 rows, strip s going to
-//                                  workgroup s mod the grid; a thread 4 picks x 8 rows, the chain of a pair in one thread, the dimensions
+//                                  row view of pair_tile.h, PairRowsAt, under pair_tile_distances: no copy of a row is kept).  A
+//                                  workgroup takes strips of 256 rows, strip s going to workgroup s mod the grid; a thread 4 picks x 8 rows, the chain of a pair in one thread, the dimensions
 //                                  ascending.  The least (key, position in the group) of a row over the row's lanes is what applying the
 //                                  group's updates in pick order leaves; it replaces the row's key iff strictly less.  A row belongs to
 //                                  BUCKET (workgroup, row mod nb) -- by stride, not by range: rows that lie together in the file
@@ -151,16 +151,8 @@ __global__ __launch_bounds__(256, 2) void farthest_first_pass_kernel(const doubl
     uint64_t mine = 0;
     if (g) {
       double acc[kFfTY][4];
-      pair_zero(acc);
-      PairStage<kFfGroup, kFfStrip> stage;
-      stage.load_indexed(a, r1, pick, start, start + g, a, j0, j1, n_dims, 0, n_dims);
-      for (uint32_t c0 = 0; c0 < n_dims; c0 += kPairDC) {
-        __syncthreads();
-        stage.store(As, Bs, s_metric, metric, c0, n_dims);
-        __syncthreads();
-        if (c0 + kPairDC < n_dims) stage.load_indexed(a, r1, pick, start, start + g, a, j0, j1, n_dims, c0 + kPairDC, n_dims);
-        pair_accumulate<KIND>(acc, As, Bs, s_metric, ti, tj, min((uint32_t)kPairDC, n_dims - c0), p);
-      }
+      pair_tile_distances<KIND, kFfTY, kFfGroup, kFfStrip>(acc, As, Bs, s_metric, PairRowsAt{a, r1, pick}, start, start + g, PairRows{a, r1}, j0, j1, n_dims,
+                                                           metric, p, ti, tj, true);
       // the epilogue: positions ascend within a thread and with the lane, so the least (key, position) is the first pick of the group
       // that brings the least distance: what the group's updates in pick order leave.  A NaN is no key
 #pragma unroll
@@ -168,7 +160,7 @@ __global__ __launch_bounds__(256, 2) void farthest_first_pass_kernel(const doubl
         KeyAt best{kFfNone, 0u};
 #pragma unroll
         for (int x = 0; x < 4; ++x) {
-          const double d = scale_distance<KIND>(acc[yy][x], p);
+          const double d = acc[yy][x];
           if (ti + x < g && d == d) {
             const uint64_t key = distance_key(d);
             if (key < best.k) best = KeyAt{key, ti + x};

@@ -140,9 +140,12 @@ __global__ __launch_bounds__(256, 1) void forest_nearest_kernel(const double *__
   uint32_t strip_lab = tile_lab[strip * kf];
   for (uint32_t q = 1; q < kf; ++q)
     if (strip * kf + q < n_ct && tile_lab[strip * kf + q] != strip_lab) strip_lab = kFMixed;
-  auto next_tile = [&](uint32_t t) {  // the first tile from t on that holds a foreign pair (the same for every thread)
+  struct Tile : PairTile {
+    uint32_t t;
+  };
+  auto tile_from = [&](uint32_t t) {  // the first tile from t on that holds a foreign pair (the same for every thread); empty at t_end
     while (t < t_end && strip_lab != kFMixed && tile_lab[t] == strip_lab) ++t;
-    return t;
+    return Tile{{t * w, t < t_end ? min(r1, t * w + w) : 0u}, t};
   };
   const uint32_t cg = threadIdx.x % n_cg, rg = threadIdx.x / n_cg;
   const bool worker = rg < n_rg;
@@ -157,27 +160,18 @@ __global__ __launch_bounds__(256, 1) void forest_nearest_kernel(const double *__
   }
   Weight wt;
   wt.rows(core, j0 + tj, j1);
+  const PairRows rows{a, r1};
   PairStage<kFMaxW, kFMaxTJ> stage;
-  uint32_t t = next_tile(t_begin);
-  if (t < t_end) stage.load(a, t * w, min(r1, t * w + w), a, j0, j1, n_dims, 0, n_dims);
-  while (t < t_end) {
-    const uint32_t t_next = next_tile(t + 1);
-    const uint32_t i0 = t * w, i1 = min(r1, i0 + w);
+  Tile cur = tile_from(t_begin), nxt;
+  for (pair_sweep_open(stage, rows, cur, rows, j0, j1, n_dims); cur.i0 < cur.i1; cur = nxt) {
+    nxt = tile_from(cur.t + 1);
+    const uint32_t i0 = cur.i0, i1 = cur.i1;
     uint32_t li[4];
 #pragma unroll
     for (int x = 0; x < 4; ++x) li[x] = (i0 + ti + x < i1) ? lab[i0 + ti + x] : 0u;
     wt.columns(core, i0 + ti, i1);
     double acc[TY][4];
-    pair_zero(acc);
-    for (uint32_t c0 = 0; c0 < n_dims; c0 += kPairDC) {
-      __syncthreads();
-      stage.store(As, Bs, s_metric, metric, c0, n_dims);
-      __syncthreads();
-      const bool more = c0 + kPairDC < n_dims;  // this tile's next dimensions, or the next tile's first
-      const uint32_t ni0 = more ? i0 : t_next * w;
-      if (more || t_next < t_end) stage.load(a, ni0, min(r1, ni0 + w), a, j0, j1, n_dims, more ? c0 + kPairDC : 0u, n_dims);
-      if (worker) pair_accumulate<KIND>(acc, As, Bs, s_metric, ti, tj, min((uint32_t)kPairDC, n_dims - c0), p);
-    }
+    pair_sweep_tile<KIND>(stage, acc, As, Bs, s_metric, rows, cur, nxt, rows, j0, j1, n_dims, metric, p, ti, tj, worker);
     // the epilogue: the pair's weight against the bound (a NaN compares false: no edge), a row of another component only
     // (which the row itself never is); columns ascend within the tile and from tile to tile, so that `below` alone keeps, among
     // equal keys, the least column
@@ -197,7 +191,6 @@ __global__ __launch_bounds__(256, 1) void forest_nearest_kernel(const double *__
           }
         }
     }
-    t = t_next;
   }
   // the least (key, column) over a row's lanes
 #pragma unroll

@@ -12,7 +12,7 @@
 // Neither the r1 x r1 matrix nor an r1 x k table is formed.  A round is a chain of launches, the launch boundary the one synchronisation:
 //   kmedoids_pos_*_kernel     pos_of[r1]: a medoid's own position, KPOP_NO_CLASS for every other row
 //   kmedoids_assign_kernel    the rows of the set against ALL k medoids in one read of the set.  farthest_first_pass_kernel's tile: a
-//                             workgroup takes strips of 256 rows, the medoids gathered as the tile's columns (PairStage::load_indexed) in
+//                             workgroup takes strips of 256 rows, the medoids gathered as the tile's columns (PairRowsAt of pair_tile.h) in
 //                             groups of 32, a thread 4 medoids x 8 rows, the chain of a pair in one thread, the dimensions ascending.  New:
 //                             the loop over the groups inside a strip -- a row's least (key, position) is carried across the groups and
 //                             written once.  Where the strips are so few that whole segments fit beside each other under two workgroups
@@ -26,7 +26,7 @@
 //   kmedoids_own_kernel       the within-class sums.  A workgroup owns TJ consecutive positions of the GROUPED order and walks the column
 //                             tiles of the classes those positions belong to, and no others: the sum of n_c^2 pairs and not r1^2 (a row
 //                             tile that spans several small classes computes their cross pairs and drops them: bounded by the tile).
-//                             Both operands gathered (PairStage::load_indexed_both).  The sum order is silhouette_pass_kernel's, position
+//                             Both operands gathered (a PairRowsAt each).  The sum order is silhouette_pass_kernel's, position
 //                             for position, so own_mean has kpop_silhouette's bits; a class's column walk is never cut
 //   kmedoids_rows_kernel, kmedoids_medoid_kernel   the two integer minima of silhouette.hip: the key of own_mean, then the row index
 //   kmedoids_update_kernel    one workgroup: M' against M; sets the done word and converged, or takes M' and counts the round
@@ -146,24 +146,19 @@ __global__ __launch_bounds__(256, 2) void kmedoids_assign_kernel(const double *_
         s_pos[tj + yy] = kSilNone;
       }
     }
+    const PairTilesOf groups{kKmGroup, min(k, g_end * kKmGroup)};  // positions in med
+    const PairRowsAt cols{a, r1, med};
+    const PairRows rows{a, r1};
     PairStage<kKmGroup, kKmStrip> stage;
-    if (g_begin < g_end) stage.load_indexed(a, r1, med, g_begin * kKmGroup, min(k, (g_begin + 1) * kKmGroup), a, j0, j1, n_dims, 0, n_dims);
-    for (uint32_t g = g_begin; g < g_end; ++g) {
-      const uint32_t i0 = g * kKmGroup, i1 = min(k, i0 + kKmGroup);
+    PairTile cur = groups.at(g_begin * kKmGroup), nxt;
+    for (pair_sweep_open(stage, cols, cur, rows, j0, j1, n_dims); cur.i0 < cur.i1; cur = nxt) {
+      nxt = groups.after(cur);
+      const uint32_t i0 = cur.i0, i1 = cur.i1;
       uint32_t mrow[4];
 #pragma unroll
       for (int x = 0; x < 4; ++x) mrow[x] = (i0 + ti + x < i1) ? min(med[i0 + ti + x], r1 - 1) : kSilNone;
       double acc[kKmTY][4];
-      pair_zero(acc);
-      for (uint32_t c0 = 0; c0 < n_dims; c0 += kPairDC) {
-        __syncthreads();
-        stage.store(As, Bs, s_metric, metric, c0, n_dims);
-        __syncthreads();
-        // this group's next dimensions, or the next group's first
-        if (c0 + kPairDC < n_dims) stage.load_indexed(a, r1, med, i0, i1, a, j0, j1, n_dims, c0 + kPairDC, n_dims);
-        else if (g + 1 < g_end) stage.load_indexed(a, r1, med, i1, min(k, i1 + kKmGroup), a, j0, j1, n_dims, 0, n_dims);
-        pair_accumulate<KIND>(acc, As, Bs, s_metric, ti, tj, min((uint32_t)kPairDC, n_dims - c0), p);
-      }
+      pair_sweep_tile<KIND>(stage, acc, As, Bs, s_metric, cols, cur, nxt, rows, j0, j1, n_dims, metric, p, ti, tj, true);
       // positions ascend within a thread, with the lane and from group to group: the least (key, position) of the group, and `<` on
       // the key alone against the groups before, keep among equal distances the first medoid.  A NaN is no key; the row itself is no pair
 #pragma unroll
@@ -267,7 +262,7 @@ __global__ __launch_bounds__(256, 1) void kmedoids_own_kernel(const double *__re
   __shared__ __attribute__((aligned(16))) double As[kPairDC][kSilMaxW + 2];
   __shared__ __attribute__((aligned(16))) double Bs[kPairDC][kSilMaxTJ + 2];
   __shared__ double s_metric[kPairDC];
-  __shared__ uint32_t s_row[kSilMaxTJ], s_cls[kSilMaxTJ];  // the tile's rows and their classes (the loop's barriers come before anybody reads)
+  __shared__ uint32_t s_row[kSilMaxTJ], s_cls[kSilMaxTJ];  // the tile's rows and their classes
   if (words[kKmDone]) return;
   const uint32_t TJ = TY * n_rg;
   const uint32_t q0 = blockIdx.x * TJ, n_in = min(start[k], r1);
@@ -283,31 +278,25 @@ __global__ __launch_bounds__(256, 1) void kmedoids_own_kernel(const double *__re
     s_row[n] = row;
     s_cls[n] = row != kSilNone ? min(lab[row], k) : k;
   }
+  __syncthreads();  // (s_row is the strip's index list: the first load reads it)
   double run[TY], own[TY];
   uint32_t own_seen = 0;  // bit yy: the row's class has been walked
 #pragma unroll
   for (int yy = 0; yy < TY; ++yy) run[yy] = own[yy] = 0.0;
   const auto sum = [](LaneSum x, LaneSum y) { return LaneSum{__dadd_rn(x.v, y.v)}; };
+  // both operands gathered.  The strip's rows do not change from step to step: their numbers come from s_row, positions 0 .. q1 - q0, an
+  // LDS read in front of each row's load where the grouped order would be a trip to memory (profiles/pair_sweep_refactor.md, section 4)
+  const PairRowsAt cols{a, r1, perm}, strip{a, r1, s_row};
+  const uint32_t n_strip = q1 - q0;
   PairStage<kSilMaxW, kSilMaxTJ> stage;
-  SilTile next = silhouette_tile(tiles, t_begin, t_end, r1, w);
-  if (t_begin < t_end) stage.load_indexed_both(a, r1, perm, next.i0, next.i1, a, r1, perm, q0, q1, n_dims, 0, n_dims);
-  for (uint32_t t = t_begin; t < t_end; ++t) {
-    const SilTile cur = next;
-    next = silhouette_tile(tiles, t + 1, t_end, r1, w);
+  SilStep cur = silhouette_tile(tiles, t_begin, t_end, r1, w), nxt;
+  for (pair_sweep_open(stage, cols, cur, strip, 0u, n_strip, n_dims); cur.i0 < cur.i1; cur = nxt) {
+    nxt = silhouette_tile(tiles, cur.t + 1, t_end, r1, w);
     uint32_t ri[4];
 #pragma unroll
     for (int x = 0; x < 4; ++x) ri[x] = (cur.i0 + ti + x < cur.i1) ? perm[cur.i0 + ti + x] : kSilNone;
     double acc[TY][4];
-    pair_zero(acc);
-    for (uint32_t c0 = 0; c0 < n_dims; c0 += kPairDC) {
-      __syncthreads();
-      stage.store(As, Bs, s_metric, metric, c0, n_dims);
-      __syncthreads();
-      const bool more = c0 + kPairDC < n_dims;  // this tile's next dimensions, or the next tile's first
-      if (more) stage.load_indexed_both(a, r1, perm, cur.i0, cur.i1, a, r1, perm, q0, q1, n_dims, c0 + kPairDC, n_dims);
-      else if (t + 1 < t_end) stage.load_indexed_both(a, r1, perm, next.i0, next.i1, a, r1, perm, q0, q1, n_dims, 0, n_dims);
-      pair_accumulate<KIND>(acc, As, Bs, s_metric, ti, tj, min((uint32_t)kPairDC, n_dims - c0), p);
-    }
+    pair_sweep_tile<KIND>(stage, acc, As, Bs, s_metric, cols, cur, nxt, strip, 0u, n_strip, n_dims, metric, p, ti, tj, true);
     // silhouette_pass_kernel's sum, operation for operation: the columns ascending, the row itself and a column beyond the tile add +0
 #pragma unroll
     for (int yy = 0; yy < TY; ++yy) {

@@ -44,34 +44,9 @@
 namespace kpop {
 
 // (a row's list and its insertion, the shapes, the workspace and the limits: knn_lists.h, shared with knn_validate.hip)
-// The tile loop (pair_tile.h).  a: the set's rows, b: the query rows, both as the chain reads them (divided by their rows' norms when
-// the set normalises).  The workgroup's rows j0 .. j1 (at most TJ), its column tiles t_begin .. t_end of W rows of the set each; no
-// thread is idle.  The next step's operands -- the tile's next 16 dimensions, or the first of the next tile -- are loaded under the
-// arithmetic.  epi(i0, i1, acc): what to do with a tile's finished sums.
-template <int KIND, int TY, int W, class Epi>
-__device__ __forceinline__ void knn_tiles(const double *__restrict__ a, uint32_t r1, const double *__restrict__ b, uint32_t j0, uint32_t j1, uint32_t n_dims,
-                                          const double *__restrict__ metric, double p, uint32_t t_begin, uint32_t t_end, double (*As)[W + 2],
-                                          double (*Bs)[KnnShape<TY, W>::TJ + 2], double *s_metric, Epi &&epi) {
-  using S = KnnShape<TY, W>;
-  const uint32_t ti = (threadIdx.x % S::NCG) * 4, tj = (threadIdx.x / S::NCG) * TY;
-  PairStage<W, S::TJ> stage;
-  if (t_begin < t_end) stage.load(a, t_begin * W, min(r1, t_begin * W + W), b, j0, j1, n_dims, 0, n_dims);
-  for (uint32_t t = t_begin; t < t_end; ++t) {
-    const uint32_t i0 = t * W, i1 = min(r1, i0 + W);
-    double acc[TY][4];
-    pair_zero(acc);
-    for (uint32_t c0 = 0; c0 < n_dims; c0 += kPairDC) {
-      __syncthreads();
-      stage.store(As, Bs, s_metric, metric, c0, n_dims);
-      __syncthreads();
-      const bool more = c0 + kPairDC < n_dims;  // this tile's next dimensions, or the next tile's first
-      const uint32_t ni0 = more ? i0 : i0 + W;
-      if (more || t + 1 < t_end) stage.load(a, ni0, min(r1, ni0 + W), b, j0, j1, n_dims, more ? c0 + kPairDC : 0u, n_dims);
-      pair_accumulate<KIND>(acc, As, Bs, s_metric, ti, tj, min((uint32_t)kPairDC, n_dims - c0), p);
-    }
-    epi(i0, i1, acc);
-  }
-}
+// The two kernels over the pairs walk their tiles with the sweep of pair_tile.h.  a: the set's rows, b: the query rows, both as the chain
+// reads them (divided by their rows' norms when the set normalises).  A workgroup's rows j0 .. j1 (at most TJ), its column tiles
+// t_begin .. t_end of W rows of the set each; no thread is idle.
 
 // Who is left out of a row's list.  The vote: nobody -- every call folds away.  The validation (knn_validate.hip), whose query rows are
 // rows of the set: row j itself, or every row of j's group.  A thread knows its rows' groups (or their indices in the set) for the
@@ -132,7 +107,12 @@ __global__ __launch_bounds__(256, 1) void knn_nearest_kernel(const double *__res
   const uint32_t ti = (threadIdx.x % S::NCG) * 4, tj = (threadIdx.x / S::NCG) * TY;  // (the rows of a wavefront: TJ / 4 in a row, nobody else's)
   Who out;
   out.rows(group_of, first_row + j0 + tj, r1);
-  knn_tiles<KIND, TY, W>(a, r1, b, j0, j1, n_dims, metric, p, t_begin, t_end, As, Bs, s_metric, [&](uint32_t i0, uint32_t i1, double(&acc)[TY][4]) {
+  const PairTilesOf tiles{W, min(r1, t_end * W)};
+  const PairRows set{a, r1}, query{b, r2};
+  PairStage<W, TJ> stage;
+  // (a function of its own and not the loop's text: written into the loop the insertion's compares come out if-converted otherwise and
+  // the vote and the validation ran 1.5 to 2 % slower, profiles/pair_sweep_refactor.md, section 4)
+  const auto epilogue = [&](uint32_t i0, uint32_t i1, double(&acc)[TY][4]) {
     out.columns(i0 + ti, i1);
     // the rows' bounds as the step before left them (a row is this wavefront's alone): read again after every step that inserted
     uint64_t bound[TY];
@@ -173,7 +153,14 @@ __global__ __launch_bounds__(256, 1) void knn_nearest_kernel(const double *__res
         if (inserted) bounds();
       }
     }
-  });
+  };
+  PairTile cur = tiles.at(t_begin * W), nxt;
+  for (pair_sweep_open(stage, set, cur, query, j0, j1, n_dims); cur.i0 < cur.i1; cur = nxt) {
+    nxt = tiles.after(cur);
+    double acc[TY][4];
+    pair_sweep_tile<KIND>(stage, acc, As, Bs, s_metric, set, cur, nxt, query, j0, j1, n_dims, metric, p, ti, tj, true);
+    epilogue(cur.i0, cur.i1, acc);
+  }
   __syncthreads();
   const uint32_t seg = blockIdx.y;
   for (uint32_t e = threadIdx.x; e < TJ * k; e += 256) {
@@ -300,7 +287,15 @@ __global__ __launch_bounds__(256, 1) void knn_ties_kernel(const double *__restri
   }
   Who out;
   out.rows(group_of, first_row + j0 + tj, r1);
-  knn_tiles<KIND, TY, W>(a, r1, b, j0, j1, n_dims, metric, p, t_begin, t_end, As, Bs, s_metric, [&](uint32_t i0, uint32_t i1, double(&acc)[TY][4]) {
+  const PairTilesOf tiles{W, min(r1, t_end * W)};
+  const PairRows set{a, r1}, query{b, r2};
+  PairStage<W, TJ> stage;
+  PairTile cur = tiles.at(t_begin * W), nxt;
+  for (pair_sweep_open(stage, set, cur, query, j0, j1, n_dims); cur.i0 < cur.i1; cur = nxt) {
+    nxt = tiles.after(cur);
+    double acc[TY][4];
+    pair_sweep_tile<KIND>(stage, acc, As, Bs, s_metric, set, cur, nxt, query, j0, j1, n_dims, metric, p, ti, tj, true);
+    const uint32_t i0 = cur.i0, i1 = cur.i1;
     out.columns(i0 + ti, i1);
 #pragma unroll
     for (int yy = 0; yy < TY; ++yy) {
@@ -320,7 +315,7 @@ __global__ __launch_bounds__(256, 1) void knn_ties_kernel(const double *__restri
         }
       }
     }
-  });
+  }
 }
 
 // a block of 64 (one wavefront) a row

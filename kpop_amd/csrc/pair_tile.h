@@ -1,6 +1,6 @@
 // pair_tile.h -- the f64 pair tile of the vector pipe, once: the loop that every kernel computing the reference chain's distances
-// of a tile of pairs is built on (within.hip, clusters.hip, forest.hip, knn.hip, representatives.hip, dbscan.hip;
-// distance_rowwise_kernel keeps the form it was written in, see distance.hip).  What the self-joins share around it: self_tile.h.
+// of a tile of pairs is built on (distance_rowwise_kernel keeps the form it was written in, see distance.hip).  What the
+// self-joins share around it: self_tile.h.
 //
 //   A workgroup of 256 threads owns columns i0 .. i1 (rows of the first operand) x rows j0 .. j1 (rows of the second); a thread
 //   4 columns x TY rows.  The chain of a pair (lib/Space.ml:192-200 with the adaptors of lib/Matrix.ml:243-250) is ONE thread's,
@@ -8,15 +8,28 @@
 //   bit, to what kpop_refset_distance_rowwise writes: the order of the operations in pair_accumulate is the contract, and this
 //   is the one place where it is written down.
 //   The dimensions go through LDS kPairDC at a time, [dimension][row]: a thread's 4 columns are one 32-byte read.  Staging is
-//   software-pipelined through registers.  A step of a kernel's loop:
+//   software-pipelined through registers.  A step:
 //       __syncthreads();                       the step before has been read
 //       stage.store(As, Bs, s_metric, ...);    what was loaded under the step before
 //       __syncthreads();
-//       stage.load(...);                       the next step's operands -- this tile's next dimensions, or the next tile's
-//                                              first -- issued before the arithmetic, landing behind it
+//       stage.load(...);                       the next step's operands, issued before the arithmetic, landing behind it
 //       if (worker) pair_accumulate(...);
-//   The tile's choice, the barriers, the LDS arrays and the epilogue are the kernel's; a kernel that computes one tile takes the
-//   whole loop as pair_tile_distances.
+//   An operand is a ROW VIEW: PairRows, position pos of a tile is row pos of the matrix, or PairRowsAt, it is row idx[pos] --
+//   gathered rows, of which no compacted copy is kept.  PairStage::load takes one view an operand; the staging, and so store and
+//   the arithmetic, do not know which.
+//   The steps are written out twice:
+//     pair_tile_distances  ONE tile, scaled: clusters.hip, dbscan.hip, representatives_hits_kernel; farthest_first_pass_kernel
+//                          (its columns the picks of a group, gathered)
+//     pair_sweep_tile      a strip of rows j0 .. j1 against a SEQUENCE of column tiles, the first 16 dimensions of the next tile
+//                          loaded under the last step of the current one: knn.hip (knn_nearest_kernel, knn_ties_kernel, and
+//                          knn_validate.hip through them), forest_nearest_kernel (reachability.hip through it),
+//                          silhouette_pass_kernel, kmedoids_assign_kernel, kmedoids_own_kernel.
+//                          The LDS arrays, the sequence, what is read at a tile's start and the epilogue are the kernel's
+//   within_tile_kernel writes the one-tile steps out itself and representatives_cover_kernel the sweep's (each says why).
+//   ONE CALL OF load A STEP.  In the sweep the next step's operands are this tile's next dimensions or the next tile's first:
+//   the tile and the dimension are chosen first, then load is called once.  Written as two calls -- if (more dimensions)
+//   load(this tile) else if (more tiles) load(next tile) -- the compiler keeps two copies of the loads, which cost
+//   forest_nearest_kernel 28 to 30 VGPRs and a wave a SIMD (profiles/pair_tile_refactor.md, section 1).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -27,6 +40,21 @@ namespace kpop {
 
 constexpr int kPairDC = 16;  // dimensions a step
 
+// The rows of an operand, by position.  m: the matrix as the chain reads it; rows: its rows.  The plain view reads neither rows
+// nor an index: it costs what a pointer costs
+struct PairRows {
+  const double *__restrict__ m;
+  uint32_t rows;
+  __device__ __forceinline__ uint32_t row(uint32_t pos) const { return pos; }
+};
+// position pos is row idx[pos].  An index is held below rows: a list that was never written cannot lead a load out of m
+struct PairRowsAt {
+  const double *__restrict__ m;
+  uint32_t rows;
+  const uint32_t *__restrict__ idx;
+  __device__ __forceinline__ uint32_t row(uint32_t pos) const { return min(idx[pos], rows - 1); }
+};
+
 // What a thread holds of the next step's operands.  MAXW, MAXTJ: the columns and rows the kernel's LDS arrays have room for;
 // thread t stages dimension t % 16 of rows t / 16, t / 16 + 16, ...  (Nothing but the operands lives here: the indices are
 // recomputed from threadIdx.x where they are used, which costs no register across the arithmetic.)
@@ -35,58 +63,22 @@ struct PairStage {
   static constexpr int NA = MAXW * kPairDC / 256, NB = MAXTJ * kPairDC / 256;
   double ra[NA], rb[NB];
 
-  // dimensions c0 .. c0 + 16 of columns i0 .. i1 of a and rows j0 .. j1 of b (i1 - i0 <= MAXW, j1 - j0 <= MAXTJ); zeroes beyond
+  // dimensions c0 .. c0 + 16 of positions i0 .. i1 of a and j0 .. j1 of b (i1 - i0 <= MAXW, j1 - j0 <= MAXTJ); zeroes beyond
   // a tile's edge and beyond d_end, the end of the dimensions that the workgroup walks
-  __device__ __forceinline__ void load(const double *__restrict__ a, uint32_t i0, uint32_t i1, const double *__restrict__ b, uint32_t j0, uint32_t j1,
-                                       uint32_t n_dims, uint32_t c0, uint32_t d_end) {
+  template <class A, class B>
+  __device__ __forceinline__ void load(const A &a, uint32_t i0, uint32_t i1, const B &b, uint32_t j0, uint32_t j1, uint32_t n_dims, uint32_t c0,
+                                       uint32_t d_end) {
     const uint32_t sc = threadIdx.x % kPairDC, rbase = threadIdx.x / kPairDC;
     const bool cok = c0 + sc < d_end;
 #pragma unroll
     for (int q = 0; q < NA; ++q) {
       const uint32_t row = rbase + q * 16;
-      ra[q] = (cok && i0 + row < i1) ? a[(uint64_t)(i0 + row) * n_dims + c0 + sc] : 0.0;
+      ra[q] = (cok && i0 + row < i1) ? a.m[(uint64_t)a.row(i0 + row) * n_dims + c0 + sc] : 0.0;
     }
 #pragma unroll
     for (int q = 0; q < NB; ++q) {
       const uint32_t row = rbase + q * 16;
-      rb[q] = (cok && j0 + row < j1) ? b[(uint64_t)(j0 + row) * n_dims + c0 + sc] : 0.0;
-    }
-  }
-
-  // load, the columns gathered: column i0 + k of the tile is row idx[i0 + k] of a, i0 .. i1 positions in the index list (an index
-  // is held below a_rows, the rows of a: a list that was never written cannot lead a load out of a); the rows of b as in load.  The
-  // staging, and so store and the arithmetic, are the same
-  __device__ __forceinline__ void load_indexed(const double *__restrict__ a, uint32_t a_rows, const uint32_t *__restrict__ idx, uint32_t i0, uint32_t i1,
-                                               const double *__restrict__ b, uint32_t j0, uint32_t j1, uint32_t n_dims, uint32_t c0, uint32_t d_end) {
-    const uint32_t sc = threadIdx.x % kPairDC, rbase = threadIdx.x / kPairDC;
-    const bool cok = c0 + sc < d_end;
-#pragma unroll
-    for (int q = 0; q < NA; ++q) {
-      const uint32_t row = rbase + q * 16;
-      ra[q] = (cok && i0 + row < i1) ? a[(uint64_t)min(idx[i0 + row], a_rows - 1) * n_dims + c0 + sc] : 0.0;
-    }
-#pragma unroll
-    for (int q = 0; q < NB; ++q) {
-      const uint32_t row = rbase + q * 16;
-      rb[q] = (cok && j0 + row < j1) ? b[(uint64_t)(j0 + row) * n_dims + c0 + sc] : 0.0;
-    }
-  }
-
-  // load_indexed, the rows gathered as well: row j0 + k of the tile is row jdx[j0 + k] of b, held below b_rows
-  __device__ __forceinline__ void load_indexed_both(const double *__restrict__ a, uint32_t a_rows, const uint32_t *__restrict__ idx, uint32_t i0, uint32_t i1,
-                                                    const double *__restrict__ b, uint32_t b_rows, const uint32_t *__restrict__ jdx, uint32_t j0, uint32_t j1,
-                                                    uint32_t n_dims, uint32_t c0, uint32_t d_end) {
-    const uint32_t sc = threadIdx.x % kPairDC, rbase = threadIdx.x / kPairDC;
-    const bool cok = c0 + sc < d_end;
-#pragma unroll
-    for (int q = 0; q < NA; ++q) {
-      const uint32_t row = rbase + q * 16;
-      ra[q] = (cok && i0 + row < i1) ? a[(uint64_t)min(idx[i0 + row], a_rows - 1) * n_dims + c0 + sc] : 0.0;
-    }
-#pragma unroll
-    for (int q = 0; q < NB; ++q) {
-      const uint32_t row = rbase + q * 16;
-      rb[q] = (cok && j0 + row < j1) ? b[(uint64_t)min(jdx[j0 + row], b_rows - 1) * n_dims + c0 + sc] : 0.0;
+      rb[q] = (cok && j0 + row < j1) ? b.m[(uint64_t)b.row(j0 + row) * n_dims + c0 + sc] : 0.0;
     }
   }
 
@@ -132,14 +124,13 @@ __device__ __forceinline__ void pair_accumulate(double (&acc)[TY][4], double (*A
   }
 }
 
-// the kernels that compute ONE tile: the distances of columns i0 .. i1 of a x rows j0 .. j1 of b, the steps above over all the
+// the kernels that compute ONE tile: the distances of positions i0 .. i1 of a x j0 .. j1 of b, the steps above over all the
 // dimensions, then the scaling.  worker: the thread holds pairs (a literal `true` where the tile's shape says so costs nothing);
 // every thread stages and meets the barriers
-template <int KIND, int TY, int MAXW, int MAXTJ>
-__device__ __forceinline__ void pair_tile_distances(double (&acc)[TY][4], double (*As)[MAXW + 2], double (*Bs)[MAXTJ + 2], double *s_metric,
-                                                    const double *__restrict__ a, uint32_t i0, uint32_t i1, const double *__restrict__ b, uint32_t j0,
-                                                    uint32_t j1, uint32_t n_dims, const double *__restrict__ metric, double p, uint32_t ti, uint32_t tj,
-                                                    bool worker) {
+template <int KIND, int TY, int MAXW, int MAXTJ, class A, class B>
+__device__ __forceinline__ void pair_tile_distances(double (&acc)[TY][4], double (*As)[MAXW + 2], double (*Bs)[MAXTJ + 2], double *s_metric, const A &a,
+                                                    uint32_t i0, uint32_t i1, const B &b, uint32_t j0, uint32_t j1, uint32_t n_dims,
+                                                    const double *__restrict__ metric, double p, uint32_t ti, uint32_t tj, bool worker) {
   pair_zero(acc);
   PairStage<MAXW, MAXTJ> stage;
   stage.load(a, i0, i1, b, j0, j1, n_dims, 0, n_dims);
@@ -155,6 +146,59 @@ __device__ __forceinline__ void pair_tile_distances(double (&acc)[TY][4], double
     for (int yy = 0; yy < TY; ++yy)
 #pragma unroll
       for (int x = 0; x < 4; ++x) acc[yy][x] = scale_distance<KIND>(acc[yy][x], p);
+  }
+}
+
+// A column tile of a sweep: positions i0 .. i1 of the first operand.  A kernel's own tile type may carry more (its number, its
+// class); an EMPTY range, i0 >= i1, is the end of the sequence
+struct PairTile {
+  uint32_t i0, i1;
+};
+// the plainest sequence: tiles of w positions up to `end`, the last one ragged.  (after: the start is i0 + w and not i1, so that
+// what the compiler knows of the first start's low bits holds for every start; behind the tile that reaches `end` comes an
+// empty one whatever the sums do at 2^32)
+struct PairTilesOf {
+  uint32_t w, end;
+  __device__ __forceinline__ PairTile at(uint32_t i0) const { return PairTile{i0, min(end, i0 + w)}; }
+  __device__ __forceinline__ PairTile after(const PairTile &t) const { return PairTile{t.i0 + w, t.i1 < end ? min(end, t.i0 + w + w) : 0u}; }
+};
+
+// the kernels that walk MANY tiles against one strip of rows j0 .. j1 of b.  The kernel keeps the loop over its tiles, what it
+// reads of a tile's columns and its epilogue; the pipelined steps of a tile are here:
+//     PairStage<MAXW, MAXTJ> stage;
+//     Tile cur = the first tile, nxt;
+//     for (pair_sweep_open(stage, a, cur, b, j0, j1, n_dims); cur.i0 < cur.i1; cur = nxt) {
+//       nxt = the tile after cur             (FIRST: it is needed under this tile's last step, and a `continue` below goes to it)
+//       ...                                  the tile's column data, read in front of the arithmetic
+//       double acc[TY][4];
+//       pair_sweep_tile<KIND>(stage, acc, As, Bs, s_metric, a, cur, nxt, b, j0, j1, n_dims, metric, p, ti, tj, worker);
+//       ...                                  the epilogue, over the UNSCALED sums of the tile
+//     }
+// "No more tiles" -- an empty nxt -- must be the same for every thread of the workgroup, which meets the barriers together.
+// worker as above.  (The tile loop and the epilogue are the kernel's text, not callables of a shared function, and the sweep's
+// state is the kernel's variables, not a struct's members, on evidence: profiles/pair_sweep_refactor.md, section 1.)
+
+// in front of the loop: the first tile's first dimensions
+template <int MAXW, int MAXTJ, class A, class B, class Tile>
+__device__ __forceinline__ void pair_sweep_open(PairStage<MAXW, MAXTJ> &stage, const A &a, const Tile &first, const B &b, uint32_t j0, uint32_t j1,
+                                                uint32_t n_dims) {
+  if (first.i0 < first.i1) stage.load(a, first.i0, first.i1, b, j0, j1, n_dims, 0, n_dims);
+}
+// the steps of tile cur over all the dimensions; under the last of them the first dimensions of nxt.  One call of load a step,
+// its tile and dimension chosen first (the header says why)
+template <int KIND, int TY, int MAXW, int MAXTJ, class A, class B, class Tile>
+__device__ __forceinline__ void pair_sweep_tile(PairStage<MAXW, MAXTJ> &stage, double (&acc)[TY][4], double (*As)[MAXW + 2], double (*Bs)[MAXTJ + 2],
+                                                double *s_metric, const A &a, const Tile &cur, const Tile &nxt, const B &b, uint32_t j0, uint32_t j1,
+                                                uint32_t n_dims, const double *__restrict__ metric, double p, uint32_t ti, uint32_t tj, bool worker) {
+  pair_zero(acc);
+  for (uint32_t c0 = 0; c0 < n_dims; c0 += kPairDC) {
+    __syncthreads();
+    stage.store(As, Bs, s_metric, metric, c0, n_dims);
+    __syncthreads();
+    const bool more = c0 + kPairDC < n_dims;  // this tile's next dimensions, or the next tile's first
+    const uint32_t ni0 = more ? cur.i0 : nxt.i0, ni1 = more ? cur.i1 : nxt.i1;
+    if (more || nxt.i0 < nxt.i1) stage.load(a, ni0, ni1, b, j0, j1, n_dims, more ? c0 + kPairDC : 0u, n_dims);
+    if (worker) pair_accumulate<KIND>(acc, As, Bs, s_metric, ti, tj, min((uint32_t)kPairDC, n_dims - c0), p);
   }
 }
 

@@ -14,7 +14,7 @@
 //                                   A workgroup owns a strip of rows (the self-join's tile shapes, tri_tile.h) and a segment of
 //                                   the column tiles, every thread keeps the best (key, position in reps) of its rows, the lanes of a
 //                                   row reduce with shuffles (self_tile.h), one store a row and segment.  The columns are gathered rows: the
-//                                   indexed load of pair_tile.h -- no compacted copy of the representatives' rows is kept.
+//                                   indexed row view of pair_tile.h (PairRowsAt) -- no compacted copy of the representatives' rows is kept.
 //                                   Positions ascend with the row index, so (key, position) orders as (d, r)
 //   representatives_row_min_kernel  the least of a row's segments; key none: not covered
 //   representatives_hits_kernel     a tile's distances and compare (self_tile.h) over the lower triangle of the step's rows against themselves,
@@ -103,7 +103,7 @@ __global__ __launch_bounds__(256) void representatives_alone_kernel(uint32_t kno
 // blockIdx.x: rows j0 .. j0 + TJ of the step js .. je, TJ = TY n_rg; segment blockIdx.y of gridDim.y: its share of the column tiles,
 // w positions of reps[lo .. hi) each -- lo = 0, hi = n_reps (newer = 0: the representatives before the step), or lo = the count
 // before the step's resolve, hi = n_reps (newer = 1: those the step chose, of which only the ones below a row are eligible to it).
-// A thread 4 columns x TY rows, the dimensions ascending in one thread, 16 at a time through LDS: the many-tile step of pair_tile.h.
+// A thread 4 columns x TY rows, the dimensions ascending in one thread, 16 at a time through LDS: the steps of pair_tile.h's sweep.
 template <int KIND, int TY>
 __global__ __launch_bounds__(256, 1) void representatives_cover_kernel(const double *__restrict__ a, uint32_t cap, uint32_t w, uint32_t n_dims,
                                                                        const double *__restrict__ metric, double p, double max_distance, uint32_t n_cg,
@@ -132,8 +132,12 @@ __global__ __launch_bounds__(256, 1) void representatives_cover_kernel(const dou
     best_k[yy] = kRepNone;
     best_c[yy] = 0u;
   }
+  // (the sweep's steps written out, with its one call of load a step: on pair_sweep_tile this kernel has the same registers and
+  // instructions within two, and the call ran 1 to 4 % slower; profiles/pair_sweep_refactor.md, section 4)
+  const PairRowsAt cols{a, cap, reps};
+  const PairRows rows{a, cap};
   PairStage<kRepMaxW, kRepMaxTJ> stage;
-  if (t_begin < t_end) stage.load_indexed(a, cap, reps, lo + t_begin * w, min(hi, lo + t_begin * w + w), a, j0, j1, n_dims, 0, n_dims);
+  if (t_begin < t_end) stage.load(cols, lo + t_begin * w, min(hi, lo + t_begin * w + w), rows, j0, j1, n_dims, 0, n_dims);
   for (uint32_t t = t_begin; t < t_end; ++t) {
     const uint32_t i0 = lo + t * w, i1 = min(hi, i0 + w);  // positions in reps
     uint32_t ri[4];
@@ -147,7 +151,7 @@ __global__ __launch_bounds__(256, 1) void representatives_cover_kernel(const dou
       __syncthreads();
       const bool more = c0 + kPairDC < n_dims;  // this tile's next dimensions, or the next tile's first
       const uint32_t ni0 = more ? i0 : i0 + w;
-      if (more || t + 1 < t_end) stage.load_indexed(a, cap, reps, ni0, min(hi, ni0 + w), a, j0, j1, n_dims, more ? c0 + kPairDC : 0u, n_dims);
+      if (more || t + 1 < t_end) stage.load(cols, ni0, min(hi, ni0 + w), rows, j0, j1, n_dims, more ? c0 + kPairDC : 0u, n_dims);
       if (worker) pair_accumulate<KIND>(acc, As, Bs, s_metric, ti, tj, min((uint32_t)kPairDC, n_dims - c0), p);
     }
     // the epilogue: the scaled distance against the bound (a NaN compares false: within nothing); a representative below the
@@ -240,7 +244,8 @@ __global__ __launch_bounds__(256, 1) void representatives_hits_kernel(const doub
   const bool worker = rg < n_rg;
   const uint32_t ti = cg * 4, tj = (worker ? rg : 0) * TY;
   double acc[TY][4];
-  pair_tile_distances<KIND, TY, kRepMaxW, kRepMaxTJ>(acc, As, Bs, s_metric, a, i0, i1, a, j0, j1, n_dims, metric, p, ti, tj, worker);
+  const PairRows rows{a, je};  // (a plain view never reads its row count; what this kernel knows of it: the step's rows end at je)
+  pair_tile_distances<KIND, TY, kRepMaxW, kRepMaxTJ>(acc, As, Bs, s_metric, rows, i0, i1, rows, j0, j1, n_dims, metric, p, ti, tj, worker);
   const uint32_t mask = worker ? self_hit_mask<TY>(acc, TriTile{blockIdx.x, blockIdx.y, i0, i1, j0, j1, true}, ti, tj, max_distance) : 0u;
   // the epilogue: a thread's 4 columns are 4 bits of its row's word, OR-ed over the row's lanes
 #pragma unroll

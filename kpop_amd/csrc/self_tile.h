@@ -1,5 +1,5 @@
 // self_tile.h -- the self-join of a resident set, once: what clusters.hip, dbscan.hip, forest.hip and representatives.hip share around
-// the loop of pair_tile.h (one tile's distances: pair_tile_distances there).  The tile shapes and the folded upper triangle are
+// the loops of pair_tile.h (one tile's distances: pair_tile_distances there; a strip against many tiles: pair_sweep_tile).  The tile shapes and the folded upper triangle are
 // tri_tile.h's (plain integers); here are the triangle's host loop, the compare, the tile's forest in LDS, and the reductions over
 // the thread layout.
 #pragma once

@@ -17,7 +17,7 @@
 //     radix_sort_pairs_u64      (radix_sort.h, 16-bit keys) the row indices grouped by class, stable: ascending inside a class
 //     silhouette_tiles_kernel   the column tiles: positions, class, whether the class ends there
 //   silhouette_pass_kernel    a workgroup owns a row tile j0 .. j1 in natural order and walks the column tiles in order, the columns
-//                             gathered through the grouped order (PairStage::load_indexed), both tile shapes of self_shape.  After a
+//                             gathered through the grouped order (PairRowsAt, the sweep of pair_tile.h), both tile shapes of self_shape.  After a
 //                             tile a thread adds its four columns' distances onto its running sum of the row (the row itself and the
 //                             tile's edge add +0); where a class ends the row's n_cg lanes reduce (reduce_row_lanes: a fixed tree), one
 //                             division, and the mean is the row's own or folds into (other_mean, other_class).  A row tile's column
@@ -79,7 +79,7 @@ static SilWork silhouette_carve(void *base, uint32_t r1, uint32_t n_classes) {
 
 // a: the set's rows as the chain reads them (divided by their norms when the set normalises), both operands.  Row tile blockIdx.x:
 // rows j0 .. j0 + TJ, TJ = TY n_rg; a thread 4 columns x TY rows, n_cg n_rg = 256 in both shapes: every thread holds pairs.  The
-// many-tile step of pair_tile.h over the column tiles of segment blockIdx.y; perm: the grouped order.  own_out[r1]: written by the
+// sweep of pair_tile.h over the column tiles of segment blockIdx.y; perm: the grouped order.  own_out[r1]: written by the
 // segment that holds the row's class; other_out, ocls_out [gridDim.y][r1]: a segment's least mean to another class, merged in
 // segment order by silhouette_rows_kernel
 template <int KIND, int TY>
@@ -119,26 +119,17 @@ __global__ __launch_bounds__(256, 1) void silhouette_pass_kernel(const double *_
     best_c[yy] = kSilNone;
   }
   const auto sum = [](LaneSum x, LaneSum y) { return LaneSum{__dadd_rn(x.v, y.v)}; };
+  const PairRowsAt cols{a, r1, perm};
+  const PairRows rows{a, r1};
   PairStage<kSilMaxW, kSilMaxTJ> stage;
-  SilTile next = silhouette_tile(tiles, t_begin, t_end, r1, w);
-  if (t_begin < t_end) stage.load_indexed(a, r1, perm, next.i0, next.i1, a, j0, j1, n_dims, 0, n_dims);
-  for (uint32_t t = t_begin; t < t_end; ++t) {
-    const SilTile cur = next;
-    next = silhouette_tile(tiles, t + 1, t_end, r1, w);  // (asked for a tile ahead: it is needed under this tile's last step)
+  SilStep cur = silhouette_tile(tiles, t_begin, t_end, r1, w), nxt;
+  for (pair_sweep_open(stage, cols, cur, rows, j0, j1, n_dims); cur.i0 < cur.i1; cur = nxt) {
+    nxt = silhouette_tile(tiles, cur.t + 1, t_end, r1, w);
     uint32_t ri[4];
 #pragma unroll
     for (int x = 0; x < 4; ++x) ri[x] = (cur.i0 + ti + x < cur.i1) ? perm[cur.i0 + ti + x] : kSilNone;
     double acc[TY][4];
-    pair_zero(acc);
-    for (uint32_t c0 = 0; c0 < n_dims; c0 += kPairDC) {
-      __syncthreads();
-      stage.store(As, Bs, s_metric, metric, c0, n_dims);
-      __syncthreads();
-      const bool more = c0 + kPairDC < n_dims;  // this tile's next dimensions, or the next tile's first
-      if (more) stage.load_indexed(a, r1, perm, cur.i0, cur.i1, a, j0, j1, n_dims, c0 + kPairDC, n_dims);
-      else if (t + 1 < t_end) stage.load_indexed(a, r1, perm, next.i0, next.i1, a, j0, j1, n_dims, 0, n_dims);
-      pair_accumulate<KIND>(acc, As, Bs, s_metric, ti, tj, min((uint32_t)kPairDC, n_dims - c0), p);
-    }
+    pair_sweep_tile<KIND>(stage, acc, As, Bs, s_metric, cols, cur, nxt, rows, j0, j1, n_dims, metric, p, ti, tj, true);
     // the tile's distances onto the row's running sum, the columns ascending; the row itself and a column beyond the tile add +0
 #pragma unroll
     for (int yy = 0; yy < TY; ++yy) {

@@ -59,12 +59,13 @@ __global__ __launch_bounds__(256, 1) void within_tile_kernel(const double *__res
   double acc[TY][4];
   pair_zero(acc);
   PairStage<kWMaxW, kWMaxTJ> stage;
-  stage.load(a, i0, i1, b, j0, j1, n_dims, 0, n_dims);
+  const PairRows rows_a{a, r1}, rows_b{b, r2};
+  stage.load(rows_a, i0, i1, rows_b, j0, j1, n_dims, 0, n_dims);
   for (uint32_t c0 = 0; c0 < n_dims; c0 += kPairDC) {
     __syncthreads();
     stage.store(As, Bs, s_metric, metric, c0, n_dims);
     __syncthreads();
-    if (c0 + kPairDC < n_dims) stage.load(a, i0, i1, b, j0, j1, n_dims, c0 + kPairDC, n_dims);
+    if (c0 + kPairDC < n_dims) stage.load(rows_a, i0, i1, rows_b, j0, j1, n_dims, c0 + kPairDC, n_dims);
     if (worker) pair_accumulate<KIND>(acc, As, Bs, s_metric, ti, tj, min((uint32_t)kPairDC, n_dims - c0), p);
   }
   // the epilogue: compare where distance_rowwise_kernel stores (a NaN compares false: never a hit)

@@ -203,7 +203,10 @@ def test_the_kernels_are_built_from_their_own_file():
     src = open(os.path.join(csrc, "kmedoids.hip")).read()
     for kernel in KERNELS:
         assert kernel in src
-    assert "load_indexed_both" in src and "load_indexed(" in src and "reduce_row_lanes" in src and "pair_accumulate" in src
+    # gathered operands through the sweep of pair_tile.h, both kernels: its steps and the chain stand there and not here
+    assert src.count("pair_sweep_tile<KIND>(") >= 2 and src.count("PairRowsAt") >= 2 and "reduce_row_lanes" in src
+    assert "load_indexed" not in src and "stage.store(" not in src and "pair_accumulate<" not in src
+    assert "pair_accumulate<KIND>(" in open(os.path.join(csrc, "pair_tile.h")).read()
     assert "atomicAdd(double" not in src and "unsafeAtomicAdd" not in src  # no floating-point atomic
     # the grouping is written once: both files take it from the header
     for name in ("kmedoids.hip", "silhouette.hip"):

@@ -105,7 +105,9 @@ def test_the_kernels_are_built_from_their_own_file():
     src = open(os.path.join(ROOT, "kpop_amd", "csrc", "silhouette.hip")).read()
     for kernel in KERNELS:
         assert kernel in src
-    assert "load_indexed" in src and "reduce_row_lanes" in src and "radix_sort_pairs_u64" in src and "exclusive_scan" in src
+    assert "PairRowsAt" in src and "pair_sweep_tile<KIND>(" in src and "reduce_row_lanes" in src  # columns gathered, the sweep of pair_tile.h
+    assert "load_indexed" not in src and "stage.store(" not in src and "pair_accumulate<" not in src
+    assert "radix_sort_pairs_u64" in src and "exclusive_scan" in src
     assert "atomicAdd(double" not in src and "unsafeAtomicAdd" not in src  # no floating-point atomic
 
 
