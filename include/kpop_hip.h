@@ -1153,6 +1153,74 @@ int kpop_distance_kmedoids(const double *m, uint32_t rows, uint32_t n_dims, cons
                            uint32_t *class_of, double *dist, double *own_mean, uint32_t *class_rows, double *cost,
                            uint32_t *n_iter, int *converged);
 
+/* ------------------------------------------------- local outlier factor of a resident set, and of query rows (lof.hip)
+ * Does this row belong to the database at all?  kpop_knn_vote gives every query row a class however far it lies,
+ * kpop_dbscan's noise needs one global eps, and a k-th neighbour's distance is not comparable between a tight lineage and
+ * a loose one.  The local outlier factor (Breunig, Kriegel, Ng, Sander 2000) is a row's density relative to its
+ * neighbours' densities: about 1 inside any lineage, well above 1 for a contaminated sample, a mislabelled assembly or the
+ * first genome of a new lineage.  d(j, i) is the distance of every block above: the reference chain's (lib/Space.ml:182-205
+ * with the adaptors of lib/Matrix.ml:243-250) -- the bits kpop_refset_distance_rowwise writes under
+ * kpop_tune("distance_mfma", 0) -- symmetric bit for bit; no kpop_tune setting is read; a NaN distance is within nothing.
+ * k in 1 .. 128: k = 0 KPOP_ERR_INVALID, k > 128 KPOP_ERR_UNSUPPORTED.
+ * THE SET FORM scores every row j of the set against the OTHER rows; the pair i == j is never examined.
+ *   kdist[j]   = kpop_core_distances(rs, k + 1)[j], bit for bit: the k-th least of the numbers among d(j, i), i != j; a
+ *                zero is written as +0; the quiet NaN 0x7FF8000000000000 when there are fewer than k numbers.
+ *   N(j)       = { i != j : d(j, i) <= kdist[j] }: the WHOLE tie group of the k-th distance, as the paper defines it, so
+ *                the result does not depend on the row order.
+ *   n_neigh[j] = |N(j)|: at least k; 0 when kdist[j] is a NaN.
+ *   lrd[j]     = n_neigh[j] / S1(j), S1(j) the sum over N(j) of max(d(j, i), kdist[i]) -- the max compared as doubles, a
+ *                zero taken as +0.  IEEE division: +inf when S1 = 0 (a row with at least k exact copies), 0 when S1 = +inf.
+ *   lof[j]     = (S2(j) / n_neigh[j]) / lrd[j], S2(j) the sum over N(j) of lrd[i].  IEEE arithmetic with ONE declared
+ *                exception: inf / inf is 1.0 -- a row inside a clump of copies is as dense as its neighbours.  So a finite
+ *                lrd beside a clump gives +inf, and 0 / 0 gives a NaN.
+ *   A row with n_neigh = 0 gets the quiet NaN for lrd and lof.  A NaN term poisons the sum it is in; every NaN written is
+ *   the quiet NaN above, every zero +0.  Where a set holds more than k copies of a row, kpop_representatives_within(0)
+ *   first (INTEGRATION.md 6n says why).
+ * THE QUERY FORM (novelty) scores row q of m2 against the set AS IT STANDS; the set's rows are not re-scored.  set_kdist,
+ * set_lrd [r1]: the set form's kdist and lrd at the same k.  kdist_q = the k-th least of the numbers among d(q, i) over ALL
+ * i -- nothing is left out: a query equal to a set row has that row at distance 0; N(q) = { i : d(q, i) <= kdist_q };
+ * lrd_q = |N| / (the sum over N of max(d(q, i), set_kdist[i])); lof_q = (the sum over N of set_lrd[i] / |N|) / lrd_q; the
+ * conventions of the set form.  r1 < k: every row the NaN row (NaN, 0, NaN, NaN).  r2 = 0: KPOP_OK.
+ * THE SUMS S1 and S2 are f64 sums in an order that is a fixed function of r1 (and r2), n_dims and k: within a thread the
+ * columns ascend and a non-member adds +0, a row's lanes meet in a fixed tree, the column segments are added in segment
+ * order.  No floating-point atomic: the same bits on every run.  Against an exact sum of n = n_neigh non-negative terms,
+ * S is within n 2^-53 relative.
+ * LIMITS: there is NO known_rows -- a new row can lower old rows' k-distances; after kpop_refset_append the set form is
+ * called again in full.  Neither the matrix nor a neighbour list longer than k a row is formed; apart from the k-NN lists
+ * of kpop_dev_core_distances the workspace is O(r1), or O(slab x segments) for a slab of 16,384 query rows.  Every output
+ * pointer may be NULL.  The cost is three full rectangles of pairs: the lists, S1 and S2 (a NULL lof saves the third).
+ * MEASURED (100,000 rows, k = 20, one MI355X): 348.7 ms at 64 dimensions and 7,997 ms at 1,635 -- 0.856 and 0.863 of
+ * kpop_dev_core_distances(21) plus two kpop_dev_silhouette calls with one class, timed in the same process; 4,096 query
+ * rows against the 64-dimensional set 19.3 ms.  Semantics: INTEGRATION.md 6n; registers and timings: profiles/lof.md.  */
+/* (lib/Space.ml:182-205; lib/Matrix.ml:243-250.)  Host arrays [r1], each may be NULL.  r1 = 0: KPOP_OK.  Synchronises.   */
+int kpop_lof(kpop_refset *rs, uint32_t k, double *kdist, uint32_t *n_neigh, double *lrd, double *lof);
+/* bytes of d_work for kpop_dev_lof (lib/Space.ml:182-205 over the set against itself, see the block above), for the set's
+   r1 at the time of the call: 16 bytes a row for kdist and lrd, 12 bytes a row and column segment (16 of them at most)
+   for what a sweep leaves, then kpop_dev_core_distances_workspace_bytes(rs, k + 1); 0 for a k the call refuses          */
+uint64_t kpop_dev_lof_workspace_bytes(const kpop_refset *rs, uint32_t k);
+/* (lib/Space.ml:182-205; lib/Matrix.ml:243-250.)  Enqueues only, reads nothing back, allocates nothing.  d_kdist, d_lrd,
+   d_lof (f64 [r1]), d_n_neigh (u32 [r1]), each or NULL: kdist and lrd, which the body needs itself, then live in d_work. */
+int kpop_dev_lof(kpop_refset *rs, uint32_t k, void *d_work, double *d_kdist, uint32_t *d_n_neigh, double *d_lrd,
+                 double *d_lof, void *stream);
+/* unprepared convenience (lib/Matrix.ml:191-266 for the distances, m against itself): a temporary set over m, then
+   kpop_lof                                                                                                             */
+int kpop_distance_lof(const double *m, uint32_t rows, uint32_t n_dims, const double *metric, int kind, double p,
+                      int normalize, uint32_t k, double *kdist, uint32_t *n_neigh, double *lrd, double *lof);
+/* (lib/Space.ml:182-205; lib/Matrix.ml:243-250.)  The query form on host arrays: set_kdist, set_lrd [r1] (needed when
+   r1 >= k), m2 [r2][n_dims]; kdist, lrd, lof (f64 [r2]), n_neigh (u32 [r2]), each may be NULL.  Synchronises.           */
+int kpop_lof_score(kpop_refset *rs, uint32_t k, const double *set_kdist, const double *set_lrd, const double *m2,
+                   uint32_t r2, double *kdist, uint32_t *n_neigh, double *lrd, double *lof);
+/* bytes of d_work for kpop_dev_lof_score (lib/Space.ml:182-205, query rows against the set, see the block above): what
+   kpop_dev_lof takes for a slab of min(r2, 16,384) query rows, the lists being kpop_dev_knn_vote's without a class or a
+   tie table (with the slab's divided copy when the set normalises); it does not depend on r1.  0 for a k the call refuses */
+uint64_t kpop_dev_lof_score_workspace_bytes(const kpop_refset *rs, uint32_t r2, uint32_t k);
+/* (lib/Space.ml:182-205; lib/Matrix.ml:243-250.)  Enqueues only, reads nothing back, allocates nothing: the query rows in
+   slabs of 16,384, a slab's lists, then its two sweeps.  d_set_kdist, d_set_lrd [r1]; d_m2 [r2][n_dims]; the outputs as
+   in kpop_dev_lof, [r2].                                                                                                */
+int kpop_dev_lof_score(kpop_refset *rs, uint32_t k, const double *d_set_kdist, const double *d_set_lrd, const double *d_m2,
+                       uint32_t r2, void *d_work, double *d_kdist, uint32_t *d_n_neigh, double *d_lrd, double *d_lof,
+                       void *stream);
+
 /* ------------------------------------------------- k-mer database (KPopCountDB)
  * the operations of lib/KMerDB.ml that touch every count.  A database is the reference's
  * `storage: I32BAVector.t array` (lib/KMerDB.ml:54-63): n_cols spectra ("columns"), each a vector of n_rows int32

@@ -20,7 +20,8 @@ from .api import (check, COSINE, DNA_DS, DNA_SS, PROTEIN, EUCLIDEAN, METRIC_FLAT
                   dev_reachability_forest_workspace_bytes, dev_reachability_forest, distance_reachability_forest, reachability_cut,
                   Silhouette, dev_silhouette_workspace_bytes, dev_silhouette, distance_silhouette, silhouette_summary, dense_labels,
                   FarthestFirst, dev_farthest_first_workspace_bytes, dev_farthest_first, distance_farthest_first,
-                  KMedoids, dev_kmedoids_workspace_bytes, dev_kmedoids, distance_kmedoids)
+                  KMedoids, dev_kmedoids_workspace_bytes, dev_kmedoids, distance_kmedoids,
+                  Lof, dev_lof_workspace_bytes, dev_lof, dev_lof_score_workspace_bytes, dev_lof_score, distance_lof)
 
 __all__ = ["init", "device_count", "count_reads", "Twister", "ca", "metric_compute", "distance_rowwise",
            "distance_summary", "embeddings", "splits_gaps", "summarize_distances", "parse_distance", "KPopError", "DNA_DS", "DNA_SS", "PROTEIN", "EUCLIDEAN", "COSINE",
@@ -38,4 +39,5 @@ __all__ = ["init", "device_count", "count_reads", "Twister", "ca", "metric_compu
            "dev_reachability_forest_workspace_bytes", "dev_reachability_forest", "distance_reachability_forest", "reachability_cut",
            "Silhouette", "dev_silhouette_workspace_bytes", "dev_silhouette", "distance_silhouette", "silhouette_summary", "dense_labels",
            "FarthestFirst", "dev_farthest_first_workspace_bytes", "dev_farthest_first", "distance_farthest_first",
-           "KMedoids", "dev_kmedoids_workspace_bytes", "dev_kmedoids", "distance_kmedoids"]
+           "KMedoids", "dev_kmedoids_workspace_bytes", "dev_kmedoids", "distance_kmedoids",
+           "Lof", "dev_lof_workspace_bytes", "dev_lof", "dev_lof_score_workspace_bytes", "dev_lof_score", "distance_lof"]

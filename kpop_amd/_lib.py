@@ -232,6 +232,14 @@ SIGNATURES = {
     "kpop_dev_kmedoids": (C.c_int, [vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "kpop_distance_kmedoids": (C.c_int, [f64p, C.c_uint32, C.c_uint32, f64p, C.c_int, C.c_double, C.c_int, C.c_uint32, u32p, C.c_uint32, u32p, u32p, f64p, f64p,
                                          u32p, f64p, u32p, C.POINTER(C.c_int)]),
+    # the local outlier factor of a set, and of query rows against it (lof.hip)
+    "kpop_lof": (C.c_int, [vp, C.c_uint32, f64p, u32p, f64p, f64p]),
+    "kpop_dev_lof_workspace_bytes": (C.c_uint64, [vp, C.c_uint32]),
+    "kpop_dev_lof": (C.c_int, [vp, C.c_uint32, vp, vp, vp, vp, vp, vp]),
+    "kpop_distance_lof": (C.c_int, [f64p, C.c_uint32, C.c_uint32, f64p, C.c_int, C.c_double, C.c_int, C.c_uint32, f64p, u32p, f64p, f64p]),
+    "kpop_lof_score": (C.c_int, [vp, C.c_uint32, f64p, f64p, f64p, C.c_uint32, f64p, u32p, f64p, f64p]),
+    "kpop_dev_lof_score_workspace_bytes": (C.c_uint64, [vp, C.c_uint32, C.c_uint32]),
+    "kpop_dev_lof_score": (C.c_int, [vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp, vp, vp, vp, vp]),
 }
 
 

@@ -912,6 +912,27 @@ class RefSet:
             medoids = self.farthest_first(max_picks=int(medoids)).pick
         return _kmedoids_call(_lib.load().kpop_kmedoids, [self._h], self.info()["r1"], medoids, max_iter)
 
+    def lof(self, k=20):
+        """The local outlier factor of every row of the set against the other rows -> Lof(kdist f64 [r1], n_neigh u32 [r1], lrd f64 [r1],
+        lof f64 [r1]).  kdist: core_distances(k + 1), bit for bit; the neighbourhood of row j is every other row within kdist[j], the whole
+        tie group of the k-th distance; lrd = n_neigh / the sum of max(d(j, i), kdist[i]) over it; lof = (the mean of lrd[i] over it) /
+        lrd[j]: about 1 inside a lineage, well above 1 for a row that belongs nowhere.  A clump of more than k copies has lrd +inf and lof
+        1.0 (inf / inf is 1.0), a row beside it lof +inf; a row with fewer than k numeric distances gets NaN, 0, NaN, NaN.  k in 1 .. 128.
+        The same bits on every run.  No earlier result is a valid start: after append the call is made again in full (kpop_lof,
+        include/kpop_hip.h)."""
+        return _lof_call(_lib.load().kpop_lof, [self._h, _min_pts(k)], self.info()["r1"])
+
+    def lof_score(self, m2, k, kdist, lrd):
+        """The novelty score of the rows of m2 against the set as it stands -> Lof, one entry a row of m2.  kdist, lrd: what self.lof(k)
+        returned (the arrays or the whole tuple's fields), at the same k.  Nothing is left out: a query equal to a set row has that row at
+        distance 0.  The set's rows are not re-scored (kpop_lof_score, include/kpop_hip.h)."""
+        i = self.info()
+        m2 = _query_rows(m2, i["n_dims"])
+        kdist, lrd = _c(kdist, np.float64), _c(lrd, np.float64)
+        if kdist.shape != (i["r1"],) or lrd.shape != (i["r1"],):
+            raise ValueError("kdist, lrd: the set form's arrays, one entry for each of the set's %d rows" % i["r1"])
+        return _lof_call(_lib.load().kpop_lof_score, [self._h, _min_pts(k), _ptr(kdist), _ptr(lrd), _ptr(m2), m2.shape[0]], m2.shape[0])
+
     def spanning_forest(self, max_distance=float("inf")):
         """The single-linkage tree of the set: the minimum spanning forest of the graph that joins rows i < j iff d(j, i) <= max_distance,
         under the order (d, i, j) -> (edge_i u32, edge_j u32, edge_dist f64, labels u32 [r1]).  The order is strict, so the forest is
@@ -1584,6 +1605,42 @@ def distance_kmedoids(m, metric, medoids, kind=EUCLIDEAN, p=2.0, normalize=True,
     kpop_distance_kmedoids -> KMedoids"""
     lead, rows = _set_geometry(m, metric, kind, p, normalize)
     return _kmedoids_call(_lib.load().kpop_distance_kmedoids, lead, rows, medoids, max_iter)
+
+
+Lof = collections.namedtuple("Lof", "kdist n_neigh lrd lof")
+
+
+def _lof_call(fn, lead, rows):
+    n = max(rows, 1)
+    res = (np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.float64))
+    check(fn(*lead, *_pointers(res)))
+    return Lof(*[x[:rows] for x in res])
+
+
+def dev_lof_workspace_bytes(rs, k):
+    """the size of d_work for dev_lof, for the set's r1 at the time of the call; 0 for a k the call refuses"""
+    return int(_lib.load().kpop_dev_lof_workspace_bytes(rs.handle, _min_pts(k)))
+
+
+def dev_lof(rs, k, d_work, d_kdist=None, d_n_neigh=None, d_lrd=None, d_lof=None, stream=0):
+    """enqueue only: d_kdist / d_lrd / d_lof (f64 [r1]) and d_n_neigh (u32 [r1]) as RefSet.lof returns them, each or None"""
+    check(_lib.load().kpop_dev_lof(rs.handle, _min_pts(k), d_work, d_kdist, d_n_neigh, d_lrd, d_lof, stream))
+
+
+def dev_lof_score_workspace_bytes(rs, r2, k):
+    """the size of d_work for dev_lof_score over r2 query rows: a slab's lists and sums, whatever the set's r1; 0 for a k the call refuses"""
+    return int(_lib.load().kpop_dev_lof_score_workspace_bytes(rs.handle, int(r2), _min_pts(k)))
+
+
+def dev_lof_score(rs, k, d_set_kdist, d_set_lrd, d_m2, r2, d_work, d_kdist=None, d_n_neigh=None, d_lrd=None, d_lof=None, stream=0):
+    """enqueue only: d_set_kdist / d_set_lrd (f64 [r1]) from dev_lof at the same k, d_m2 (f64 [r2][n_dims]); the outputs as in dev_lof, [r2]"""
+    check(_lib.load().kpop_dev_lof_score(rs.handle, _min_pts(k), d_set_kdist, d_set_lrd, d_m2, int(r2), d_work, d_kdist, d_n_neigh, d_lrd, d_lof, stream))
+
+
+def distance_lof(m, metric, k=20, kind=EUCLIDEAN, p=2.0, normalize=True):
+    """RefSet(m, ...).lof(k) without keeping the set: one call of kpop_distance_lof -> Lof"""
+    lead, rows = _set_geometry(m, metric, kind, p, normalize)
+    return _lof_call(_lib.load().kpop_distance_lof, lead + [_min_pts(k)], rows)
 
 
 def dense_labels(labels):

@@ -485,6 +485,13 @@ int knn_run_leave_self_out_lists(int kind, const double *a, uint32_t r1, uint32_
   return knn_passes_of_kind<true>(kind, a, r1, a + (uint64_t)first_row * n_dims, n_rows, n_dims, metric, p, k, nullptr, first_row, nullptr, 0, w, n_seg, false, st);
 }
 
+// (knn_lists.h) the same two passes for query rows b, nobody left out: w.m_n, w.m_tau again, for a caller that wants every query row's
+// k-th key over the whole set (lof.hip).  r1 > 0
+int knn_run_lists(int kind, const double *a, uint32_t r1, const double *b, uint32_t r2, uint32_t n_dims, const double *metric, double p, uint32_t k, const KnnWork &w,
+                  uint32_t *n_seg, hipStream_t st) {
+  return knn_passes_of_kind<false>(kind, a, r1, b, r2, n_dims, metric, p, k, nullptr, 0, nullptr, 0, w, n_seg, false, st);
+}
+
 // the body of both entry points: enqueues only
 static int knn_dev(kpop_refset *rs, const uint32_t *d_class_of, uint32_t n_classes, const double *d_m2, uint32_t r2, uint32_t k, void *d_work,
                    uint32_t *d_out_class, uint32_t *d_out_votes, uint32_t *d_out_n, double *d_out_first_dist, hipStream_t st, const char *who) {

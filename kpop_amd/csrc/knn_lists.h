@@ -158,5 +158,13 @@ int knn_run_leave_out_passes(int kind, const double *a, uint32_t r1, uint32_t fi
 // class array, no tie table: the tie pass settles WHICH rows share the k-th key, never its value (reachability.hip's core distances)
 int knn_run_leave_self_out_lists(int kind, const double *a, uint32_t r1, uint32_t first_row, uint32_t n_rows, uint32_t n_dims, const double *metric, double p,
                                  uint32_t k, const KnnWork &w, uint32_t *n_seg, hipStream_t st);
+// the same two for query rows b with nobody left out: every query row's k-th key over the whole set (lof.hip's query form).  r1 > 0
+int knn_run_lists(int kind, const double *a, uint32_t r1, const double *b, uint32_t r2, uint32_t n_dims, const double *metric, double p, uint32_t k, const KnnWork &w,
+                  uint32_t *n_seg, hipStream_t st);
+
+// reachability.hip: every row's core distance at min_pts (in 1 .. kKMaxK + 1, checked by the caller; r1 > 0) into d_core[r1], the set
+// walked in slabs whose lists are d_work's core_workspace_bytes.  Enqueues only.  lof.hip's k-distances are these at min_pts = k + 1
+uint64_t core_workspace_bytes(uint32_t r1, uint32_t min_pts, uint32_t n_dims);
+int core_dev(kpop_refset *rs, uint32_t min_pts, void *d_work, double *d_core, hipStream_t st);
 
 }  // namespace kpop

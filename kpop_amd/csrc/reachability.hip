@@ -57,8 +57,9 @@ static int reach_check_min_pts(uint32_t min_pts, const char *who) {
 
 // The slab rule: slabs of kRcSlabRows rows, the last one what is left.  A slab's bytes are knn_carve's without a query side, a class
 // or a tie table: a row takes (12 k + 8) bytes a segment of its strip (the segments' lists), 12 k for the merged list and 16 more; a
-// slab of 16,384 rows is cut into 1 segment (k > 32) or 2 (k <= 32), a shorter last slab into more -- hence the larger of the two
-static uint64_t core_workspace_bytes(uint32_t r1, uint32_t min_pts, uint32_t n_dims) {
+// slab of 16,384 rows is cut into 1 segment (k > 32) or 2 (k <= 32), a shorter last slab into more -- hence the larger of the two.
+// (Declared in knn_lists.h, with core_dev: lof.hip's k-distances)
+uint64_t core_workspace_bytes(uint32_t r1, uint32_t min_pts, uint32_t n_dims) {
   const uint32_t k = min_pts - 1;
   if (k == 0 || k >= r1) return 256;
   const uint32_t slab = std::min(r1, kRcSlabRows), last = r1 % slab ? r1 % slab : slab;
@@ -66,7 +67,7 @@ static uint64_t core_workspace_bytes(uint32_t r1, uint32_t min_pts, uint32_t n_d
 }
 
 // the body of the core distances' entry points: enqueues only.  min_pts is checked, r1 > 0
-static int core_dev(kpop_refset *rs, uint32_t min_pts, void *d_work, double *d_core, hipStream_t st) {
+int core_dev(kpop_refset *rs, uint32_t min_pts, void *d_work, double *d_core, hipStream_t st) {
   const uint32_t r1 = rs->r1, D = rs->n_dims, k = min_pts - 1;
   const dim3 rows_grid(std::min(div_up(r1, 256), 4096u));
   if (k == 0 || k >= r1) {
