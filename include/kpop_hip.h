@@ -1041,6 +1041,69 @@ int kpop_distance_silhouette(const double *m, uint32_t rows, uint32_t n_dims, co
 int kpop_silhouette_summary(uint32_t r1, const uint32_t *class_of, uint32_t n_classes, const double *silhouette,
                             double *class_mean, double *overall_mean);
 
+/* ------------------------------------------------- class linkage: the distances between every two classes, and their tree
+ * The labelled-set calls above answer questions about rows; this one answers them about the CLASSES: which two touch and
+ * through which two rows, how wide a class is, how far apart two classes are on average, and what tree they form (the
+ * reference's README section 5.3, "Pseudo-phylogenetic trees", is empty).  class_of[r1]: a class in [0, n_classes), or
+ * KPOP_NO_CLASS for a row that is LEFT OUT of everything.  d(i, j) is kpop_silhouette's distance: the reference chain's
+ * (lib/Space.ml:182-205 with the adaptors of lib/Matrix.ml:243-250), the bits kpop_refset_distance_rowwise writes on the
+ * vector pipe with the set's rows as the query, symmetric bit for bit; the pair i == j is never examined; no kpop_tune
+ * setting is read.  P(a, b), a != b: the pairs of one row of a and one row of b; P(a, a): the pairs i < j of two rows of a.
+ *   class_rows[a]     the rows of class a
+ *   mean_dist[a][b]   the sum of d over P(a, b) divided by |P(a, b)|; P empty (an empty class, the diagonal of a class of
+ *                     one row): the quiet NaN 0x7FF8000000000000; one NaN distance in P makes the mean a NaN
+ *   min_dist, max_dist  the least and the greatest d over the pairs of P whose distance is a number, -0 as +0; no such
+ *                     pair: the declared NaN
+ *   min_i < min_j     the two rows of the least pair under the strict order (d with -0 as +0, i, j), i < j the natural row
+ *                     indices (which of them lies in which class is class_of's to say); min_dist NaN: both KPOP_NO_CLASS
+ * The five tables are [n_classes x n_classes], row-major, and SYMMETRIC bit for bit: every unordered class pair is computed
+ * once and written to both halves.  max_dist[a][a] is the class's diameter, min_dist[a][a] and its pair the class's closest
+ * two rows.  THE SAME BITS ON EVERY RUN: no floating-point atomic, nothing that depends on timing; a sum is taken in an
+ * order that is a function of r1 and of the labelling alone (class_linkage.hip's header writes it down).  min_dist,
+ * max_dist, min_i and min_j do not depend on any order: under a renumbering of the classes the tables are permuted and
+ * nothing else changes.  mean_dist under a renumbering stays within (N + 2) 2^-53 relative of the exact mean, N = n_a n_b
+ * (n_a^2 on the diagonal), but is NOT promised bit for bit: the class that supplies a strip's rows may change.
+ * ERRORS: n_classes == 0: KPOP_ERR_INVALID; n_classes > 4,096: KPOP_ERR_UNSUPPORTED (the tables are n_classes^2 entries:
+ * 134 MB each at 4,096); the workspace-bytes call returns 0 for both.  r1 = 0: KPOP_OK, every class_rows 0, every table
+ * entry its NaN / KPOP_NO_CLASS.  No known_rows: after kpop_refset_append the call is made again in full.  Neither the
+ * r1 x r1 matrix nor an r1 x n_classes table is formed.  MEASURED: profiles/class_linkage.md.                          */
+
+/* the set on the handle.  Host arrays, each may be NULL: class_rows [n_classes]; the others [n_classes^2].  A class_of[i]
+   >= n_classes that is not KPOP_NO_CLASS is KPOP_ERR_INVALID.  Synchronises.                                            */
+int kpop_class_linkage(kpop_refset *rs, const uint32_t *class_of, uint32_t n_classes, uint32_t *class_rows,
+                       double *mean_dist, double *min_dist, double *max_dist, uint32_t *min_i, uint32_t *min_j);
+/* bytes of d_work for kpop_dev_class_linkage (lib/Space.ml:182-205 over the set against itself, see the block above), for
+   the set's r1 at the time of the call: the grouping and (r1 / TJ + 1 + n_classes) n_classes partials of 32 bytes, TJ the
+   tile shape's strip (64 rows, 256 from 65,536 rows on); 0 for an n_classes the call refuses                           */
+uint64_t kpop_dev_class_linkage_workspace_bytes(const kpop_refset *rs, uint32_t n_classes);
+/* enqueues only on `stream`: reads nothing back, allocates nothing.  d_class_of is TRUSTED and guarded: an entry that is
+   no class counts as left out.  Every output pointer may be NULL (lib/Space.ml:182-205, see the block above)            */
+int kpop_dev_class_linkage(kpop_refset *rs, const uint32_t *d_class_of, uint32_t n_classes, void *d_work,
+                           uint32_t *d_class_rows, double *d_mean_dist, double *d_min_dist, double *d_max_dist,
+                           uint32_t *d_min_i, uint32_t *d_min_j, void *stream);
+/* without keeping a set (Matrix.get_distance_rowwise's operands, lib/Matrix.ml:191-266, m against itself): a temporary set
+   over m, then kpop_class_linkage                                                                                        */
+int kpop_distance_class_linkage(const double *m, uint32_t rows, uint32_t n_dims, const double *metric, int kind, double p,
+                                int normalize, const uint32_t *class_of, uint32_t n_classes, uint32_t *class_rows,
+                                double *mean_dist, double *min_dist, double *max_dist, uint32_t *min_i, uint32_t *min_j);
+
+#define KPOP_LINK_SINGLE 0   /* pass min_dist */
+#define KPOP_LINK_COMPLETE 1 /* pass max_dist */
+#define KPOP_LINK_AVERAGE 2  /* pass mean_dist: UPGMA, weighted by class_rows */
+/* pure host arithmetic, no GPU and no kpop_init: the agglomeration of the classes under dist[n_classes^2] (a table of
+   kpop_class_linkage over the reference chain's distances, lib/Space.ml:182-205, or any other), of which only the entries
+   dist[a][b], a < b, of classes with rows are read.  The leaves are the classes with class_rows > 0, their node ids their
+   class numbers; merge t makes node n_classes + t.  Each step merges the two live nodes least under (distance with -0 as
+   +0, lower id, higher id): left[t] < right[t] their ids, height[t] that distance (-0 as +0), size[t] the rows under the
+   new node.  The new node's distance to a third node z: single min(d_xz, d_yz), complete max, average
+   (n_x d_xz + n_y d_yz) / (n_x + n_y) in exactly that order in f64, x the left node; a NaN operand gives a NaN.  A NaN is
+   never the least: when no two live nodes have a number between them the call stops with *n_merges below leaves - 1, and
+   the result is a forest.  All three linkages are reducible: the heights never decrease.  left, right, height, size:
+   n_classes - 1 entries each.  KPOP_ERR_INVALID: a null pointer, n_classes == 0, another linkage; n_classes > 4,096:
+   KPOP_ERR_UNSUPPORTED.                                                                                                  */
+int kpop_class_tree(uint32_t n_classes, const uint32_t *class_rows, const double *dist, int linkage, uint32_t *n_merges,
+                    uint32_t *left, uint32_t *right, double *height, uint32_t *size);
+
 /* ------------------------------------------------- farthest-first traversal of a resident set (k diverse rows, every k)
  * kpop_representatives_within thins a set at a radius that is known; this is its partner when a COUNT is known, or
  * nothing: one ordering of the rows (Gonzalez 1985) whose every prefix is a cover of the set, its radius written beside

@@ -19,6 +19,8 @@ from .api import (check, COSINE, DNA_DS, DNA_SS, PROTEIN, EUCLIDEAN, METRIC_FLAT
                   dev_dbscan_workspace_bytes, dev_dbscan, distance_dbscan, dev_core_distances_workspace_bytes, dev_core_distances,
                   dev_reachability_forest_workspace_bytes, dev_reachability_forest, distance_reachability_forest, reachability_cut,
                   Silhouette, dev_silhouette_workspace_bytes, dev_silhouette, distance_silhouette, silhouette_summary, dense_labels,
+                  ClassLinkage, dev_class_linkage_workspace_bytes, dev_class_linkage, distance_class_linkage, ClassTree, class_tree, class_tree_newick,
+                  LINK_SINGLE, LINK_COMPLETE, LINK_AVERAGE,
                   FarthestFirst, dev_farthest_first_workspace_bytes, dev_farthest_first, distance_farthest_first,
                   KMedoids, dev_kmedoids_workspace_bytes, dev_kmedoids, distance_kmedoids,
                   Lof, dev_lof_workspace_bytes, dev_lof, dev_lof_score_workspace_bytes, dev_lof_score, distance_lof)
@@ -38,6 +40,8 @@ __all__ = ["init", "device_count", "count_reads", "Twister", "ca", "metric_compu
            "dev_dbscan_workspace_bytes", "dev_dbscan", "distance_dbscan", "dev_core_distances_workspace_bytes", "dev_core_distances",
            "dev_reachability_forest_workspace_bytes", "dev_reachability_forest", "distance_reachability_forest", "reachability_cut",
            "Silhouette", "dev_silhouette_workspace_bytes", "dev_silhouette", "distance_silhouette", "silhouette_summary", "dense_labels",
+           "ClassLinkage", "dev_class_linkage_workspace_bytes", "dev_class_linkage", "distance_class_linkage", "ClassTree", "class_tree", "class_tree_newick",
+           "LINK_SINGLE", "LINK_COMPLETE", "LINK_AVERAGE",
            "FarthestFirst", "dev_farthest_first_workspace_bytes", "dev_farthest_first", "distance_farthest_first",
            "KMedoids", "dev_kmedoids_workspace_bytes", "dev_kmedoids", "distance_kmedoids",
            "Lof", "dev_lof_workspace_bytes", "dev_lof", "dev_lof_score_workspace_bytes", "dev_lof_score", "distance_lof"]

@@ -220,6 +220,13 @@ SIGNATURES = {
     "kpop_distance_silhouette": (C.c_int, [f64p, C.c_uint32, C.c_uint32, f64p, C.c_int, C.c_double, C.c_int, u32p, C.c_uint32, f64p, f64p, u32p, f64p, u32p,
                                            u32p, f64p]),
     "kpop_silhouette_summary": (C.c_int, [C.c_uint32, u32p, C.c_uint32, f64p, f64p, f64p]),
+    # the distances between every two classes of a labelled set, and the classes' tree (class_linkage.hip)
+    "kpop_class_linkage": (C.c_int, [vp, u32p, C.c_uint32, u32p, f64p, f64p, f64p, u32p, u32p]),
+    "kpop_dev_class_linkage_workspace_bytes": (C.c_uint64, [vp, C.c_uint32]),
+    "kpop_dev_class_linkage": (C.c_int, [vp, vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "kpop_distance_class_linkage": (C.c_int, [f64p, C.c_uint32, C.c_uint32, f64p, C.c_int, C.c_double, C.c_int, u32p, C.c_uint32, u32p, f64p, f64p, f64p, u32p,
+                                              u32p]),
+    "kpop_class_tree": (C.c_int, [C.c_uint32, u32p, f64p, C.c_int, u32p, u32p, u32p, f64p, u32p]),
     # the farthest-first traversal: k diverse rows for every k (farthest_first.hip)
     "kpop_farthest_first": (C.c_int, [vp, C.c_uint32, C.c_double, u32p, C.c_uint32, u32p, u32p, f64p, u32p, u32p, f64p, u32p]),
     "kpop_dev_farthest_first_workspace_bytes": (C.c_uint64, [vp, C.c_uint32]),

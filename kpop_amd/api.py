@@ -884,6 +884,18 @@ class RefSet:
         after append the call is made again in full (kpop_silhouette, include/kpop_hip.h)."""
         return _silhouette_call(_lib.load().kpop_silhouette, [self._h], self.info()["r1"], class_of, n_classes)
 
+    def class_linkage(self, class_of, n_classes=None):
+        """The distances between every two classes of the set under a labelling -> ClassLinkage(class_rows u32 [n_classes], mean_dist,
+        min_dist, max_dist f64 [n_classes, n_classes], min_i, min_j u32 [n_classes, n_classes]).  class_of[i] is a class in [0, n_classes)
+        or NO_CLASS: the row is left out of everything.  Over the pairs of one row of a and one row of b (on the diagonal: the pairs i < j
+        of two rows of a): the mean, the least and the greatest distance, and the two rows min_i < min_j of the least pair under
+        (d, i, j); no pair (an empty class, the diagonal of a class of one row): NaN and NO_CLASS.  max_dist[a, a] is a class's diameter.
+        All five tables are symmetric bit for bit; the same bits on every run; under a renumbering of the classes min_dist, max_dist,
+        min_i and min_j are permuted and nothing else, mean_dist stays within its rounding.  n_classes None: one more than the largest
+        class; at most 4,096.  No earlier result is a valid start: after append the call is made again in full (kpop_class_linkage,
+        include/kpop_hip.h).  class_tree makes the classes' tree of a table."""
+        return _class_linkage_call(_lib.load().kpop_class_linkage, [self._h], self.info()["r1"], class_of, n_classes)
+
     def farthest_first(self, max_picks=None, cover_radius=-1.0, seeds=None):
         """The farthest-first traversal of the set -> FarthestFirst(pick u32 [n], pick_radius f64 [n], pick_parent u32 [n], rep_of u32 [r1],
         rep_dist f64 [r1], n_passes).  Every row has a cover distance (+inf at first) and a cover row (NOISE at first); a pick lowers the
@@ -1511,6 +1523,106 @@ def silhouette_summary(class_of, silhouette, n_classes=None):
     check(_lib.load().kpop_silhouette_summary(len(silhouette), _p(_nz(class_of, np.uint32), C.c_uint32), n_classes, _p(_nz(silhouette, np.float64), C.c_double),
                                               _p(class_mean, C.c_double), C.byref(overall)))
     return class_mean[:n_classes], float(overall.value)
+
+
+ClassLinkage = collections.namedtuple("ClassLinkage", "class_rows mean_dist min_dist max_dist min_i min_j")
+ClassTree = collections.namedtuple("ClassTree", "left right height size")
+LINK_SINGLE, LINK_COMPLETE, LINK_AVERAGE = 0, 1, 2
+LINK_MAX_CLASSES = 4096
+
+
+def _class_linkage_call(fn, lead, r1, class_of, n_classes):
+    class_of, n_classes = _left_out_classes(class_of, r1, n_classes)
+    nc = n_classes if 1 <= n_classes <= LINK_MAX_CLASSES else 1  # (the library refuses any other number of classes before it writes)
+    res = (np.zeros(nc, dtype=np.uint32), np.zeros((nc, nc), dtype=np.float64), np.zeros((nc, nc), dtype=np.float64), np.zeros((nc, nc), dtype=np.float64),
+           np.zeros((nc, nc), dtype=np.uint32), np.zeros((nc, nc), dtype=np.uint32))
+    check(fn(*lead, _ptr(class_of), n_classes, *_pointers(res)))
+    return ClassLinkage(*res)
+
+
+def dev_class_linkage_workspace_bytes(rs, n_classes):
+    """the size of d_work for dev_class_linkage, for the set's r1 at the time of the call; 0 for an n_classes the call refuses"""
+    return int(_lib.load().kpop_dev_class_linkage_workspace_bytes(rs.handle, int(n_classes)))
+
+
+def dev_class_linkage(rs, d_class_of, n_classes, d_work, d_class_rows=None, d_mean_dist=None, d_min_dist=None, d_max_dist=None, d_min_i=None, d_min_j=None,
+                      stream=0):
+    """enqueue only: d_class_rows (u32 [n_classes]), d_mean_dist / d_min_dist / d_max_dist (f64 [n_classes^2]), d_min_i / d_min_j (u32
+    [n_classes^2]) as RefSet.class_linkage returns them, each or None; d_class_of (u32, one a row of the set) is trusted: an entry that is
+    no class counts as left out"""
+    check(_lib.load().kpop_dev_class_linkage(rs.handle, d_class_of, int(n_classes), d_work, d_class_rows, d_mean_dist, d_min_dist, d_max_dist, d_min_i, d_min_j,
+                                             stream))
+
+
+def distance_class_linkage(m, metric, class_of, kind=EUCLIDEAN, p=2.0, normalize=True, n_classes=None):
+    """RefSet(m, ...).class_linkage(class_of, n_classes) without keeping the set: one call of kpop_distance_class_linkage -> ClassLinkage"""
+    lead, rows = _set_geometry(m, metric, kind, p, normalize)
+    return _class_linkage_call(_lib.load().kpop_distance_class_linkage, lead, rows, class_of, n_classes)
+
+
+def class_tree(class_rows, dist, linkage):
+    """The agglomeration of the classes under a table of RefSet.class_linkage -> ClassTree(left u32 [n], right u32 [n], height f64 [n], size
+    u32 [n]), n the merges.  linkage: LINK_SINGLE (pass min_dist), LINK_COMPLETE (max_dist) or LINK_AVERAGE (mean_dist: UPGMA weighted by
+    class_rows).  The leaves are the classes with rows, their ids their class numbers; merge t makes node n_classes + t of the two live
+    nodes least under (distance, lower id, higher id): left < right, height that distance, size the rows under the new node.  A NaN is
+    never the least: where no two live nodes have a number between them the merges stop and the result is a forest.  Host arithmetic
+    alone: no GPU, no init (kpop_class_tree, include/kpop_hip.h)."""
+    class_rows = np.asarray(class_rows)
+    if class_rows.ndim != 1 or (len(class_rows) and (class_rows.min() < 0 or class_rows.max() > 0xFFFFFFFF)):
+        raise ValueError("class_rows: one count of rows a class")
+    class_rows = _c(class_rows, np.uint32)
+    n_classes = len(class_rows)
+    dist = _c(dist, np.float64)
+    if dist.shape != (n_classes, n_classes):
+        raise ValueError("dist: a table of %d x %d distances" % (n_classes, n_classes))
+    n = n_classes - 1 if 2 <= n_classes <= LINK_MAX_CLASSES else 1  # (as above; one entry so that every pointer is valid)
+    left, right, size = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+    height = np.zeros(n, dtype=np.float64)
+    n_merges = C.c_uint32()
+    check(_lib.load().kpop_class_tree(n_classes, _p(_nz(class_rows, np.uint32), C.c_uint32), _p(_nz(dist, np.float64), C.c_double), int(linkage),
+                                      C.byref(n_merges), _p(left, C.c_uint32), _p(right, C.c_uint32), _p(height, C.c_double), _p(size, C.c_uint32)))
+    k = int(n_merges.value)
+    return ClassTree(left[:k], right[:k], height[:k], size[:k])
+
+
+def class_tree_newick(tree, n_classes, names=None):
+    """The Newick strings of a ClassTree, one a root in ascending node id: a leaf is names[class] (its class number without names), a branch's
+    length the height of the parent minus the height of the child (a leaf lies at height 0), written with repr's shortest digits.  Leaves
+    that no merge names are not written (class_tree does not say which classes have rows).  Plain Python: no library call."""
+    n_classes = int(n_classes)
+    left, right, height = [int(v) for v in tree.left], [int(v) for v in tree.right], [float(v) for v in tree.height]
+    if not len(left) == len(right) == len(height):
+        raise ValueError("tree: left, right and height of one length")
+    if names is not None and len(names) < n_classes:
+        raise ValueError("names: one a class")
+    child = set(left) | set(right)
+    for t, (a, b) in enumerate(zip(left, right)):
+        if not (0 <= a < b < n_classes + t):
+            raise ValueError("tree: merge %d joins nodes %d and %d" % (t, a, b))
+
+    def node_height(v):
+        return 0.0 if v < n_classes else height[v - n_classes]
+
+    def label(v):
+        return str(v) if names is None else str(names[v])
+
+    out = []
+    for root in range(n_classes, n_classes + len(left)):
+        if root in child:
+            continue
+        # (an explicit stack: a chain of 4,095 merges is deeper than Python's recursion limit)
+        text, stack = {}, [(root, False)]
+        while stack:
+            v, seen = stack.pop()
+            if v < n_classes:
+                text[v] = label(v)
+            elif not seen:
+                stack.extend([(v, True), (left[v - n_classes], False), (right[v - n_classes], False)])
+            else:
+                a, b = left[v - n_classes], right[v - n_classes]
+                text[v] = "(%s:%r,%s:%r)" % (text.pop(a), node_height(v) - node_height(a), text.pop(b), node_height(v) - node_height(b))
+        out.append(text[root] + ";")
+    return out
 
 
 FarthestFirst = collections.namedtuple("FarthestFirst", "pick pick_radius pick_parent rep_of rep_dist n_passes")
