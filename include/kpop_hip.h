@@ -1284,6 +1284,64 @@ int kpop_dev_lof_score(kpop_refset *rs, uint32_t k, const double *d_set_kdist, c
                        uint32_t r2, void *d_work, double *d_kdist, uint32_t *d_n_neigh, double *d_lrd, double *d_lof,
                        void *stream);
 
+/* ------------------------------------------------- density peaks of a resident set: nearest denser row, tree and cut
+ * (density_peaks.hip)  Clusters when neither a radius nor a count is known and the lineages differ in tightness
+ * (Rodriguez & Laio, Science 2014), and "the nearest row that ranks above me" for any score the caller holds: with
+ * assembly quality as the score, delta > radius marks the rows with no better genome within the radius.  d(j, i) is the
+ * distance of every block above: the reference chain's (lib/Space.ml:182-205 with the adaptors of lib/Matrix.ml:243-250)
+ * -- the bits kpop_refset_distance_rowwise writes under kpop_tune("distance_mfma", 0) -- symmetric bit for bit; no
+ * kpop_tune setting is read; the pair i == j is never examined; a NaN distance is no candidate; a zero is written as +0.
+ * DENSITY: density[r1] (f64) is the caller's, or NULL: density[i] = (double) degree[i], kpop_dbscan's at eps (1 + the
+ *   other rows within eps); eps is then required and a NaN eps is KPOP_ERR_INVALID.  With a density given eps is not read.
+ *   A row whose density is a NaN is LEFT OUT: it is nobody's candidate, its delta is the quiet NaN 0x7FF8000000000000,
+ *   its parent and its label are KPOP_NOISE.  -0 equals +0; +inf and -inf are numbers.
+ * RANK: row i ranks above row j iff density[i] > density[j], or the densities are equal and i < j: a strict total order
+ *   of the rows that are not left out.
+ * PARENT, DELTA: among the rows i that rank above j and whose d(j, i) is a number, parent[j] is the least under
+ *   (d with -0 as +0, i) -- ties of distance go to the smaller row index -- and delta[j] that distance.  None:
+ *   parent[j] = j, delta[j] = +inf, a ROOT (the top of the order, a row with a NaN in it, r1 = 1).  A parent ranks above
+ *   its child, so the parents form a forest; as the minimum of a strict order it is a function of the distances and the
+ *   densities alone: the same bits on every run.
+ * CUT: row j is a CENTRE iff it is a root, or delta[j] > min_delta && density[j] >= min_density.  labels[j] = j for a
+ *   centre, otherwise labels[parent[j]]: the centre's row index, labels[labels[j]] == labels[j].  counts[0]: the
+ *   centres, counts[1]: the roots, counts[2]: the rows left out.  A NaN threshold is KPOP_ERR_INVALID;
+ *   min_density = -inf is no density bar; min_delta = +inf makes only the roots centres.
+ * r1 = 0: KPOP_OK, the counts zero.  eps < 0: every degree is 1, every row ties, the rank is the row order.  There is NO
+ * known_rows: a new row changes degrees; after kpop_refset_append the call is made again in full.  Neither the matrix
+ * nor a neighbour list is formed; the workspace is O(r1).  The cost is the degree pass (a triangle, when no density is
+ * given), a 64-bit radix sort of r1 keys, and ONE triangle of pairs in rank order: the row at position q of the rank
+ * order meets only the positions below q.
+ * MEASURED (100,000 rows, one MI355X): with a given density 54.5 ms at 64 dimensions and 1,315 ms at 1,635 -- 0.41 and 0.39
+ * of kpop_dev_silhouette with one class, timed in the same process (0.5 by pair count); with the degree density 102.8 and
+ * 2,377 ms, the difference one kpop_dev_clusters_within.  Semantics: INTEGRATION.md 6p; registers and timings:
+ * profiles/density_peaks.md.                                                                                            */
+/* (lib/Space.ml:182-205; lib/Matrix.ml:243-250.)  Host arrays: density [r1] or NULL; density_out, delta (f64 [r1]),
+   parent, labels (u32 [r1]), counts (u32 [3]), each may be NULL.  Synchronises.                                         */
+int kpop_density_peaks(kpop_refset *rs, double eps, const double *density, double min_density, double min_delta,
+                       double *density_out, double *delta, uint32_t *parent, uint32_t *labels, uint32_t *counts);
+/* bytes of d_work for kpop_dev_density_peaks (lib/Space.ml:182-205 over the set against itself, see the block above),
+   for the set's r1 at the time of the call: O(r1) -- 12 bytes a row and column segment (16 of them), the sort's buffers,
+   two label buffers, and kpop_dev_dbscan_workspace_bytes for the degrees                                               */
+uint64_t kpop_dev_density_peaks_workspace_bytes(const kpop_refset *rs);
+/* (lib/Space.ml:182-205; lib/Matrix.ml:243-250.)  Enqueues only, reads nothing back, allocates nothing.  d_density
+   (f64 [r1]) or NULL; d_density_out, d_delta (f64 [r1]), d_parent, d_labels (u32 [r1]), d_counts (u32 [3]), each or
+   NULL: what the body needs itself then lives in d_work.  NULL d_labels and d_counts: no cut is made.                   */
+int kpop_dev_density_peaks(kpop_refset *rs, double eps, const double *d_density, double min_density, double min_delta,
+                           void *d_work, double *d_density_out, double *d_delta, uint32_t *d_parent, uint32_t *d_labels,
+                           uint32_t *d_counts, void *stream);
+/* unprepared convenience (lib/Matrix.ml:191-266 for the distances, m against itself): a temporary set over m, then
+   kpop_density_peaks                                                                                                   */
+int kpop_distance_density_peaks(const double *m, uint32_t rows, uint32_t n_dims, const double *metric, int kind, double p,
+                                int normalize, double eps, const double *density, double min_density, double min_delta,
+                                double *density_out, double *delta, uint32_t *parent, uint32_t *labels, uint32_t *counts);
+/* The CUT alone, of the arrays a call above returned, at other thresholds: host arithmetic, no GPU and no kpop_init, so
+   the thresholds can be chosen after a look at the decision graph (density, delta).  (No counterpart in the reference:
+   the distances behind delta are lib/Space.ml:182-205's.)  KPOP_ERR_INVALID for a NaN threshold and for a parent that is
+   neither KPOP_NOISE, the row itself, nor a row of the set ranking strictly above it -- the check that rules a cycle
+   out; nothing is written then.  labels (u32 [r1]) and counts (u32 [3]) may each be NULL.                               */
+int kpop_density_peaks_cut(uint32_t r1, const double *density, const double *delta, const uint32_t *parent,
+                           double min_density, double min_delta, uint32_t *labels, uint32_t *counts);
+
 /* ------------------------------------------------- k-mer database (KPopCountDB)
  * the operations of lib/KMerDB.ml that touch every count.  A database is the reference's
  * `storage: I32BAVector.t array` (lib/KMerDB.ml:54-63): n_cols spectra ("columns"), each a vector of n_rows int32

@@ -23,7 +23,8 @@ from .api import (check, COSINE, DNA_DS, DNA_SS, PROTEIN, EUCLIDEAN, METRIC_FLAT
                   LINK_SINGLE, LINK_COMPLETE, LINK_AVERAGE,
                   FarthestFirst, dev_farthest_first_workspace_bytes, dev_farthest_first, distance_farthest_first,
                   KMedoids, dev_kmedoids_workspace_bytes, dev_kmedoids, distance_kmedoids,
-                  Lof, dev_lof_workspace_bytes, dev_lof, dev_lof_score_workspace_bytes, dev_lof_score, distance_lof)
+                  Lof, dev_lof_workspace_bytes, dev_lof, dev_lof_score_workspace_bytes, dev_lof_score, distance_lof,
+                  DensityPeaks, dev_density_peaks_workspace_bytes, dev_density_peaks, distance_density_peaks, density_peaks_cut)
 
 __all__ = ["init", "device_count", "count_reads", "Twister", "ca", "metric_compute", "distance_rowwise",
            "distance_summary", "embeddings", "splits_gaps", "summarize_distances", "parse_distance", "KPopError", "DNA_DS", "DNA_SS", "PROTEIN", "EUCLIDEAN", "COSINE",
@@ -44,4 +45,5 @@ __all__ = ["init", "device_count", "count_reads", "Twister", "ca", "metric_compu
            "LINK_SINGLE", "LINK_COMPLETE", "LINK_AVERAGE",
            "FarthestFirst", "dev_farthest_first_workspace_bytes", "dev_farthest_first", "distance_farthest_first",
            "KMedoids", "dev_kmedoids_workspace_bytes", "dev_kmedoids", "distance_kmedoids",
-           "Lof", "dev_lof_workspace_bytes", "dev_lof", "dev_lof_score_workspace_bytes", "dev_lof_score", "distance_lof"]
+           "Lof", "dev_lof_workspace_bytes", "dev_lof", "dev_lof_score_workspace_bytes", "dev_lof_score", "distance_lof",
+           "DensityPeaks", "dev_density_peaks_workspace_bytes", "dev_density_peaks", "distance_density_peaks", "density_peaks_cut"]

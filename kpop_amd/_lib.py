@@ -247,6 +247,13 @@ SIGNATURES = {
     "kpop_lof_score": (C.c_int, [vp, C.c_uint32, f64p, f64p, f64p, C.c_uint32, f64p, u32p, f64p, f64p]),
     "kpop_dev_lof_score_workspace_bytes": (C.c_uint64, [vp, C.c_uint32, C.c_uint32]),
     "kpop_dev_lof_score": (C.c_int, [vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp, vp, vp, vp, vp]),
+    # density peaks: every row's nearest denser row, their forest and its cut (density_peaks.hip)
+    "kpop_density_peaks": (C.c_int, [vp, C.c_double, f64p, C.c_double, C.c_double, f64p, f64p, u32p, u32p, u32p]),
+    "kpop_dev_density_peaks_workspace_bytes": (C.c_uint64, [vp]),
+    "kpop_dev_density_peaks": (C.c_int, [vp, C.c_double, vp, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp, vp]),
+    "kpop_distance_density_peaks": (C.c_int, [f64p, C.c_uint32, C.c_uint32, f64p, C.c_int, C.c_double, C.c_int, C.c_double, f64p, C.c_double, C.c_double, f64p, f64p,
+                                              u32p, u32p, u32p]),
+    "kpop_density_peaks_cut": (C.c_int, [C.c_uint32, f64p, f64p, u32p, C.c_double, C.c_double, u32p, u32p]),
 }
 
 

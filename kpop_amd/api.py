@@ -945,6 +945,17 @@ class RefSet:
             raise ValueError("kdist, lrd: the set form's arrays, one entry for each of the set's %d rows" % i["r1"])
         return _lof_call(_lib.load().kpop_lof_score, [self._h, _min_pts(k), _ptr(kdist), _ptr(lrd), _ptr(m2), m2.shape[0]], m2.shape[0])
 
+    def density_peaks(self, eps=None, density=None, min_density=float("-inf"), min_delta=None):
+        """Density peaks (Rodriguez & Laio 2014): for every row the distance delta to, and the index parent of, the nearest row that ranks
+        above it -> DensityPeaks(density f64 [r1], delta f64 [r1], parent u32 [r1], labels u32 [r1], counts u32 [3]).  density: one score a
+        row (assembly quality, lof().lrd, ...), or None: dbscan(eps, .)'s degree as doubles.  Row i ranks above row j iff its density is
+        higher, or equal and i < j; a row without anybody above it at a numeric distance is a ROOT (parent itself, delta +inf); a row
+        whose density is a NaN is left out (delta NaN, parent and label NOISE).  min_delta given: a row is a CENTRE iff it is a root or
+        delta > min_delta and density >= min_density; labels[j] is the centre's row index that j reaches along its parents, counts =
+        (centres, roots, rows left out).  min_delta None: labels and counts are None -- look at (density, delta), then density_peaks_cut.
+        The same bits on every run.  After append the call is made again in full (kpop_density_peaks, include/kpop_hip.h)."""
+        return _density_peaks_call(_lib.load().kpop_density_peaks, [self._h], self.info()["r1"], eps, density, min_density, min_delta)
+
     def spanning_forest(self, max_distance=float("inf")):
         """The single-linkage tree of the set: the minimum spanning forest of the graph that joins rows i < j iff d(j, i) <= max_distance,
         under the order (d, i, j) -> (edge_i u32, edge_j u32, edge_dist f64, labels u32 [r1]).  The order is strict, so the forest is
@@ -1753,6 +1764,60 @@ def distance_lof(m, metric, k=20, kind=EUCLIDEAN, p=2.0, normalize=True):
     """RefSet(m, ...).lof(k) without keeping the set: one call of kpop_distance_lof -> Lof"""
     lead, rows = _set_geometry(m, metric, kind, p, normalize)
     return _lof_call(_lib.load().kpop_distance_lof, lead + [_min_pts(k)], rows)
+
+
+DensityPeaks = collections.namedtuple("DensityPeaks", "density delta parent labels counts")
+
+
+def _density_peaks_call(fn, lead, rows, eps, density, min_density, min_delta):
+    n = max(rows, 1)
+    if density is not None:
+        density = _c(density, np.float64)
+        if density.shape != (rows,):
+            raise ValueError("density: one score for each of the set's %d rows" % rows)
+    cut = min_delta is not None
+    res = (np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.uint32))
+    labels, counts = (np.zeros(n, dtype=np.uint32), np.zeros(3, dtype=np.uint32)) if cut else (None, None)
+    # (no eps: a NaN, which the library refuses when there is no density either)
+    check(fn(*lead, float("nan") if eps is None else float(eps), None if density is None else _ptr(density), float(min_density),
+             float(min_delta) if cut else float("inf"), *_pointers(res), _ptr(labels) if cut else None, _ptr(counts) if cut else None))
+    return DensityPeaks(res[0][:rows], res[1][:rows], res[2][:rows], labels[:rows] if cut else None, counts)
+
+
+def dev_density_peaks_workspace_bytes(rs):
+    """the size of d_work for dev_density_peaks, for the set's r1 at the time of the call"""
+    return int(_lib.load().kpop_dev_density_peaks_workspace_bytes(rs.handle))
+
+
+def dev_density_peaks(rs, eps, d_work, d_density=None, min_density=float("-inf"), min_delta=float("inf"), d_density_out=None, d_delta=None, d_parent=None,
+                      d_labels=None, d_counts=None, stream=0):
+    """enqueue only: d_density (f64 [r1]) or None for the degrees at eps; d_density_out / d_delta (f64 [r1]), d_parent / d_labels (u32 [r1]),
+    d_counts (u32 [3]) as RefSet.density_peaks returns them, each or None"""
+    check(_lib.load().kpop_dev_density_peaks(rs.handle, float(eps), d_density, float(min_density), float(min_delta), d_work, d_density_out, d_delta, d_parent,
+                                             d_labels, d_counts, stream))
+
+
+def distance_density_peaks(m, metric, kind=EUCLIDEAN, p=2.0, normalize=True, eps=None, density=None, min_density=float("-inf"), min_delta=None):
+    """RefSet(m, ...).density_peaks(eps, density, min_density, min_delta) without keeping the set: one call of kpop_distance_density_peaks ->
+    DensityPeaks"""
+    lead, rows = _set_geometry(m, metric, kind, p, normalize)
+    return _density_peaks_call(_lib.load().kpop_distance_density_peaks, lead, rows, eps, density, min_density, min_delta)
+
+
+def density_peaks_cut(density, delta, parent, min_density=float("-inf"), min_delta=float("inf")):
+    """The cut of a density-peak forest at other thresholds, on the host (no GPU, no init) -> (labels u32 [r1], counts u32 [3]): what
+    RefSet.density_peaks gives at these thresholds, from its density, delta and parent.  Refused: a NaN threshold, a parent that is
+    neither NOISE, the row itself, nor a row ranking strictly above it (kpop_density_peaks_cut, include/kpop_hip.h)."""
+    density, delta, parent = _c(density, np.float64), _c(delta, np.float64), np.asarray(parent)
+    if parent.ndim != 1 or (len(parent) and (parent.min() < 0 or parent.max() > 0xFFFFFFFF)):
+        raise ValueError("parent: one uint32 a row")
+    parent = _c(parent, np.uint32)
+    r1 = len(parent)
+    if density.shape != (r1,) or delta.shape != (r1,):
+        raise ValueError("density, delta, parent: one entry a row")
+    labels, counts = np.zeros(max(r1, 1), dtype=np.uint32), np.zeros(3, dtype=np.uint32)
+    check(_lib.load().kpop_density_peaks_cut(r1, _ptr(density), _ptr(delta), _ptr(parent), float(min_density), float(min_delta), _ptr(labels), _ptr(counts)))
+    return labels[:r1], counts
 
 
 def dense_labels(labels):

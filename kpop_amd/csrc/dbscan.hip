@@ -366,6 +366,27 @@ static int dbscan_dev(kpop_refset *rs, double eps, uint32_t min_pts, void *d_wor
   return KPOP_OK;
 }
 
+// the degree pass alone (declared in self_tile.h; density_peaks.hip's densities): the counters cleared, then dbscan_degree_kernel over
+// the triangle as dbscan_dev launches it.  The workspace is the whole call's, so that one carve describes both
+uint64_t dbscan_degree_workspace_bytes(uint32_t r1) { return dbscan_carve(nullptr, r1).bytes; }
+
+int dbscan_degree_dev(kpop_refset *rs, double eps, void *d_work, const uint32_t **cnt, hipStream_t st) {
+  const uint32_t r1 = rs->r1, D = rs->n_dims;
+  const SelfShape s = self_shape(r1);
+  const DbWork f = dbscan_carve(d_work, r1);
+  *cnt = f.cnt;
+  KPOP_HIP(hipMemsetAsync(f.cnt, 0, f.clear_bytes, st));
+  if (!(eps >= 0.0)) return 0;  // (no distance is negative: below zero every degree is 1)
+  const double *a;
+  KPOP_TRY(refset_chain_rows(rs, st, &a));
+  return by_kind(rs->kind, [&](auto K) {
+    return self_triangle_launch(s, r1, 0, [&](auto TY, dim3 grid, uint32_t ybase) {
+      dbscan_degree_kernel<decltype(K)::value, decltype(TY)::value><<<grid, dim3(256), 0, st>>>(a, s.w, r1, D, rs->metric, rs->p, eps, s.n_cg, s.n_rg, s.kf, f.n_rt, ybase,
+                                                                                               f.cnt, f.hit_map);
+    });
+  });
+}
+
 }  // namespace kpop
 
 using namespace kpop;

@@ -93,4 +93,9 @@ __device__ __forceinline__ T reduce_column_lanes(T v, uint32_t n_cg, Op op) {
   return v;
 }
 
+// dbscan.hip: the degree pass alone, for density_peaks.hip.  *cnt [r1], inside d_work's dbscan_degree_workspace_bytes: the OTHER rows
+// within eps of every row (kpop_dbscan's degree - 1), all zero for eps < 0.  Enqueues only; eps a number, r1 > 0
+uint64_t dbscan_degree_workspace_bytes(uint32_t r1);
+int dbscan_degree_dev(kpop_refset *rs, double eps, void *d_work, const uint32_t **cnt, hipStream_t st);
+
 }  // namespace kpop
